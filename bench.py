@@ -11,7 +11,13 @@ the reference's order, and the dense int32 label volume of both signs.
    entries -- the path shards over entries with no data-path collective, scaling = weak --
    and RCCL carries only the final statistics reduction.)
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").
+Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").  A plain run sets up, warms up, times the K
+steps and prints the headline (`value`, `ms_per_step`, ...).  Everything else the line can carry -- dispersion windows, the
++-3 sigma and multi-stream legs, per-kernel event times and the roofline, the beyond-cache leg, the analysis, multiple-structure
+and radius-sweep legs, the host upload and the CPU baselines -- runs only with --full.
+
+  --dump-outputs DIR   after the timed steps, write what the last timed step returned (blob statistics, voxel membership and
+                       label volumes of both signs; float64 / float32 .npy, seeded samples of the large arrays, < 64 MB in all)
 """
 import argparse
 import json
@@ -56,7 +62,12 @@ def parse_args():
     ap.add_argument("--no-beyond-cache", action="store_true", help="skip the informational leg on a working set larger than the Infinity Cache")
     ap.add_argument("--beyond-seconds", type=float, default=0.5, help="beyond-cache leg: timed region at least this long")
     ap.add_argument("--stream-seconds", type=float, default=0.5, help="multi-stream leg: entries are dealt to the streams until the timed region is at least this long")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every informational leg, profile pass and baseline (off: the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def csrc_sha16():
@@ -82,6 +93,55 @@ def algorithmic_bytes(kernel, n_vox, n_planes):
         "k_face_merge": 0,                                 # run lists of the rows on tile faces: KB per tile
     }
     return table.get(kernel)
+
+
+DUMP_BLOBS = 1 << 16        # per sign: blob rows kept in a dump (a seeded sample beyond that)
+DUMP_VOXELS = 1 << 20       # per sign: voxel rows (crs) kept
+DUMP_LABELS = 1 << 19       # label-volume voxels kept, the same positions for both signs
+DUMP_LIMIT = 64 * 10 ** 6   # bytes of all arrays of a dump (the caps above come to 50 MB at most)
+BLOB_FIELDS = ("n", "totalDensity", "centroid", "coordCenter", "volume", "firstKey", "group")
+
+
+def _seeded_rows(n, cap, seed):
+    """Sorted row indices: all n rows, or a fixed sample of `cap` of them (the same for the same n, cap and seed)."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=cap, replace=False))
+
+
+def canonical_voxels(crs, off):
+    """The voxels of a blob list, blob after blob as listed, each blob's voxels sorted by (col 0, col 1, col 2): a blob is a SET of
+    voxels -- the order inside it is whatever order the device's tiles emitted them in, and may change from run to run."""
+    blob = np.repeat(np.arange(len(off) - 1), np.diff(off))
+    return crs[np.lexsort((crs[:, 2], crs[:, 1], crs[:, 0], blob))]
+
+
+def dump_outputs(directory, green, red, shape, labels):
+    """What a caller of the timed step receives from its last call -- for the green and the red list: the per-blob statistics
+    (float64), the voxels of every blob (crs, float32: exact below 2^24; canonical order inside a blob) and, with labels, the
+    signed label volume at a seeded sample of positions (float64).  Arrays longer than their cap are cut to a seeded sample of
+    rows, so that two builds run with the same arguments compare element for element.  Returns {name: shape}."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    for seed, (tag, bl) in enumerate((("green", green), ("red", red))):
+        st = bl.stats()
+        rows = _seeded_rows(len(st["n"]), DUMP_BLOBS, 101 + seed)
+        for key in BLOB_FIELDS:
+            arrays["%s_%s" % (tag, key)] = np.asarray(st[key][rows], dtype=np.float64)
+        crs = canonical_voxels(*bl.voxels())
+        arrays[tag + "_voxels_crs"] = np.asarray(crs[_seeded_rows(len(crs), DUMP_VOXELS, 201 + seed)], dtype=np.float32)
+    if labels:
+        n_vox = int(np.prod(shape))
+        where = _seeded_rows(n_vox, DUMP_LABELS, 301)
+        arrays["labels_sample_index"] = where.astype(np.float64)
+        for tag, bl in (("green", green), ("red", red)):
+            arrays[tag + "_labels_sample"] = bl.labels(shape).reshape(-1)[where].astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def analysis_leg(ctx, case="c2_bench_entry", reps=5):
@@ -635,7 +695,7 @@ def main():
 
     # multiple-structure leg: its worker processes are spawned now, before the GPU is initialised here
     pool = None
-    if args.entries > 0:
+    if args.full and args.entries > 0:
         # the leg's figure is quoted with BOTH maps of an entry uploaded, as the reference's loader reads both (its workers inherit
         # the switch); the product's default -- the Fo-Fc grid follows only if the analysis asks for it -- is timed beside it
         os.environ["PDBEDA_EAGER_DIFF_MAP"] = "1"
@@ -687,8 +747,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:       # (what the last timed step returned, before any other pass replaces it)
+        dump_outputs(args.dump_outputs, keep[0], keep[1], dmap.unique_shape, labels)
     windows = []                      # dispersion: further windows of K steps each (never `value`)
-    for _ in range(max(0, args.windows)):
+    for _ in range(max(0, args.windows) if args.full else 0):
         barrier()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -701,7 +763,7 @@ def main():
 
     # ---- the same map at pdb_eda's own green / red default, +-(mean + 3 std) (densityAnalysis.py:148) -- informational, never `value`
     sigma3 = None
-    if args.nsd != 3.0 and not args.no_sigma3:
+    if args.full and args.nsd != 3.0 and not args.no_sigma3:
         cut3 = mean + 3.0 * std
         for _ in range(max(args.warmup, 2)):
             keep3 = dmap.full_blobs_pm(cut3, -cut3, labels=labels)
@@ -732,7 +794,7 @@ def main():
     # ---- multiple-structure mode on one GPU (informational, never `value`): S entries in flight, each on its own context
     # (HIP stream + arena pool) driven by its own host thread (ctypes releases the GIL); K steps dealt round-robin ----
     multi = None
-    if args.streams > 1:
+    if args.full and args.streams > 1:
         import threading
         lanes = []
         for k in range(args.streams):
@@ -800,57 +862,58 @@ def main():
             lane["keep"] = None
         lanes = lanes[:1]
 
-    # ---- per-kernel durations with HIP events on the library's stream (separate K-step pass) ----
-    ctx.profile_begin()
-    for _ in range(args.steps):
-        keep = step()
-    prof = ctx.profile_end()
-    # ONE clock for the roofline: HIP events on the launch stream.  An event pair around a launch also times the launch gap
-    # (~2 us): the gap is calibrated in this same run as (sum of the event times of a step - host-timed step) / launches and
-    # taken off every kernel, so the corrected kernel times add up to ms_per_step by construction (the rocprofv3 averages
-    # under profiles/ are the cross-check).
-    n_launch = sum(c for c, _ in prof.values()) / args.steps
-    step_events_us = 1e3 * sum(ms for _, ms in prof.values()) / args.steps
-    step_wall_us = 1e6 * elapsed / args.steps
-    gap_us = max(0.0, (step_events_us - step_wall_us) / n_launch)
-    per_kernel = {k: {"calls": c, "event_us": 1e3 * ms / c, "avg_us": max(1e3 * ms / c - gap_us, 0.0)} for k, (c, ms) in prof.items()}
-    dominant = max((k for k in prof if algorithmic_bytes(k, n_vox, 2)), key=lambda k: per_kernel[k]["avg_us"])
-    dom_avg_s = per_kernel[dominant]["avg_us"] * 1e-6
-    dom_bytes = algorithmic_bytes(dominant, n_vox, 2)
-    achieved = dom_bytes / dom_avg_s / 1e9
-    step_kernel_s = sum(v["avg_us"] * v["calls"] for v in per_kernel.values()) / args.steps * 1e-6
+    if args.full:
+        # ---- per-kernel durations with HIP events on the library's stream (separate K-step pass) ----
+        ctx.profile_begin()
+        for _ in range(args.steps):
+            keep = step()
+        prof = ctx.profile_end()
+        # ONE clock for the roofline: HIP events on the launch stream.  An event pair around a launch also times the launch gap
+        # (~2 us): the gap is calibrated in this same run as (sum of the event times of a step - host-timed step) / launches and
+        # taken off every kernel, so the corrected kernel times add up to ms_per_step by construction (the rocprofv3 averages
+        # under profiles/ are the cross-check).
+        n_launch = sum(c for c, _ in prof.values()) / args.steps
+        step_events_us = 1e3 * sum(ms for _, ms in prof.values()) / args.steps
+        step_wall_us = 1e6 * elapsed / args.steps
+        gap_us = max(0.0, (step_events_us - step_wall_us) / n_launch)
+        per_kernel = {k: {"calls": c, "event_us": 1e3 * ms / c, "avg_us": max(1e3 * ms / c - gap_us, 0.0)} for k, (c, ms) in prof.items()}
+        dominant = max((k for k in prof if algorithmic_bytes(k, n_vox, 2)), key=lambda k: per_kernel[k]["avg_us"])
+        dom_avg_s = per_kernel[dominant]["avg_us"] * 1e-6
+        dom_bytes = algorithmic_bytes(dominant, n_vox, 2)
+        achieved = dom_bytes / dom_avg_s / 1e9
+        step_kernel_s = sum(v["avg_us"] * v["calls"] for v in per_kernel.values()) / args.steps * 1e-6
 
-    # measured HBM traffic of the dominant kernel: the PMC passes committed under profiles/ count -- but only if they were
-    # taken on THESE kernel sources (the file carries the hash of pdb_eda_amd/csrc at collection time); otherwise null
-    traffic, rocprof_avg_us, kernels_traffic = None, None, None
-    try:
-        import glob
-        sha = csrc_sha16()
-        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):
-            with open(path) as fh:
-                pmc = json.load(fh)
-            if pmc.get("csrc_sha16") == sha and dominant in pmc["kernels"] and n == 256 and labels and args.nsd == 1.5:
-                traffic = pmc["kernels"][dominant]["hbm_bytes_per_launch_corrected"]
-                rocprof_avg_us = pmc.get("rocprofv3_avg_us", {}).get(dominant)     # (the kernel-trace average of the same sources, for comparison)
-                # every kernel of the step: measured HBM bytes per launch, its algorithmic bytes where it has any, and the ratio;
-                # "step": all of them against the 8 B / voxel of the labelling pass
-                kernels_traffic = {}
-                for k in per_kernel:
-                    if k in pmc["kernels"]:
-                        b, a = pmc["kernels"][k]["hbm_bytes_per_launch_corrected"], algorithmic_bytes(k, n_vox, 2)
-                        kernels_traffic[k] = {"hbm_bytes": b, "algorithmic_bytes": a or None, "traffic_ratio": round(b / a, 3) if a else None}
-                total = sum(v["hbm_bytes"] for v in kernels_traffic.values())
-                kernels_traffic["step"] = {"hbm_bytes": total, "algorithmic_bytes": 8 * n_vox, "traffic_ratio": round(total / (8 * n_vox), 3)}
-                break
-    except Exception:
-        traffic = None
+        # measured HBM traffic of the dominant kernel: the PMC passes committed under profiles/ count -- but only if they were
+        # taken on THESE kernel sources (the file carries the hash of pdb_eda_amd/csrc at collection time); otherwise null
+        traffic, rocprof_avg_us, kernels_traffic = None, None, None
+        try:
+            import glob
+            sha = csrc_sha16()
+            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):
+                with open(path) as fh:
+                    pmc = json.load(fh)
+                if pmc.get("csrc_sha16") == sha and dominant in pmc["kernels"] and n == 256 and labels and args.nsd == 1.5:
+                    traffic = pmc["kernels"][dominant]["hbm_bytes_per_launch_corrected"]
+                    rocprof_avg_us = pmc.get("rocprofv3_avg_us", {}).get(dominant)     # (the kernel-trace average of the same sources, for comparison)
+                    # every kernel of the step: measured HBM bytes per launch, its algorithmic bytes where it has any, and the ratio;
+                    # "step": all of them against the 8 B / voxel of the labelling pass
+                    kernels_traffic = {}
+                    for k in per_kernel:
+                        if k in pmc["kernels"]:
+                            b, a = pmc["kernels"][k]["hbm_bytes_per_launch_corrected"], algorithmic_bytes(k, n_vox, 2)
+                            kernels_traffic[k] = {"hbm_bytes": b, "algorithmic_bytes": a or None, "traffic_ratio": round(b / a, 3) if a else None}
+                    total = sum(v["hbm_bytes"] for v in kernels_traffic.values())
+                    kernels_traffic["step"] = {"hbm_bytes": total, "algorithmic_bytes": 8 * n_vox, "traffic_ratio": round(total / (8 * n_vox), 3)}
+                    break
+        except Exception:
+            traffic = None
 
     # ---- the same fused step on a working set LARGER than the 256 MiB Infinity Cache (informational, never `value`): the headline
     # re-labels ONE resident 64 MiB map, and FETCH_SIZE counts Infinity-Cache hits -- so this leg visits `n_bc` distinct resident maps
     # round-robin on ONE stream (each a rolled copy of the entry: other memory, the same statistics; inputs alone 8 x 64 MiB, and
     # every step writes a 64 MiB label volume): what it shows is whether the headline is inflated by the cache ----
     beyond = None
-    if not args.no_beyond_cache and n == 256:
+    if args.full and not args.no_beyond_cache and n == 256:
         n_bc = 8
         bc_t = [dens] + [torch.roll(dens, shifts=(17 * k, 31 * k, 5 * k), dims=(0, 1, 2)).contiguous() for k in range(1, n_bc)]
         bc_m = [dmap] + [_native.DeviceMap(ctx, t, header.geometry(), device_ptr=t.data_ptr()) for t in bc_t[1:]]
@@ -894,24 +957,25 @@ def main():
         del bc_m, bc_t
         keep = step()
 
-    # on-box device-to-device copy ceiling (report the roofline against the datasheet peak AND a measured ceiling)
-    src_t = torch.empty(64 << 20, dtype=torch.float32, device="cuda")   # 256 MiB
-    dst_t = torch.empty_like(src_t)
-    dst_t.copy_(src_t)
-    torch.cuda.synchronize()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(10):
+    if args.full:
+        # device-to-device copy ceiling of this GPU (report the roofline against the datasheet peak AND a measured ceiling)
+        src_t = torch.empty(64 << 20, dtype=torch.float32, device="cuda")   # 256 MiB
+        dst_t = torch.empty_like(src_t)
         dst_t.copy_(src_t)
-    ev1.record()
-    torch.cuda.synchronize()
-    copy_gbs = 10 * 2 * src_t.numel() * 4 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9   # read + write bytes
-    del src_t, dst_t
+        torch.cuda.synchronize()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        for _ in range(10):
+            dst_t.copy_(src_t)
+        ev1.record()
+        torch.cuda.synchronize()
+        copy_gbs = 10 * 2 * src_t.numel() * 4 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9   # read + write bytes
+        del src_t, dst_t
 
     # densityAnalysis leg (informational): a "~2 A entry" (SURVEY 8d config 3 stand-in) through aggregateCloud + atom / residue
     # region discrepancies + blob statistics, maps uploaded from host buffers -> entries/min of the whole per-entry pipeline
     analysis = None
-    if rank == 0 and not args.no_analysis:
+    if args.full and rank == 0 and not args.no_analysis:
         analysis = guarded("analysis_entry", lambda: analysis_leg(ctx))
 
     # ---- BASELINE configs[3]: multiple-structure mode.  Every rank analyses ITS shard of the entries (no data-path collective):
@@ -924,14 +988,15 @@ def main():
 
     # ---- BASELINE configs[4]: optimise-mode iterations over resident entries + the statistics reduction (informational) ----
     sweep = None
-    if args.sweep_entries > 0 and args.sweep_iterations > 0:
+    if args.full and args.sweep_entries > 0 and args.sweep_iterations > 0:
         sweep = guarded("radius_sweep", lambda: sweep_leg(args, rank, local_rank, world, barrier, dist if world > 1 else None, torch))
 
-    # host -> HBM upload of one entry (the boundary hands over a host buffer); never part of `value`
-    t1 = time.perf_counter()
-    tmp = _native.DeviceMap(ctx, grid, header.geometry())
-    h2d_s = time.perf_counter() - t1
-    tmp.free()
+    if args.full:
+        # host -> HBM upload of one entry (the boundary hands over a host buffer); never part of `value`
+        t1 = time.perf_counter()
+        tmp = _native.DeviceMap(ctx, grid, header.geometry())
+        h2d_s = time.perf_counter() - t1
+        tmp.free()
 
     value = world * n_vox * args.steps / elapsed / 1e6
     out = {
@@ -954,29 +1019,32 @@ def main():
                    "host_affinity": ("%d cores of the GPU's NUMA node" % pinned_cpus) if pinned_cpus else "unchanged"},
         "entries_per_min": 60.0 * world * args.steps / elapsed,
         "blobs": {"green": n_green, "red": n_red, "significant_voxels": sig_vox, "all_ranks": [int(x) for x in totals.tolist()]},
-        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic, "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_us": 1e6 * dom_avg_s,
-                     # the conservative figure: the raw HIP-event time of the launch (it includes the launch gap) -- and, when the committed
-                     # rocprofv3 kernel trace was taken on these very sources, its average for the same kernel
-                     "event_us": per_kernel[dominant]["event_us"], "achieved_on_event_time": dom_bytes / (per_kernel[dominant]["event_us"] * 1e-6) / 1e9,
-                     "frac_on_event_time": dom_bytes / (per_kernel[dominant]["event_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                     "rocprofv3_avg_us": rocprof_avg_us,
-                     "d2d_copy_ceiling_GBs": copy_gbs, "frac_of_copy_ceiling": achieved / copy_gbs,
-                     # (the dispersion of the host-timed step rides in this object too: the driver's record keeps `roofline` whole)
-                     "ms_per_step_windows": {"n": len(windows), "steps_each": args.steps, "min": min(windows) if windows else None,
-                                             "median": float(np.median(windows)) if windows else None, "max": max(windows) if windows else None},
-                     "timing": "HIP events on the launch stream (separate %d-step pass), minus the per-launch event gap calibrated in this run: "
-                               "%.2f us = (sum of event times %.1f us - host-timed step %.1f us) / %.0f launches" % (args.steps, gap_us, step_events_us, step_wall_us, n_launch),
-                     "pass_8B_per_voxel": {"bytes": 8 * n_vox, "kernel_sum_us": 1e6 * step_kernel_s,
-                                           "achieved": 8 * n_vox / step_kernel_s / 1e9, "frac": 8 * n_vox / step_kernel_s / 1e9 / HBM_PEAK_GBS}},
-        "kernels_us": {k: round(v["avg_us"] * v["calls"] / args.steps, 2) for k, v in sorted(per_kernel.items())},
-        "kernels_traffic": kernels_traffic,
-        "windows_ms_per_step": {"windows": [round(w, 5) for w in windows], "min": min(windows) if windows else None,
-                                "median": float(np.median(windows)) if windows else None, "steps_per_window": args.steps},
-        "h2d": {"upload_ms": 1e3 * h2d_s, "pcie_inclusive_Mvoxels_per_s": n_vox / (h2d_s + elapsed / args.steps) / 1e6,
-                "note": "pageable host buffer -> HBM through pdbeda_map_upload; reported for information, never part of value"},
-        "fallback_tiles": green.counters(),
     }
+    if args.full:
+        out.update({
+            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                         "traffic": traffic, "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_us": 1e6 * dom_avg_s,
+                         # the conservative figure: the raw HIP-event time of the launch (it includes the launch gap) -- and, when the committed
+                         # rocprofv3 kernel trace was taken on these very sources, its average for the same kernel
+                         "event_us": per_kernel[dominant]["event_us"], "achieved_on_event_time": dom_bytes / (per_kernel[dominant]["event_us"] * 1e-6) / 1e9,
+                         "frac_on_event_time": dom_bytes / (per_kernel[dominant]["event_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                         "rocprofv3_avg_us": rocprof_avg_us,
+                         "d2d_copy_ceiling_GBs": copy_gbs, "frac_of_copy_ceiling": achieved / copy_gbs,
+                         # (the dispersion of the host-timed step rides in this object too)
+                         "ms_per_step_windows": {"n": len(windows), "steps_each": args.steps, "min": min(windows) if windows else None,
+                                                 "median": float(np.median(windows)) if windows else None, "max": max(windows) if windows else None},
+                         "timing": "HIP events on the launch stream (separate %d-step pass), minus the per-launch event gap calibrated in this run: "
+                                   "%.2f us = (sum of event times %.1f us - host-timed step %.1f us) / %.0f launches" % (args.steps, gap_us, step_events_us, step_wall_us, n_launch),
+                         "pass_8B_per_voxel": {"bytes": 8 * n_vox, "kernel_sum_us": 1e6 * step_kernel_s,
+                                               "achieved": 8 * n_vox / step_kernel_s / 1e9, "frac": 8 * n_vox / step_kernel_s / 1e9 / HBM_PEAK_GBS}},
+            "kernels_us": {k: round(v["avg_us"] * v["calls"] / args.steps, 2) for k, v in sorted(per_kernel.items())},
+            "kernels_traffic": kernels_traffic,
+            "windows_ms_per_step": {"windows": [round(w, 5) for w in windows], "min": min(windows) if windows else None,
+                                    "median": float(np.median(windows)) if windows else None, "steps_per_window": args.steps},
+            "h2d": {"upload_ms": 1e3 * h2d_s, "pcie_inclusive_Mvoxels_per_s": n_vox / (h2d_s + elapsed / args.steps) / 1e6,
+                    "note": "pageable host buffer -> HBM through pdbeda_map_upload; reported for information, never part of value"},
+        })
+    out["fallback_tiles"] = green.counters()
     if sigma3:
         out["sigma3"] = sigma3
     if multi:
@@ -991,7 +1059,7 @@ def main():
         out["radius_sweep"] = sweep
 
     # ---- CPU baseline: the oracle (CPU restatement, O(N) clustering) on the same entry, 1 core ----
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         from oracle import oracle as ora
         o = ora.Oracle(header, grid)
         done, spent = 0, 0.0

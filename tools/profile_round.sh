@@ -18,6 +18,6 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -o p -- pytho
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write" -o p -- python3 "$root/tools/profile_step.py" > "$out/pmc_write.log" 2>&1
 cd "$root"
 python3 tools/make_profiles.py "$tag" "$out" > /dev/null      # the counters first: bench.py prints roofline.traffic from them
-python3 bench.py --steps 50 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
+python3 bench.py --full --steps 50 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
 python3 tools/make_profiles.py "$tag" "$out"
 echo "profiles refreshed from $out"
