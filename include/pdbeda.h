@@ -277,6 +277,31 @@ int pdbeda_symmetry_atoms(pdbeda_ctx *ctx, const double *xyz, int64_t n_atoms, c
 int pdbeda_nearest_atom(pdbeda_ctx *ctx, const double *centroids, int64_t n_centroids, const double *atom_xyz,
                         int64_t n_atoms, int64_t *index, double *distance);
 
+/* ---- crystal contacts --------------------------------------------------------------- */
+/* crystalContacts.findCoordContacts (crystalContacts.py:87-101): for every query point
+ * q_xyz[i] the minimum fp64 distance to the points p_xyz, reported as (i, distance) in
+ * ascending i when <= cutoff (boundary included).  Returns the row count through n_out;
+ * PDBEDA_ERR_CAPACITY when it exceeds cap (n_q always suffices).  cutoff must be finite
+ * and > 0, every coordinate finite.  One wait. */
+int pdbeda_coord_contacts(pdbeda_ctx *ctx, const double *q_xyz, int64_t n_q, const double *p_xyz, int64_t n_p,
+                          double cutoff, int64_t *out_index, double *out_distance, int64_t cap, int64_t *n_out);
+/* crystalContacts.main + simulateCrystalNeighborCoordinates (crystalContacts.py:37-84,
+ * 104-142) without pymol.  Image c of the candidate list cand[4c..4c+3] = (op, n0, n1, n2)
+ * maps x to R_op x + t_op + ortho (n0, n1, n2) (rot: n_ops x 12 as in
+ * pdbeda_symmetry_atoms; the same arithmetic).  (op 0, n = 0) is the asymmetric unit and
+ * is refused.  Image c is kept (kept_out[c] = 1, optional) when some image of a poly_xyz
+ * point lies within cutoff of some poly_xyz point; the query rows are then those of
+ * pdbeda_coord_contacts against every point of every kept image.  Two waits. */
+int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int64_t n_q, const double *poly_xyz, int64_t n_poly,
+                            const double *rot /* n_ops x 12 */, int32_t n_ops, const double ortho[9],
+                            const int32_t *cand /* n_cand x 4 */, int64_t n_cand, double cutoff, uint8_t *kept_out,
+                            int64_t *out_index, double *out_distance, int64_t cap, int64_t *n_out);
+/* The neighbour list of simulateCrystalNeighborCoordinates (crystalContacts.py:104-142):
+ * the points of the listed images in (image, point) order, n_cand x n_poly x 3 doubles. */
+int pdbeda_image_coords(pdbeda_ctx *ctx, const double *poly_xyz, int64_t n_poly, const double *rot /* n_ops x 12 */,
+                        int32_t n_ops, const double ortho[9], const int32_t *cand /* n_cand x 4 */, int64_t n_cand,
+                        double *out_xyz);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,9 @@ _SIGS = {
     "pdbeda_test_overlap": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, _p]),
     "pdbeda_symmetry_atoms": (C.c_int, [_p, _p, _i64, _p, C.c_int32, _p, _p, _p, _p, _p, _p, _i64, C.POINTER(_i64)]),
     "pdbeda_nearest_atom": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _p]),
+    "pdbeda_coord_contacts": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_double, _p, _p, _i64, C.POINTER(_i64)]),
+    "pdbeda_crystal_contacts": (C.c_int, [_p, _p, _i64, _p, _i64, _p, C.c_int32, _p, _p, _i64, C.c_double, _p, _p, _p, _i64, C.POINTER(_i64)]),
+    "pdbeda_image_coords": (C.c_int, [_p, _p, _i64, _p, C.c_int32, _p, _p, _i64, _p]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
 
@@ -230,6 +233,44 @@ class Context(object):
         self.check(self._lib.pdbeda_nearest_atom(self._h, _ptr(cen), len(cen), _ptr(at), len(at), _ptr(idx), _ptr(dist)),
                    "pdbeda_nearest_atom")
         return idx, dist
+
+    def coord_contacts(self, q_xyz, p_xyz, cutoff):
+        """(index, distance) of the query points whose nearest p_xyz point is within cutoff (pdbeda_coord_contacts)."""
+        q = np.ascontiguousarray(q_xyz, dtype=np.float64).reshape(-1, 3)
+        p = np.ascontiguousarray(p_xyz, dtype=np.float64).reshape(-1, 3)
+        idx = np.zeros(len(q), dtype=np.int64)
+        dist = np.zeros(len(q), dtype=np.float64)
+        n = C.c_int64(0)
+        self.check(self._lib.pdbeda_coord_contacts(self._h, _ptr(q), len(q), _ptr(p), len(p), C.c_double(float(cutoff)), _ptr(idx), _ptr(dist), len(q),
+                                                   C.byref(n)), "pdbeda_coord_contacts")
+        return idx[:n.value].copy(), dist[:n.value].copy()
+
+    def crystal_contacts(self, q_xyz, poly_xyz, rot, ortho, cand, cutoff):
+        """(kept flag per candidate image, index, distance) of pdbeda_crystal_contacts."""
+        q = np.ascontiguousarray(q_xyz, dtype=np.float64).reshape(-1, 3)
+        p = np.ascontiguousarray(poly_xyz, dtype=np.float64).reshape(-1, 3)
+        rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 12)
+        ortho = np.ascontiguousarray(ortho, dtype=np.float64).reshape(9)
+        cand = np.ascontiguousarray(cand, dtype=np.int32).reshape(-1, 4)
+        kept = np.zeros(len(cand), dtype=np.uint8)
+        idx = np.zeros(len(q), dtype=np.int64)
+        dist = np.zeros(len(q), dtype=np.float64)
+        n = C.c_int64(0)
+        self.check(self._lib.pdbeda_crystal_contacts(self._h, _ptr(q), len(q), _ptr(p), len(p), _ptr(rot), len(rot), _ptr(ortho), _ptr(cand), len(cand),
+                                                     C.c_double(float(cutoff)), _ptr(kept), _ptr(idx), _ptr(dist), len(q), C.byref(n)),
+                   "pdbeda_crystal_contacts")
+        return kept.astype(bool), idx[:n.value].copy(), dist[:n.value].copy()
+
+    def image_coords(self, poly_xyz, rot, ortho, cand):
+        """The points of the listed images in (image, point) order, as an (n_cand * n_poly, 3) array (pdbeda_image_coords)."""
+        p = np.ascontiguousarray(poly_xyz, dtype=np.float64).reshape(-1, 3)
+        rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 12)
+        ortho = np.ascontiguousarray(ortho, dtype=np.float64).reshape(9)
+        cand = np.ascontiguousarray(cand, dtype=np.int32).reshape(-1, 4)
+        out = np.zeros((len(cand) * len(p), 3), dtype=np.float64)
+        self.check(self._lib.pdbeda_image_coords(self._h, _ptr(p), len(p), _ptr(rot), len(rot), _ptr(ortho), _ptr(cand), len(cand), _ptr(out)),
+                   "pdbeda_image_coords")
+        return out
 
     def __del__(self):
         try:

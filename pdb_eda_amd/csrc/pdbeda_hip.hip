@@ -27,6 +27,7 @@
 #include "pdbeda_kernels.h"
 #include "pdbeda_tile.h"
 #include "pdbeda_upload.h"
+#include "pdbeda_contacts.h"
 
 using namespace pdbeda;
 
@@ -376,7 +377,7 @@ static inline unsigned grid_for(int64_t n, int block, int64_t cap = 1 << 20) {
 // staging block as on the device; one by one from the caller's memory when the block has no room (the caller waits before it
 // returns either way).
 struct H2DItem { void *dst; const void *src; size_t bytes; };
-static hipError_t h2d_row(pdbeda_ctx *ctx, const H2DItem *items, int n) {
+static hipError_t h2d_row(pdbeda_ctx *ctx, const H2DItem *items, int n, size_t max_span = 256u << 10) {
     char *lo = nullptr, *hi = nullptr;
     for (int k = 0; k < n; ++k) {
         if (items[k].bytes == 0) continue;
@@ -386,7 +387,7 @@ static hipError_t h2d_row(pdbeda_ctx *ctx, const H2DItem *items, int n) {
     }
     if (!lo) return hipSuccess;
     const size_t span = (size_t)(hi - lo), need = (span + 63) & ~(size_t)63;
-    if (ctx->pinned && span <= (256u << 10) && ctx->pinned_used + need <= ctx->pinned_cap) {
+    if (ctx->pinned && span <= max_span && ctx->pinned_used + need <= ctx->pinned_cap) {
         char *stage = ctx->pinned + ctx->pinned_used;
         for (int k = 0; k < n; ++k)
             if (items[k].bytes) memcpy(stage + ((char *)items[k].dst - lo), items[k].src, items[k].bytes);
@@ -2405,6 +2406,267 @@ extern "C" int pdbeda_nearest_atom(pdbeda_ctx *ctx, const double *centroids, int
         hipLaunchKernelGGL(k_nearest_atom, dim3((unsigned)n_centroids), dim3(256), 0, st, d_c, d_a, n_atoms, r_i ? r_i : d_i, r_d ? r_d : d_d);
         if (!r_i) HIP_TRY(ctx, d2h(ctx, index, d_i, 8 * n_centroids));
         if (!r_d) HIP_TRY(ctx, d2h(ctx, distance, d_d, 8 * n_centroids));
+        return 0;
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// Crystal contacts (crystalContacts.py): cell grids, symmetry images, minimum distances
+// ------------------------------------------------------------------------------------
+// How large a staged input may be so that `results` bytes of pinned_out results still fit in the pinned block behind it (a result without
+// room there costs a wait of its own).
+static size_t pinned_room_beside(const pdbeda_ctx *ctx, size_t results) {
+    const size_t reserve = results + (size_t)(4 << 10);
+    return ctx->pinned_cap > ctx->pinned_used + reserve ? ctx->pinned_cap - ctx->pinned_used - reserve : 0;
+}
+
+static bool all_finite(const double *v, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+static void bbox3(const double *xyz, int64_t n, double lo[3], double hi[3]) {
+    for (int q = 0; q < 3; ++q) { lo[q] = INFINITY; hi[q] = -INFINITY; }
+    for (int64_t i = 0; i < n; ++i)
+        for (int q = 0; q < 3; ++q) { lo[q] = std::min(lo[q], xyz[3 * i + q]); hi[q] = std::max(hi[q], xyz[3 * i + q]); }
+}
+
+// Grid over the box [lo, hi] (pdbeda_contacts.h): edge just above the cutoff, enlarged until the cells number at most 8 per point (at least
+// 4096, at most 2^22: the single-block scan stays short).  Correctness only needs edge > cutoff.
+static CellGrid make_cell_grid(const double lo[3], const double hi[3], double cutoff, int64_t n_points, const double crop_lo[3], const double crop_hi[3]) {
+    const double cap = (double)std::min<int64_t>(1 << 22, std::max<int64_t>(4096, 8 * n_points));
+    double edge = cutoff * (1.0 + 1e-6);
+    for (;;) {
+        double cells = 1.0;
+        for (int q = 0; q < 3; ++q) cells *= std::floor((hi[q] - lo[q]) / edge) + 1.0;
+        if (cells <= cap) break;
+        edge *= 1.25;
+    }
+    CellGrid g;
+    g.edge = edge;
+    g.n_cells = 1;
+    for (int q = 0; q < 3; ++q) {
+        g.lo[q] = lo[q];
+        g.dim[q] = (int)std::floor((hi[q] - lo[q]) / edge) + 1;
+        g.n_cells *= g.dim[q];
+        g.crop_lo[q] = crop_lo[q];
+        g.crop_hi[q] = crop_hi[q];
+    }
+    return g;
+}
+
+// The grid a query set searches: its bounding box grown by twice the cutoff, which is also the crop box of the points gridded into it.
+static CellGrid query_grid(const double *q_xyz, int64_t n_q, double cutoff, int64_t n_points) {
+    double lo[3], hi[3];
+    bbox3(q_xyz, n_q, lo, hi);
+    for (int q = 0; q < 3; ++q) { lo[q] -= 2 * cutoff; hi[q] += 2 * cutoff; }
+    return make_cell_grid(lo, hi, cutoff, n_points, lo, hi);
+}
+
+static int check_images(pdbeda_ctx *ctx, const double *rot, int32_t n_ops, const double *ortho, const int32_t *cand, int64_t n_cand) {
+    if (n_cand == 0) return PDBEDA_OK;
+    if (!cand || !rot || !ortho || n_ops < 1) return fail(ctx, PDBEDA_ERR_ARGUMENT, "images need operators, a cell and a candidate list");
+    if (!all_finite(rot, 12 * (int64_t)n_ops) || !all_finite(ortho, 9)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "non-finite operator or cell");
+    for (int64_t c = 0; c < n_cand; ++c) {
+        const int32_t *k = cand + 4 * c;
+        if (k[0] < 0 || k[0] >= n_ops) return fail(ctx, PDBEDA_ERR_ARGUMENT, "candidate %lld: operator %d out of range", (long long)c, k[0]);
+        for (int q = 1; q < 4; ++q)
+            if (k[q] < -(1 << 20) || k[q] > (1 << 20)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "candidate %lld: cell shift out of range", (long long)c);
+        if (k[0] == 0 && k[1] == 0 && k[2] == 0 && k[3] == 0)
+            return fail(ctx, PDBEDA_ERR_ARGUMENT, "candidate %lld is (op 0, n = 0): the asymmetric unit, not an image", (long long)c);
+    }
+    return PDBEDA_OK;
+}
+
+static int check_contacts_args(pdbeda_ctx *ctx, const double *q_xyz, int64_t n_q, const double *p_xyz, int64_t n_p, double cutoff,
+                               const int64_t *out_index, const double *out_distance, int64_t cap) {
+    if ((n_q > 0 && !q_xyz) || (n_p > 0 && !p_xyz) || (cap > 0 && (!out_index || !out_distance))) return fail(ctx, PDBEDA_ERR_ARGUMENT, "null array");
+    if (!std::isfinite(cutoff) || !(cutoff > 0.0)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "cutoff must be finite and > 0");
+    if (n_q >= (1ll << 31) || n_p >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "more than 2^31 points");
+    if (!all_finite(q_xyz, 3 * n_q) || !all_finite(p_xyz, 3 * n_p)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "non-finite coordinate");
+    return PDBEDA_OK;
+}
+
+// The compaction of k_contact_min's distances into the caller's (index, distance) rows and their count: written by k_contact_compact straight
+// into the pinned block when it has room, else on the device and copied.  Complete after the next ctx_sync.
+static int enqueue_compact(pdbeda_ctx *ctx, const double *d_dist, int64_t n_q, double cutoff, int64_t *out_index, double *out_distance, int64_t cap,
+                           int64_t *n_out, int64_t *d_idx, double *d_odist, int64_t *d_nout) {
+    const int64_t rows = std::min(cap, n_q);
+    int64_t *r_i = pinned_out(ctx, out_index, (size_t)rows);
+    double *r_d = pinned_out(ctx, out_distance, (size_t)rows);
+    int64_t *r_n = pinned_out(ctx, n_out, 1);
+    { PROF(ctx, "k_contact_compact"); hipLaunchKernelGGL(k_contact_compact, dim3(1), dim3(1024), 0, ctx->stream, d_dist, n_q, cutoff, r_i ? r_i : d_idx, r_d ? r_d : d_odist, rows, r_n ? r_n : d_nout); }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!r_i && rows > 0) HIP_TRY(ctx, d2h(ctx, out_index, d_idx, 8 * rows));
+    if (!r_d && rows > 0) HIP_TRY(ctx, d2h(ctx, out_distance, d_odist, 8 * rows));
+    if (!r_n) HIP_TRY(ctx, d2h(ctx, n_out, d_nout, 8));
+    return 0;
+}
+
+extern "C" int pdbeda_coord_contacts(pdbeda_ctx *ctx, const double *q_xyz, int64_t n_q, const double *p_xyz, int64_t n_p, double cutoff,
+                                     int64_t *out_index, double *out_distance, int64_t cap, int64_t *n_out) {
+    if (!ctx || !n_out || n_q < 0 || n_p < 0 || cap < 0) return PDBEDA_ERR_ARGUMENT;
+    *n_out = 0;
+    if (int rc = check_contacts_args(ctx, q_xyz, n_q, p_xyz, n_p, cutoff, out_index, out_distance, cap)) return rc;
+    if (n_q == 0 || n_p == 0) return PDBEDA_OK;      // nothing to be near to: no rows (cdist + np.min would raise on an empty list)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const CellGrid g = query_grid(q_xyz, n_q, cutoff, n_q + n_p);
+    const int64_t cells = g.n_cells;
+    std::vector<unsigned> zeros((size_t)cells, 0u);
+    int64_t total = 0;
+    const size_t bytes = align_up(24 * n_q) + align_up(24 * n_p) + align_up(4 * cells) + align_up(24 * n_p) + align_up(4 * (cells + 1)) + align_up(4 * cells) +
+                         3 * align_up(8 * n_q) + align_up(8);
+    int rc = with_scratch(ctx, bytes, [&](char *base) -> int {
+        Carver cv(base);
+        double *d_q = cv.take<double>(3 * n_q);
+        double *d_p = cv.take<double>(3 * n_p);
+        unsigned *d_count = cv.take<unsigned>(cells);
+        double *d_sorted = cv.take<double>(3 * n_p);
+        unsigned *d_start = cv.take<unsigned>(cells + 1);
+        unsigned *d_cursor = cv.take<unsigned>(cells);
+        double *d_dist = cv.take<double>(n_q);
+        int64_t *d_idx = cv.take<int64_t>(n_q);
+        double *d_odist = cv.take<double>(n_q);
+        int64_t *d_nout = cv.take<int64_t>(1);
+        hipStream_t st = ctx->stream;
+        {
+            const H2DItem in[3] = {{d_q, q_xyz, (size_t)(24 * n_q)}, {d_p, p_xyz, (size_t)(24 * n_p)}, {d_count, zeros.data(), (size_t)(4 * cells)}};
+            // ONE copy whenever the pinned block holds it beside the rows (else one per item); the cell counts start from the zeros that ride in it
+            HIP_TRY(ctx, h2d_row(ctx, in, 3, pinned_room_beside(ctx, 16 * (size_t)n_q + 64)));
+        }
+        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_p, 256)), dim3(256), 0, st, d_p, n_p, g, d_count); }
+        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count, (int)cells, d_start, d_cursor, nullptr); }
+        { PROF(ctx, "k_grid_scatter_points"); hipLaunchKernelGGL(k_grid_scatter_points, dim3(grid_for(n_p, 256)), dim3(256), 0, st, d_p, n_p, g, d_cursor, d_sorted, n_p); }
+        { PROF(ctx, "k_contact_min"); hipLaunchKernelGGL(k_contact_min, dim3(grid_for(n_q, 256)), dim3(256), 0, st, d_q, n_q, d_sorted, d_start, g, d_dist); }
+        HIP_TRY(ctx, hipGetLastError());
+        return enqueue_compact(ctx, d_dist, n_q, cutoff, out_index, out_distance, cap, &total, d_idx, d_odist, d_nout);
+    });
+    if (rc) return rc;
+    *n_out = total;
+    if (total > cap) return fail(ctx, PDBEDA_ERR_CAPACITY, "need capacity %lld", (long long)total);
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int64_t n_q, const double *poly_xyz, int64_t n_poly, const double *rot,
+                                       int32_t n_ops, const double ortho[9], const int32_t *cand, int64_t n_cand, double cutoff, uint8_t *kept_out,
+                                       int64_t *out_index, double *out_distance, int64_t cap, int64_t *n_out) {
+    if (!ctx || !n_out || n_q < 0 || n_poly < 0 || n_cand < 0 || n_ops < 0 || cap < 0) return PDBEDA_ERR_ARGUMENT;
+    *n_out = 0;
+    if (int rc = check_contacts_args(ctx, q_xyz, n_q, poly_xyz, n_poly, cutoff, out_index, out_distance, cap)) return rc;
+    if (int rc = check_images(ctx, rot, n_ops, ortho, cand, n_cand)) return rc;
+    if (n_cand > 0 && n_poly > 0 && n_cand * n_poly >= (1ll << 32) - 1) return fail(ctx, PDBEDA_ERR_ARGUMENT, "more than 2^32 image atoms");
+    if (kept_out && n_cand > 0) memset(kept_out, 0, (size_t)n_cand);
+    if (n_cand == 0 || n_poly == 0) return PDBEDA_OK;   // no image: no neighbours, no rows (the reference's np.min of an empty array would raise)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double plo[3], phi[3];
+    bbox3(poly_xyz, n_poly, plo, phi);
+    const double inf_lo[3] = {-INFINITY, -INFINITY, -INFINITY}, inf_hi[3] = {INFINITY, INFINITY, INFINITY};
+    const CellGrid gp = make_cell_grid(plo, phi, cutoff, n_poly, inf_lo, inf_hi);
+    const CellGrid gn = n_q > 0 ? query_grid(q_xyz, n_q, cutoff, n_q + n_poly) : gp;
+    const int64_t cells_p = gp.n_cells, cells_n = n_q > 0 ? gn.n_cells : 0;
+    std::vector<unsigned> zeros((size_t)std::max({cells_p, cells_n, n_cand}), 0u);
+    std::vector<unsigned> h_keep((size_t)n_cand);
+    unsigned h_total = 0;
+    int64_t rows = 0;
+    const size_t bytes_a = align_up(24 * n_poly) + align_up(24 * n_q) + align_up(96 * n_ops) + align_up(72) + align_up(16 * n_cand) + align_up(4 * cells_p) +
+                           align_up(4 * n_cand) + align_up(4 * cells_n) + align_up(24 * n_poly) + align_up(4 * (cells_p + 1)) + align_up(4 * cells_p) +
+                           align_up(4 * (cells_n + 1)) + align_up(4 * cells_n) + 3 * align_up(8 * n_q) + align_up(8);
+    Arena A, B;
+    int rc = arena_get(ctx, bytes_a, &A);
+    if (rc) return rc;
+    rc = [&]() -> int {
+        Carver cv(A.base);
+        double *d_poly = cv.take<double>(3 * n_poly);
+        double *d_q = cv.take<double>(3 * n_q);
+        double *d_rot = cv.take<double>(12 * n_ops);
+        double *d_ortho = cv.take<double>(9);
+        int32_t *d_cand = cv.take<int32_t>(4 * n_cand);
+        unsigned *d_count_p = cv.take<unsigned>(cells_p);
+        unsigned *d_keep = cv.take<unsigned>(n_cand);
+        unsigned *d_count_n = cv.take<unsigned>(cells_n);
+        double *d_sorted_p = cv.take<double>(3 * n_poly);
+        unsigned *d_start_p = cv.take<unsigned>(cells_p + 1);
+        unsigned *d_cursor_p = cv.take<unsigned>(cells_p);
+        unsigned *d_start_n = cv.take<unsigned>(cells_n + 1);
+        unsigned *d_cursor_n = cv.take<unsigned>(cells_n);
+        double *d_dist = cv.take<double>(n_q);
+        int64_t *d_idx = cv.take<int64_t>(n_q);
+        double *d_odist = cv.take<double>(n_q);
+        int64_t *d_nout = cv.take<int64_t>(1);
+        hipStream_t st = ctx->stream;
+        {   // inputs and the zeroed counters and flags in a row: ONE copy whenever the pinned block holds them (up to ~80 000 atoms), else one per item
+            const H2DItem in[8] = {{d_poly, poly_xyz, (size_t)(24 * n_poly)}, {d_q, q_xyz, (size_t)(24 * n_q)}, {d_rot, rot, (size_t)(96 * n_ops)},
+                                   {d_ortho, ortho, 72}, {d_cand, cand, (size_t)(16 * n_cand)}, {d_count_p, zeros.data(), (size_t)(4 * cells_p)},
+                                   {d_keep, zeros.data(), (size_t)(4 * n_cand)}, {d_count_n, zeros.data(), (size_t)(4 * cells_n)}};
+            HIP_TRY(ctx, h2d_row(ctx, in, 8, pinned_room_beside(ctx, 4 * (size_t)n_cand + 64)));
+        }
+        const int64_t lanes = n_cand * n_poly;
+        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_poly, 256)), dim3(256), 0, st, d_poly, n_poly, gp, d_count_p); }
+        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count_p, (int)cells_p, d_start_p, d_cursor_p, nullptr); }
+        { PROF(ctx, "k_grid_scatter_points"); hipLaunchKernelGGL(k_grid_scatter_points, dim3(grid_for(n_poly, 256)), dim3(256), 0, st, d_poly, n_poly, gp, d_cursor_p, d_sorted_p, n_poly); }
+        { PROF(ctx, "k_image_select"); hipLaunchKernelGGL(k_image_select, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_sorted_p, d_start_p, gp, cutoff, d_keep); }
+        if (n_q > 0) {      // (the keep flags and the neighbour count go to the host from inside these two launches: no copy launch)
+            unsigned *r_keep = pinned_out(ctx, h_keep.data(), (size_t)n_cand);
+            unsigned *r_total = pinned_out(ctx, &h_total, 1);
+            { PROF(ctx, "k_image_count"); hipLaunchKernelGGL(k_image_count, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_keep, gn, d_count_n, r_keep); }
+            { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count_n, (int)cells_n, d_start_n, d_cursor_n, r_total); }
+            HIP_TRY(ctx, hipGetLastError());
+            if (!r_keep) HIP_TRY(ctx, d2h(ctx, h_keep.data(), d_keep, 4 * (size_t)n_cand));
+            if (!r_total) HIP_TRY(ctx, d2h(ctx, &h_total, d_start_n + cells_n, 4));
+        } else {
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, d2h(ctx, h_keep.data(), d_keep, 4 * (size_t)n_cand));
+        }
+        HIP_TRY(ctx, ctx_sync(ctx));                 // wait 1: the kept images and the size of the neighbour grid
+        if (kept_out)
+            for (int64_t c = 0; c < n_cand; ++c) kept_out[c] = h_keep[(size_t)c] ? 1 : 0;
+        if (n_q == 0 || h_total == 0) return 0;
+        if ((int64_t)h_total > lanes) return fail(ctx, PDBEDA_ERR_DEVICE, "neighbour grid holds %u points of at most %lld", h_total, (long long)lanes);
+        if (int e = arena_get(ctx, align_up(24 * (size_t)h_total), &B)) return e;
+        double *d_sorted_n = reinterpret_cast<double *>(B.base);
+        { PROF(ctx, "k_image_scatter"); hipLaunchKernelGGL(k_image_scatter, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_keep, gn, d_cursor_n, d_sorted_n, (int64_t)h_total); }
+        { PROF(ctx, "k_contact_min"); hipLaunchKernelGGL(k_contact_min, dim3(grid_for(n_q, 256)), dim3(256), 0, st, d_q, n_q, d_sorted_n, d_start_n, gn, d_dist); }
+        HIP_TRY(ctx, hipGetLastError());
+        if (int e = enqueue_compact(ctx, d_dist, n_q, cutoff, out_index, out_distance, cap, &rows, d_idx, d_odist, d_nout)) return e;
+        HIP_TRY(ctx, ctx_sync(ctx));                 // wait 2: the rows
+        return 0;
+    }();
+    if (rc) (void)ctx_sync(ctx);                     // (a failed call drains the stream before its arenas go back to the pool)
+    if (B.base) arena_put(ctx, B);
+    arena_put(ctx, A);
+    if (rc) return rc;
+    *n_out = rows;
+    if (rows > cap) return fail(ctx, PDBEDA_ERR_CAPACITY, "need capacity %lld", (long long)rows);
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_image_coords(pdbeda_ctx *ctx, const double *poly_xyz, int64_t n_poly, const double *rot, int32_t n_ops, const double ortho[9],
+                                   const int32_t *cand, int64_t n_cand, double *out_xyz) {
+    if (!ctx || n_poly < 0 || n_cand < 0 || n_ops < 0 || (n_poly > 0 && !poly_xyz) || (n_poly > 0 && n_cand > 0 && !out_xyz)) return PDBEDA_ERR_ARGUMENT;
+    if (n_poly >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "more than 2^31 points");
+    if (!all_finite(poly_xyz, 3 * n_poly)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "non-finite coordinate");
+    if (int rc = check_images(ctx, rot, n_ops, ortho, cand, n_cand)) return rc;
+    if (n_cand == 0 || n_poly == 0) return PDBEDA_OK;
+    if (n_cand * n_poly >= (1ll << 32) - 1) return fail(ctx, PDBEDA_ERR_ARGUMENT, "more than 2^32 image atoms");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t total = n_cand * n_poly;
+    return with_scratch(ctx, align_up(24 * n_poly) + align_up(96 * n_ops) + align_up(72) + align_up(16 * n_cand) + align_up(24 * total), [&](char *base) -> int {
+        Carver cv(base);
+        double *d_poly = cv.take<double>(3 * n_poly);
+        double *d_rot = cv.take<double>(12 * n_ops);
+        double *d_ortho = cv.take<double>(9);
+        int32_t *d_cand = cv.take<int32_t>(4 * n_cand);
+        double *d_out = cv.take<double>(3 * total);
+        hipStream_t st = ctx->stream;
+        {
+            const H2DItem in[4] = {{d_poly, poly_xyz, (size_t)(24 * n_poly)}, {d_rot, rot, (size_t)(96 * n_ops)}, {d_ortho, ortho, 72}, {d_cand, cand, (size_t)(16 * n_cand)}};
+            HIP_TRY(ctx, h2d_row(ctx, in, 4));
+        }
+        double *r_out = pinned_out(ctx, out_xyz, 3 * (size_t)total);
+        { PROF(ctx, "k_image_emit"); hipLaunchKernelGGL(k_image_emit, dim3(grid_for(total, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, r_out ? r_out : d_out); }
+        HIP_TRY(ctx, hipGetLastError());
+        if (!r_out) HIP_TRY(ctx, d2h(ctx, out_xyz, d_out, 24 * (size_t)total));
         return 0;
     });
 }
