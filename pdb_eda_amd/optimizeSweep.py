@@ -6,8 +6,8 @@ re-analysed with the candidate parameter table (``processFunction``, 410-448: ``
 record of diffs / slopes / overlap counters) and the records are reduced to per-atom-type medians, sizes and an overlap
 completeness (341-408).  Here every rank re-analyses ITS shard of the entries on its GPU (stream pool, one entry per
 stream) and the reduction is the path's one exchange step (``optimizeStats``: all-gather of the rows + all-reduce of the
-counters over RCCL / xGMI).  The descent logic that picks the next radius (optimizeParams.py:176-327) is control plane
-and stays with the caller: ``sweep`` takes the parameter tables to evaluate.
+counters over RCCL / xGMI).  The descent that picks the next radius (optimizeParams.py:176-327) is
+``pdb_eda_amd.optimizeParams.optimize``, which calls ``iteration`` once per candidate table; ``sweep`` evaluates a given list.
 
 Entries keep their parsed maps resident in HBM between iterations (``ResidentEntry``): an iteration changes radii and
 slopes, never the maps, so only the analysis is repeated.
