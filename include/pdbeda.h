@@ -45,6 +45,7 @@ typedef enum pdbeda_status {
 typedef struct pdbeda_ctx pdbeda_ctx;           /* device + stream + reusable workspace */
 typedef struct pdbeda_map pdbeda_map;           /* one density grid resident in HBM */
 typedef struct pdbeda_bloblist pdbeda_bloblist; /* result of a labelling call */
+typedef struct pdbeda_peaklist pdbeda_peaklist; /* result of a peak search */
 
 /* The "unit-cell basis" ccp4.py computes on the host (DensityHeader, ccp4.py:225-286). */
 typedef struct pdbeda_geometry {
@@ -91,7 +92,8 @@ int64_t pdbeda_reap_abandoned(void);
 const char *pdbeda_last_error(pdbeda_ctx *ctx);
 /* Per-kernel timing with HIP events recorded on the context's stream (measurement aid for
  * bench.py; no reference counterpart).  profile_end synchronises and writes one
- * "kernel_name calls total_ms" line per kernel into buf. */
+ * "kernel_name calls total_ms" line per kernel into buf (and a "host_peak_sort" line when peak lists were ordered meanwhile:
+ * host time, the same units). */
 int pdbeda_ctx_profile_begin(pdbeda_ctx *ctx);
 int pdbeda_ctx_profile_end(pdbeda_ctx *ctx, char *buf, int64_t cap);
 
@@ -202,6 +204,44 @@ int pdbeda_bloblist_free(pdbeda_bloblist *bl);
  * components than the LDS tables hold, united in LDS all the same; unit tiles: no ids left for a wide tile), bytes of device memory
  * the job holds. */
 int pdbeda_bloblist_counters(pdbeda_bloblist *bl, int64_t *out);
+
+/* ---- density peaks ---------------------------------------------------------------- */
+/* The local extrema of a map (no reference counterpart: the reference stops at blobs, whose centroid is the wrong handle on a
+ * blob that covers two waters).  Domain: the voxels of the non-repeating box header.uniqueNcrs (the domain of
+ * createFullCrsList, utils.py:180-198); the neighbourhood of a voxel is those of its 26 neighbours that lie inside that box
+ * (nothing wraps: the connectivity of createCrsLists).  For cutoff > 0 voxel a BEATS voxel b when D[a] > D[b], or D[a] == D[b]
+ * and a comes first in c-major (c, r, s) order; for cutoff < 0 the same with <: a strict total order, so plateaus have exactly
+ * one peak.  A PEAK is a voxel with D >= cutoff (D <= cutoff for cutoff < 0; inclusive, float32 cutoff) that beats every
+ * neighbour; a NaN voxel is never a peak and beats nothing.  Per peak: crs (raw, as pdbeda_bloblist_voxels), height (the
+ * voxel value), on_border (fewer than 26 neighbours in the box), and a position / height refined by one parabola per axis in
+ * fp64: with a, v, b the values at -1, 0, +1 along the axis and den = a - 2 v + b, offset = 0.5 (a - b) / den, taken as 0 when
+ * den == 0 or an axial neighbour is outside the box, clamped to [-0.5, 0.5]; refined_height = v - 0.25 sum over axes of
+ * (a - b) offset; refined_xyz = crs2xyzCoord (ccp4.py:304-316) of the fractional crs.  The list is ordered by descending
+ * |height|, ties by c-major position, bit-identical from run to run.
+ * blobs: NULL, or the whole-map list of the SAME map and float32 cutoff (else PDBEDA_ERR_ARGUMENT; the call then waits for the
+ * labelling job): a peak passes the cutoff, so it lies in exactly one blob of that list -- `blob` is its index there (-1
+ * throughout without a list).  The blob list must stay alive until the first accessor of the peak list has returned.
+ * cutoff == 0 -> PDBEDA_ERR_ARGUMENT.  Asynchronous: returns after enqueueing; the first accessor synchronises. */
+int pdbeda_map_peaks(pdbeda_map *map, float cutoff, pdbeda_bloblist *blobs /* may be NULL */, pdbeda_peaklist **out);
+/* Fused: ONE pass over the grid finds the maxima with D >= cutoff_pos and the minima with D <= cutoff_neg (the green and red
+ * peaks of an Fo-Fc map, as pdbeda_full_blobs_pm does for blobs); each list equals the single call's to the bit.  No reference
+ * counterpart.  Asynchronous until the first accessor of either list. */
+int pdbeda_map_peaks_pm(pdbeda_map *map, float cutoff_pos, float cutoff_neg,
+                        pdbeda_bloblist *green, pdbeda_bloblist *red /* both may be NULL */,
+                        pdbeda_peaklist **pos, pdbeda_peaklist **neg);
+/* Number of peaks (no reference counterpart; synchronises, orders the list, and runs the job again when its typical-size
+ * arena -- room for a peak per 64 voxels of every 64 x 8 x 8 tile -- was too small for this map). */
+int64_t pdbeda_peaklist_count(pdbeda_peaklist *pl);
+/* The columns of the list in list order (no reference counterpart; synchronises): crs n x 3, height n, refined_xyz n x 3,
+ * refined_height n, blob n, on_border n. */
+int pdbeda_peaklist_rows(pdbeda_peaklist *pl, int32_t *crs, float *height, double *refined_xyz,
+                         double *refined_height, int32_t *blob, uint8_t *on_border);   /* any pointer may be NULL */
+/* Diagnostic (no reference counterpart; synchronises), like pdbeda_bloblist_counters: out[4] = candidates tested (voxels of
+ * the box that pass the cutoff), peaks, runs of the job beyond the first (1 = the typical-size arena overflowed), bytes of
+ * device memory the job holds. */
+int pdbeda_peaklist_counters(pdbeda_peaklist *pl, int64_t *out);
+/* Release a list (no reference counterpart; does not wait: the arena is recycled in stream order).  The handle is gone afterwards. */
+int pdbeda_peaklist_free(pdbeda_peaklist *pl);
 
 /* ---- regional sums ---------------------------------------------------------------- */
 /* The voxel part of calculateRegionDiscrepancy / calculateRegionDensity

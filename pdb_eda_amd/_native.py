@@ -108,6 +108,12 @@ _SIGS = {
     "pdbeda_bloblist_labels": (C.c_int, [_p, _p]),
     "pdbeda_bloblist_free": (C.c_int, [_p]),
     "pdbeda_bloblist_counters": (C.c_int, [_p, _p]),
+    "pdbeda_map_peaks": (C.c_int, [_p, C.c_float, _p, C.POINTER(_p)]),
+    "pdbeda_map_peaks_pm": (C.c_int, [_p, C.c_float, C.c_float, _p, _p, C.POINTER(_p), C.POINTER(_p)]),
+    "pdbeda_peaklist_count": (_i64, [_p]),
+    "pdbeda_peaklist_rows": (C.c_int, [_p, _p, _p, _p, _p, _p, _p]),
+    "pdbeda_peaklist_counters": (C.c_int, [_p, _p]),
+    "pdbeda_peaklist_free": (C.c_int, [_p]),
     "pdbeda_region_sums": (C.c_int, [_p, _p, _p, _i64, _p, _i64, C.c_float, _p, _p, _p, _p]),
     "pdbeda_aggregate_cloud": (C.c_int, [_p, C.POINTER(CloudAtoms), C.c_float, C.c_double, C.POINTER(_p)]),
     "pdbeda_cloud_counts": (C.c_int, [_p, _p, _p]),
@@ -400,6 +406,50 @@ class BlobList(object):
             pass
 
 
+class PeakList(object):
+    """Result of a peak search (pdbeda_map_peaks): the columns are fetched on demand, in list order."""
+
+    def __init__(self, ctx, handle, keepalive=None):
+        self._ctx = ctx
+        self._h = handle
+        self._keep = keepalive             # the map and the blob list(s) the job reads
+        self._rows = None
+
+    def __len__(self):
+        n = self._ctx._lib.pdbeda_peaklist_count(self._h)
+        if n < 0:
+            self._ctx.check(int(n), "pdbeda_peaklist_count")
+        return int(n)
+
+    def rows(self):
+        """{"crs" n x 3 int32, "height" float32, "xyz" n x 3, "refinedHeight", "blob" int32, "onBorder" bool}."""
+        if self._rows is None:
+            n = len(self)
+            st = {"crs": np.zeros((n, 3), np.int32), "height": np.zeros(n, np.float32), "xyz": np.zeros((n, 3), np.float64),
+                  "refinedHeight": np.zeros(n, np.float64), "blob": np.zeros(n, np.int32), "onBorder": np.zeros(n, np.uint8)}
+            self._ctx.check(self._ctx._lib.pdbeda_peaklist_rows(self._h, _ptr(st["crs"]), _ptr(st["height"]), _ptr(st["xyz"]), _ptr(st["refinedHeight"]),
+                                                                _ptr(st["blob"]), _ptr(st["onBorder"])), "pdbeda_peaklist_rows")
+            st["onBorder"] = st["onBorder"].astype(bool)
+            self._rows = st
+        return self._rows
+
+    def counters(self):
+        out = np.zeros(4, dtype=np.int64)
+        self._ctx.check(self._ctx._lib.pdbeda_peaklist_counters(self._h, _ptr(out)), "pdbeda_peaklist_counters")
+        return {"tested": int(out[0]), "peaks": int(out[1]), "reruns": int(out[2]), "arena_bytes": int(out[3])}
+
+    def free(self):
+        if self._h is not None and self._ctx._h:
+            self._ctx._lib.pdbeda_peaklist_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class DeviceMap(object):
     """A density grid resident in HBM + its unit-cell basis."""
 
@@ -543,6 +593,19 @@ class DeviceMap(object):
                                                             PDBEDA_FLAG_LABELS if labels else 0, C.byref(g), C.byref(r)),
                         "pdbeda_full_blobs_pm")
         return BlobList(self._ctx, g, self), BlobList(self._ctx, r, self)
+
+    def peaks(self, cutoff, blobs=None):
+        """Local extrema beyond ``cutoff`` (pdbeda_map_peaks); blobs: the BlobList of ``full_blobs(cutoff)`` or None."""
+        h = C.c_void_p()
+        self._ctx.check(self._ctx._lib.pdbeda_map_peaks(self._h, C.c_float(cutoff), blobs._h if blobs is not None else None, C.byref(h)),
+                        "pdbeda_map_peaks")
+        return PeakList(self._ctx, h, (self, blobs))
+
+    def peaks_pm(self, cutoff_pos, cutoff_neg, green=None, red=None):
+        p, n = C.c_void_p(), C.c_void_p()
+        self._ctx.check(self._ctx._lib.pdbeda_map_peaks_pm(self._h, C.c_float(cutoff_pos), C.c_float(cutoff_neg), green._h if green is not None else None,
+                                                           red._h if red is not None else None, C.byref(p), C.byref(n)), "pdbeda_map_peaks_pm")
+        return PeakList(self._ctx, p, (self, green, red)), PeakList(self._ctx, n, (self, green, red))
 
     def sphere_blobs(self, xyz, radii, group_offsets, cutoff):
         xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)

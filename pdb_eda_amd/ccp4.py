@@ -418,6 +418,83 @@ class DensityMatrix(object):
         crs = np.asarray([list(c) for c in crsList], dtype=np.int32).reshape(-1, 3)
         return DensityBlob.listFromDevice(self._map.list_blobs(crs), self)
 
+    # -- peaks (no reference counterpart) -------------------------------------------
+    @staticmethod
+    def _deviceListOf(blobList):
+        """The device list behind what ``createFullBlobList`` returned (None stays None)."""
+        if blobList is None:
+            return None
+        if not isinstance(blobList, DeviceBlobs) or len(blobList._segments) != 1:
+            raise ValueError("blobList must be what createFullBlobList / createFullBlobLists returned")
+        return blobList._segments[0].bl
+
+    def findPeaks(self, cutoff, blobList=None):
+        """The local maxima with density >= cutoff (minima with density <= cutoff when it is negative) of the non-repeating box,
+        strongest first, as ``DensityPeak`` items (``pdbeda_map_peaks`` in include/pdbeda.h has the contract); None for cutoff == 0,
+        as ``createFullBlobList``.  blobList: ``createFullBlobList(cutoff)`` of this map -- every peak then knows its blob."""
+        if np.float32(cutoff) == 0:
+            return None
+        return DevicePeaks(self._map.peaks(cutoff, self._deviceListOf(blobList)), self)
+
+    def findPeakLists(self, cutoff, blobLists=None):
+        """Fused (positive, negative) peak lists at +-|cutoff| from ONE pass over the grid; blobLists: the pair
+        ``createFullBlobLists(cutoff)`` returned, or None."""
+        green, red = blobLists if blobLists is not None else (None, None)
+        pos, neg = self._map.peaks_pm(abs(cutoff), -abs(cutoff), self._deviceListOf(green), self._deviceListOf(red))
+        return DevicePeaks(pos, self), DevicePeaks(neg, self)
+
+
+class DensityPeak(object):
+    """One local extremum of a map: ``crs`` (raw voxel), ``height`` (the voxel's value), ``xyz`` / ``refinedHeight`` (vertex of
+    one parabola per axis), ``blobIndex`` (in the blob list the search was given, else -1), ``onBorder`` (a voxel on the edge of
+    the stored box: the extremum may be the edge's)."""
+    __slots__ = ("crs", "height", "xyz", "refinedHeight", "blobIndex", "onBorder", "densityMatrix")
+
+    def __init__(self, crs, height, xyz, refinedHeight, blobIndex, onBorder, densityMatrix=None):
+        self.crs, self.height, self.xyz, self.refinedHeight = crs, height, xyz, refinedHeight
+        self.blobIndex, self.onBorder, self.densityMatrix = blobIndex, onBorder, densityMatrix
+
+    def __repr__(self):
+        return "DensityPeak(crs=%r, height=%r)" % (self.crs, self.height)
+
+
+class DevicePeaks(collections.abc.Sequence):
+    """What ``findPeaks`` returns: a read-only sequence of ``DensityPeak`` in list order, lazy like ``DeviceBlobs`` -- the
+    columns come from the device on first use, the objects are made when somebody reads one."""
+
+    def __init__(self, pl, densityMatrix):
+        self._pl, self.densityMatrix = pl, densityMatrix
+        self._items = None
+
+    def __len__(self):
+        return len(self._pl)
+
+    def columns(self):
+        """{"crs", "height", "xyz", "refinedHeight", "blobIndex", "onBorder"} of all peaks as arrays."""
+        rows = self._pl.rows()
+        return {"crs": rows["crs"], "height": rows["height"], "xyz": rows["xyz"], "refinedHeight": rows["refinedHeight"],
+                "blobIndex": rows["blob"], "onBorder": rows["onBorder"]}
+
+    def counters(self):
+        return self._pl.counters()
+
+    def _all(self):
+        if self._items is None:
+            st = self.columns()
+            self._items = [DensityPeak(*row, densityMatrix=self.densityMatrix)
+                           for row in zip(st["crs"].tolist(), st["height"].tolist(), st["xyz"].tolist(), st["refinedHeight"].tolist(),
+                                          st["blobIndex"].tolist(), st["onBorder"].tolist())]
+        return self._items
+
+    def __getitem__(self, i):
+        return self._all()[i]
+
+    def __iter__(self):
+        return iter(self._all())
+
+    def __repr__(self):
+        return "DevicePeaks(%d peaks)" % len(self)
+
 
 class _DeviceBlobSegment(object):
     """One device blob list behind a ``DeviceBlobs`` sequence: its statistics columns and, once somebody asked, its objects."""

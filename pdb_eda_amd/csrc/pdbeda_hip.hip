@@ -28,6 +28,7 @@
 #include "pdbeda_tile.h"
 #include "pdbeda_upload.h"
 #include "pdbeda_contacts.h"
+#include "pdbeda_peaks.h"
 
 using namespace pdbeda;
 
@@ -68,6 +69,7 @@ struct pdbeda_ctx {
     bool profiling = false;
     struct ProfRec { const char *name; hipEvent_t a, b; };
     std::vector<ProfRec> prof;
+    std::vector<std::pair<const char *, double>> prof_host;   // host-side phases timed while profiling is on (name, ms): the ordering of a peak list
     // test hooks (environment, read once at creation): PDBEDA_DEBUG_POISON=1 fills every arena with 0xFF bytes when it
     // is handed out (a kernel that trusts recycled memory shows up at once); PDBEDA_DEBUG_EDGE_CAP=n shrinks the
     // cross-tile pair buffer so the shard-overflow path runs on small inputs.
@@ -582,6 +584,7 @@ extern "C" int pdbeda_ctx_profile_begin(pdbeda_ctx *ctx) {
     if (!ctx) return PDBEDA_ERR_ARGUMENT;
     for (auto &r : ctx->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     ctx->prof.clear();
+    ctx->prof_host.clear();
     ctx->profiling = true;
     return PDBEDA_OK;
 }
@@ -599,6 +602,8 @@ extern "C" int pdbeda_ctx_profile_end(pdbeda_ctx *ctx, char *buf, int64_t cap) {
         (void)hipEventDestroy(r.b);
     }
     ctx->prof.clear();
+    for (auto &h : ctx->prof_host) { auto &e = agg[h.first]; e.first++; e.second += h.second; }
+    ctx->prof_host.clear();
     std::string out;
     char line[160];
     for (auto &kv : agg) {
@@ -1795,6 +1800,289 @@ extern "C" int pdbeda_bloblist_free(pdbeda_bloblist *bl) {
         if (other) delete other;
         delete bl;
     }
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Density peaks (pdbeda_peaks.h): local extrema of a map, tied to the blobs of a whole-map list
+// ------------------------------------------------------------------------------------
+// One job serves one list, or the two lists of a fused call.  The call enqueues the stencil and the finish kernel and returns;
+// the first accessor reads the counters (one wait), runs the job again in an arena of the size the counters ask for when the
+// typical-size one was too small, and brings the keys over to order them: the list order is the ascending order of the keys
+// (std::sort on the host -- DESIGN.md 4.5 has the measurement behind that choice), applied to the columns as they are fetched.
+struct PeakJob {
+    pdbeda_ctx *ctx = nullptr;
+    pdbeda_map *map = nullptr;
+    Arena arena;
+    PeakJobArgs args;
+    pdbeda_bloblist *blobs[2] = {nullptr, nullptr};   // the caller's lists (alive until the first accessor has returned: include/pdbeda.h)
+    int refs = 0, reruns = 0;
+    size_t bytes = 0;
+    bool resolved = false;
+    int64_t n[2] = {0, 0}, tested[2] = {0, 0};
+    std::vector<uint32_t> order[2];                   // list position -> arena slot
+};
+struct pdbeda_peaklist {
+    PeakJob *job = nullptr;
+    int plane = 0;
+    bool freed = false;
+};
+
+// Carve and enqueue.  seg[p]: keys a tile's segment of plane p holds; cap[p]: peaks its compact list holds.  The label volumes of lists that were made without PDBEDA_FLAG_LABELS
+// are written into the job's own arena (two lists of one fused labelling job share one signed volume).
+static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]) {
+    pdbeda_ctx *ctx = pj->ctx;
+    pdbeda_map *m = pj->map;
+    PeakJobArgs &a = pj->args;
+    const int64_t nvox = (int64_t)a.uc * a.ur * a.us;
+    const int32_t *have[2] = {nullptr, nullptr};
+    bool need_own[2] = {false, false};
+    for (int p = 0; p < a.n_planes; ++p) {
+        pdbeda_bloblist *bl = pj->blobs[p];
+        if (!bl) continue;
+        if (bl->labels_dev && bl->labels_done) have[p] = bl->labels_dev;
+        else need_own[p] = true;
+    }
+    // (the two lists of ONE fused labelling job: one signed volume serves both planes)
+    const bool shared = need_own[0] && need_own[1] && pj->blobs[0]->job.ctr == pj->blobs[1]->job.ctr;
+    if (shared) need_own[1] = false;
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver cv(pass ? pj->arena.base : nullptr);
+        a.ctr = cv.take<PeakCounters>(1);
+        int32_t *own[2] = {nullptr, nullptr};
+        for (int p = 0; p < a.n_planes; ++p) {
+            PeakPlane &pl = a.plane[p];
+            const size_t k = (size_t)cap[p];
+            pl.cap = (unsigned long long)cap[p];
+            pl.seg = (uint32_t)seg[p];
+            pl.seg_keys = cv.take<unsigned long long>((size_t)a.n_tiles * (size_t)seg[p]);
+            pl.tile_count = cv.take<uint32_t>((size_t)a.n_tiles);
+            pl.tile_tested = cv.take<uint32_t>((size_t)a.n_tiles);
+            pl.tile_off = cv.take<uint32_t>((size_t)a.n_tiles);
+            pl.keys = cv.take<unsigned long long>(k);
+            pl.xyz = cv.take<double>(3 * k);
+            pl.refined = cv.take<double>(k);
+            pl.crs = cv.take<int32_t>(3 * k);
+            pl.height = cv.take<float>(k);
+            pl.blob = cv.take<int32_t>(k);
+            pl.border = cv.take<uint8_t>(k);
+            if (need_own[p]) own[p] = cv.take<int32_t>((size_t)nvox);
+            pl.labels = have[p] ? have[p] : (need_own[p] ? own[p] : ((p == 1 && shared) ? own[0] : nullptr));
+        }
+        if (pass == 0) {
+            need = cv.off;
+            const int rc = arena_get(ctx, need, &pj->arena);
+            if (rc) return rc;
+        }
+    }
+    pj->bytes = need;
+    hipError_t e = hipSuccess;
+    {   // (nothing to clear: the stencil stores every tile's counts, the scan every counter)
+        for (int p = 0; p < a.n_planes; ++p)
+            if (need_own[p]) launch_labels<false>(ctx, pj->blobs[p]->job, pj->blobs[p]->td, const_cast<int32_t *>(a.plane[p].labels), m->geom_dev);
+        const dim3 grid((unsigned)((a.uc + PK_C - 1) / PK_C), (unsigned)((a.ur + PK_R - 1) / PK_R), (unsigned)((a.us + PK_S - 1) / PK_S));
+        { PROF(ctx, "k_peak_stencil"); hipLaunchKernelGGL(k_peak_stencil, grid, dim3(PK_THREADS), 0, ctx->stream, a, m->dens); }
+        { PROF(ctx, "k_peak_scan"); hipLaunchKernelGGL(k_peak_scan, dim3(1), dim3(PK_SCAN_THREADS), 0, ctx->stream, a); }
+        const int64_t most = (int64_t)a.n_tiles * std::max<int64_t>(seg[0], a.n_planes > 1 ? seg[1] : 0);
+        { PROF(ctx, "k_peak_finish"); hipLaunchKernelGGL(k_peak_finish, dim3(grid_for(most, 256, 2048)), dim3(256), 0, ctx->stream, a, m->dens, m->geom_dev); }
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { arena_put(ctx, pj->arena); return fail(ctx, PDBEDA_ERR_DEVICE, "peak search launch: %s", hipGetErrorString(e)); }
+    return PDBEDA_OK;
+}
+
+// A blob list handed to a peak call: a live whole-map list of the same map, sign and float32 cutoff.  Its counters are read
+// here (a wait; a labelling job whose typical-size arena overflowed runs again now), so that its label volume is final.
+static int peaks_check_blobs(pdbeda_map *m, pdbeda_bloblist *bl, int sign, float cutoff) {
+    if (!bl) return PDBEDA_OK;
+    pdbeda_ctx *ctx = m->ctx;
+    if (bl->freed || !bl->whole_map || bl->map != m || bl->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "peaks: the blob list is not a whole-map list of this map");
+    if (bl->sign != sign || (sign > 0 ? bl->cut_pos : bl->cut_neg) != cutoff)
+        return fail(ctx, PDBEDA_ERR_ARGUMENT, "peaks: the blob list was made with another cutoff (%g, asked for %g)", (double)(bl->sign > 0 ? bl->cut_pos : bl->cut_neg), (double)cutoff);
+    return list_resolve_counts(bl);
+}
+
+static int peaks_impl(pdbeda_map *m, int n_planes, const float cut[2], const int sign[2], pdbeda_bloblist *const blobs[2], pdbeda_peaklist **out[2]) {
+    pdbeda_ctx *ctx = m->ctx;
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const Geom &g = m->geom;
+    const int64_t nvox = (int64_t)g.unique_ncrs[0] * g.unique_ncrs[1] * g.unique_ncrs[2];
+    if (nvox >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");       // (the c-major position is the low word of a key)
+    if ((g.unique_ncrs[1] + PK_R - 1) / PK_R > 65535 || (g.unique_ncrs[2] + PK_S - 1) / PK_S > 65535) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");
+    const int64_t n_tiles = (int64_t)((g.unique_ncrs[0] + PK_C - 1) / PK_C) * ((g.unique_ncrs[1] + PK_R - 1) / PK_R) * ((g.unique_ncrs[2] + PK_S - 1) / PK_S);
+    if (n_tiles * 512 >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");      // (a tile holds at most 512 peaks: no two are neighbours)
+    for (int p = 0; p < n_planes; ++p) {
+        const int rc = peaks_check_blobs(m, blobs[p], sign[p], cut[p]);
+        if (rc) return rc;
+    }
+    PeakJob *pj = new PeakJob();
+    pj->ctx = ctx;
+    pj->map = m;
+    memset(&pj->args, 0, sizeof pj->args);
+    PeakJobArgs &a = pj->args;
+    a.n_planes = n_planes;
+    a.uc = g.unique_ncrs[0]; a.ur = g.unique_ncrs[1]; a.us = g.unique_ncrs[2];
+    a.nc = g.ncrs[0]; a.nr = g.ncrs[1];
+    a.n_tiles = (int32_t)n_tiles;
+    // typical size: a peak per 64 voxels of a tile (a smooth map at 1.5 sigma has one per several hundred; white noise, one per 27, runs twice)
+    int64_t cap[2] = {0, 0}, seg[2] = {0, 0};
+    for (int p = 0; p < n_planes; ++p) {
+        a.plane[p].cut = cut[p];
+        a.plane[p].sign = sign[p];
+        pj->blobs[p] = blobs[p];
+        seg[p] = PK_C * PK_R * PK_S / 64;
+        cap[p] = n_tiles * seg[p];
+    }
+    const int rc = peaks_enqueue(pj, cap, seg);
+    if (rc) { delete pj; return rc; }
+    for (int p = 0; p < n_planes; ++p) {
+        pdbeda_peaklist *pl = new pdbeda_peaklist();
+        pl->job = pj;
+        pl->plane = p;
+        pj->refs++;
+        ctx->live_handles++;
+        *out[p] = pl;
+    }
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_map_peaks(pdbeda_map *m, float cutoff, pdbeda_bloblist *blobs, pdbeda_peaklist **out) {
+    if (!m || !out) return PDBEDA_ERR_ARGUMENT;
+    *out = nullptr;
+    if (cutoff == 0.0f || cutoff != cutoff) return fail(m->ctx, PDBEDA_ERR_ARGUMENT, "cutoff must be non-zero");
+    const float cut[2] = {cutoff, 0.0f};
+    const int sign[2] = {cutoff > 0 ? 1 : -1, 0};
+    pdbeda_bloblist *const bl[2] = {blobs, nullptr};
+    pdbeda_peaklist **outs[2] = {out, nullptr};
+    return peaks_impl(m, 1, cut, sign, bl, outs);
+}
+
+extern "C" int pdbeda_map_peaks_pm(pdbeda_map *m, float cutoff_pos, float cutoff_neg, pdbeda_bloblist *green, pdbeda_bloblist *red,
+                                   pdbeda_peaklist **pos, pdbeda_peaklist **neg) {
+    if (!m || !pos || !neg) return PDBEDA_ERR_ARGUMENT;
+    *pos = *neg = nullptr;
+    if (!(cutoff_pos > 0.0f) || !(cutoff_neg < 0.0f)) return fail(m->ctx, PDBEDA_ERR_ARGUMENT, "need cutoff_pos > 0 > cutoff_neg");
+    const float cut[2] = {cutoff_pos, cutoff_neg};
+    const int sign[2] = {1, -1};
+    pdbeda_bloblist *const bl[2] = {green, red};
+    pdbeda_peaklist **outs[2] = {pos, neg};
+    return peaks_impl(m, 2, cut, sign, bl, outs);
+}
+
+static int peaks_resolve(PeakJob *pj) {
+    if (pj->resolved) return 0;
+    pdbeda_ctx *ctx = pj->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int np = pj->args.n_planes;
+    PeakCounters c;
+    for (;;) {
+        HIP_TRY(ctx, d2h(ctx, &c, pj->args.ctr, sizeof c));
+        HIP_TRY(ctx, ctx_sync(ctx));
+        bool over = false;
+        for (int p = 0; p < np; ++p) over = over || c.max_tile[p] > pj->args.plane[p].seg || c.peaks[p] > pj->args.plane[p].cap;
+        if (!over) break;
+        // the typical-size arena was too small for this map: once more, in one of the size the counters name
+        if (pj->reruns) return fail(ctx, PDBEDA_ERR_STATE, "peak search overflowed an arena sized from its own count");
+        int64_t cap[2] = {0, 0}, seg[2] = {0, 0};
+        for (int p = 0; p < np; ++p) {
+            seg[p] = std::max<int64_t>((int64_t)pj->args.plane[p].seg, (int64_t)c.max_tile[p]);
+            cap[p] = std::max<int64_t>(1, (int64_t)c.peaks[p]);
+        }
+        arena_put(ctx, pj->arena);                         // (stream order: the first run is done -- ctx_sync above)
+        const int rc = peaks_enqueue(pj, cap, seg);
+        if (rc) { pj->arena.base = nullptr; pj->arena.cap = 0; return rc; }
+        pj->reruns = 1;
+    }
+    std::vector<unsigned long long> keys[2];
+    for (int p = 0; p < np; ++p) {
+        pj->n[p] = (int64_t)c.peaks[p];
+        pj->tested[p] = (int64_t)c.tested[p];
+        keys[p].resize((size_t)pj->n[p]);
+        HIP_TRY(ctx, d2h(ctx, keys[p].data(), pj->args.plane[p].keys, 8 * (size_t)pj->n[p]));
+    }
+    HIP_TRY(ctx, ctx_sync(ctx));
+    const auto sort_t0 = std::chrono::steady_clock::now();
+    for (int p = 0; p < np; ++p) {
+        std::vector<uint32_t> &ord = pj->order[p];
+        std::vector<std::pair<unsigned long long, uint32_t>> kv(keys[p].size());      // (sorted in place: no indirection in the comparisons)
+        for (size_t i = 0; i < kv.size(); ++i) kv[i] = {keys[p][i], (uint32_t)i};
+        std::sort(kv.begin(), kv.end());                                              // (keys are unique: one order)
+        ord.resize(kv.size());
+        for (size_t i = 0; i < kv.size(); ++i) ord[i] = kv[i].second;
+    }
+    if (ctx->profiling) ctx->prof_host.push_back({"host_peak_sort", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sort_t0).count()});
+    pj->resolved = true;
+    return 0;
+}
+
+extern "C" int64_t pdbeda_peaklist_count(pdbeda_peaklist *pl) {
+    if (!pl || pl->freed) return PDBEDA_ERR_ARGUMENT;
+    const int rc = peaks_resolve(pl->job);
+    if (rc) return rc;
+    return pl->job->n[pl->plane];
+}
+
+template <typename T>
+static void peaks_permute(const std::vector<uint32_t> &ord, const std::vector<T> &src, T *dst, int width) {
+    for (size_t i = 0; i < ord.size(); ++i)
+        for (int k = 0; k < width; ++k) dst[width * i + k] = src[(size_t)width * ord[i] + k];
+}
+
+extern "C" int pdbeda_peaklist_rows(pdbeda_peaklist *pl, int32_t *crs, float *height, double *refined_xyz, double *refined_height,
+                                    int32_t *blob, uint8_t *on_border) {
+    if (!pl || pl->freed) return PDBEDA_ERR_ARGUMENT;
+    PeakJob *pj = pl->job;
+    const int rc = peaks_resolve(pj);
+    if (rc) return rc;
+    pdbeda_ctx *ctx = pj->ctx;
+    const PeakPlane &dp = pj->args.plane[pl->plane];
+    const size_t n = (size_t)pj->n[pl->plane];
+    if (n == 0) return PDBEDA_OK;
+    std::vector<int32_t> h_crs(crs ? 3 * n : 0), h_blob(blob ? n : 0);
+    std::vector<float> h_height(height ? n : 0);
+    std::vector<double> h_xyz(refined_xyz ? 3 * n : 0), h_ref(refined_height ? n : 0);
+    std::vector<uint8_t> h_border(on_border ? n : 0);
+    if (crs) HIP_TRY(ctx, d2h(ctx, h_crs.data(), dp.crs, 12 * n));
+    if (height) HIP_TRY(ctx, d2h(ctx, h_height.data(), dp.height, 4 * n));
+    if (refined_xyz) HIP_TRY(ctx, d2h(ctx, h_xyz.data(), dp.xyz, 24 * n));
+    if (refined_height) HIP_TRY(ctx, d2h(ctx, h_ref.data(), dp.refined, 8 * n));
+    if (blob) HIP_TRY(ctx, d2h(ctx, h_blob.data(), dp.blob, 4 * n));
+    if (on_border) HIP_TRY(ctx, d2h(ctx, h_border.data(), dp.border, n));
+    HIP_TRY(ctx, ctx_sync(ctx));
+    const std::vector<uint32_t> &ord = pj->order[pl->plane];
+    if (crs) peaks_permute(ord, h_crs, crs, 3);
+    if (height) peaks_permute(ord, h_height, height, 1);
+    if (refined_xyz) peaks_permute(ord, h_xyz, refined_xyz, 3);
+    if (refined_height) peaks_permute(ord, h_ref, refined_height, 1);
+    if (blob) peaks_permute(ord, h_blob, blob, 1);
+    if (on_border) peaks_permute(ord, h_border, on_border, 1);
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_peaklist_counters(pdbeda_peaklist *pl, int64_t *out) {
+    if (!pl || pl->freed || !out) return PDBEDA_ERR_ARGUMENT;
+    const int rc = peaks_resolve(pl->job);
+    if (rc) return rc;
+    out[0] = pl->job->tested[pl->plane];
+    out[1] = pl->job->n[pl->plane];
+    out[2] = pl->job->reruns;
+    out[3] = (int64_t)pl->job->bytes;
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_peaklist_free(pdbeda_peaklist *pl) {
+    if (!pl) return PDBEDA_ERR_ARGUMENT;
+    if (pl->freed) return PDBEDA_ERR_STATE;
+    PeakJob *pj = pl->job;
+    pl->freed = true;
+    pj->ctx->live_handles--;
+    if (--pj->refs == 0) {   // last list of the job: the arena is recycled in stream order, as a blob list's
+        arena_put(pj->ctx, pj->arena);
+        delete pj;
+    }
+    delete pl;
     return PDBEDA_OK;
 }
 

@@ -311,6 +311,8 @@ class DensityAnalysis(object):
     domainCloudHeader = residueCloudHeader
     blobStatisticsHeader = ['distance_to_atom', 'sign', 'electrons_of_discrepancy', 'num_voxels', 'volume', 'chain', 'residue_number', 'residue_name',
                             'atom_name', 'atom_symmetry', 'atom_xyz', 'centroid_xyz']
+    peakStatisticsHeader = ['distance_to_atom', 'sign', 'height_in_sigma', 'height_in_electrons_per_A3', 'blob_index', 'on_border', 'chain', 'residue_number',
+                            'residue_name', 'atom_name', 'symmetry', 'atom_xyz', 'peak_xyz']
     regionDensityHeader = ["actual_significant_regional_density", "num_electrons_actual_significant_regional_density"]
     atomRegionDensityHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy"] + regionDensityHeader
     symmetryAtomRegionDensityHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "symmetry", "atom_xyz", "fully_within_density_map"] + regionDensityHeader
@@ -339,6 +341,9 @@ class DensityAnalysis(object):
         self._greenBlobList = None
         self._redBlobList = None
         self._blueBlobList = None
+        self._greenPeakList = None
+        self._redPeakList = None
+        self._bluePeakList = None
         self._medians = None
         self._atomCloudDescriptions = None
         self._residueCloudDescriptions = None
@@ -425,6 +430,33 @@ class DensityAnalysis(object):
         if self._blueBlobList is None:
             self._blueBlobList = self.densityObj.createFullBlobList(self.densityObj.densityCutoff)
         return self._blueBlobList
+
+    # ---- peak lists (no reference counterpart): local extrema, tied to the blob lists above ----
+    def _greenRedPeaks(self):
+        # ONE fused pass over the Fo-Fc grid gives both lists; the blob lists at the same cutoff give every peak its blob
+        diff = self.diffDensityObj
+        self._greenPeakList, self._redPeakList = diff.findPeakLists(diff.diffDensityCutoff, (self.greenBlobList, self.redBlobList))
+
+    @property
+    def greenPeakList(self):
+        """Maxima of the Fo-Fc map at or above ``diffDensityCutoff`` (3 sigma), strongest first."""
+        if self._greenPeakList is None:
+            self._greenRedPeaks()
+        return self._greenPeakList
+
+    @property
+    def redPeakList(self):
+        """Minima of the Fo-Fc map at or below ``-diffDensityCutoff``, deepest first."""
+        if self._redPeakList is None:
+            self._greenRedPeaks()
+        return self._redPeakList
+
+    @property
+    def bluePeakList(self):
+        """Maxima of the 2Fo-Fc map at or above ``densityCutoff``."""
+        if self._bluePeakList is None:
+            self._bluePeakList = self.densityObj.findPeaks(self.densityObj.densityCutoff, self.blueBlobList)
+        return self._bluePeakList
 
     # ---- aggregateCloud (ref densityAnalysis.py:571-780) --------------------------------------
     def _cloudInputs(self):
@@ -757,6 +789,40 @@ class DensityAnalysis(object):
         return self._rows(list(dist), sign, np.abs(total / ratio), num_voxels, volume,
                           (chain, rows), (number, rows), (resname, rows), (cols.name if isinstance(cols.name, (list, tuple)) else list(cols.name), rows),       # (picked by _rows)
                           symmetry, coords, centroid)
+
+    # ---- peak statistics (no reference counterpart; built like the blob table above) ------------
+    def calculateAtomSpecificPeakStatistics(self, peakList):
+        """One row per peak (``peakStatisticsHeader``): the nearest symmetry atom is taken from the REFINED peak position;
+        height in units of the map's standard deviation and in electrons per cubic Angstrom (height / densityElectronRatio)."""
+        symmetryAtoms = self.symmetryAtoms
+        symmetryAtomCoords = self.symmetryAtomCoords
+        if not self.densityElectronRatio:
+            raise RuntimeError("Failed to calculate densityElectronRatio, probably due to total aggregated electrons less than the minimum.")
+        ratio = self.densityElectronRatio
+        if not peakList:
+            return []
+        if len(symmetryAtomCoords) == 0:
+            raise ValueError("XB must be a 2-dimensional array.")       # (the blob table's failure for a file without operators)
+        if isinstance(peakList, ccp4.DevicePeaks):
+            listed, std = peakList.columns(), peakList.densityMatrix.stdDensity
+            peak_xyz = np.ascontiguousarray(listed["xyz"], dtype=np.float64)
+            height = np.asarray(listed["height"], dtype=np.float64)
+            blob, border = np.asarray(listed["blobIndex"], dtype=np.int64), np.asarray(listed["onBorder"], dtype=np.bool_)
+        else:
+            std = peakList[0].densityMatrix.stdDensity
+            peak_xyz = np.array([peak.xyz for peak in peakList], dtype=np.float64)
+            height = np.array([peak.height for peak in peakList], dtype=np.float64)
+            blob = np.array([peak.blobIndex for peak in peakList], dtype=np.int64)
+            border = np.array([peak.onBorder for peak in peakList], dtype=np.bool_)
+        idx, dist = self.densityObj._ctx.nearest_atom(peak_xyz, np.asarray(symmetryAtomCoords, dtype=np.float64))
+        rows, symmetry, coords = symmetryAtoms.columns(idx)
+        cols = _structure.columns(self.biopdbObj)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        chain, number, resname = (cols.atom_lists(which) for which in ("chain", "number", "resname"))
+        sign = np.where(height >= 0, '+', '-').tolist()
+        return self._rows(list(dist), sign, height / std, height / ratio, blob, border,
+                          (chain, rows), (number, rows), (resname, rows), (cols.name if isinstance(cols.name, (list, tuple)) else list(cols.name), rows),
+                          symmetry, coords, peak_xyz)
 
     # ---- Fo / Fc maps, RSCC / RSR (ref densityAnalysis.py:426-446, 783-882) -------------------
     @property

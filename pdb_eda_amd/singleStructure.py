@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak")
 
 
 def numpyConverter(obj):
@@ -51,6 +51,23 @@ def _blobTable(analyzer, o):
     return _plainColumns(table, listColumns=(9,), floatColumns=(10, 11))
 
 
+def _peakTable(analyzer, o):
+    """peak sub-mode (no reference counterpart): the local extrema of the green and / or red Fo-Fc map, else of the blue 2Fo-Fc
+    map, each with its blob of the blob sub-mode's list at the same cutoff and its nearest symmetry atom."""
+    diffObj, densObj, numSD = analyzer.diffDensityObj, analyzer.densityObj, o["numSD"]
+    if o["green"] and o["red"]:          # one fused pass over the Fo-Fc grid gives both lists
+        cut = diffObj.meanDensity + numSD * diffObj.stdDensity
+        lists = diffObj.findPeakLists(cut, diffObj.createFullBlobLists(cut))
+    elif o["green"] or o["red"]:
+        cut = (1 if o["green"] else -1) * (diffObj.meanDensity + numSD * diffObj.stdDensity)
+        lists = [diffObj.findPeaks(cut, diffObj.createFullBlobList(cut))]
+    else:
+        cut = densObj.meanDensity + numSD * densObj.stdDensity
+        lists = [densObj.findPeaks(cut, densObj.createFullBlobList(cut))]
+    table = [row for peaks in lists for row in analyzer.calculateAtomSpecificPeakStatistics(peaks)]
+    return _plainColumns(table, listColumns=(10,), floatColumns=(11, 12))
+
+
 def _cloudTable(attribute):
     def table(analyzer, o):
         return [[numpyConverter(v) for v in item] + [analyzer.densityElectronRatio] for item in getattr(analyzer, attribute)]
@@ -79,6 +96,7 @@ TABLES = {
     ("difference", "symmetry-atom"): (lambda an: _DA.symmetryAtomRegionDiscrepancyHeader,
                                       lambda an, o: _plainColumns(an.calculateSymmetryAtomRegionDiscrepancies(o["radius"], o["numSD"], o["type"]), **_SYM)),
     ("blob", None): (lambda an: _DA.blobStatisticsHeader, _blobTable),
+    ("peak", None): (lambda an: _DA.peakStatisticsHeader, _peakTable),
     ("statistics", "residue"): (lambda an: an.residueMetricsHeaderList, lambda an, o: an.residueMetrics()),
     ("statistics", "atom"): (lambda an: an.atomMetricsHeaderList, lambda an, o: _plainColumns(an.atomMetrics(), **_SYM)),
 }
@@ -88,12 +106,12 @@ def rows(analyzer, mode, level="atom", radius=3.5, numSD=None, type="", atomMask
          includePdbid=False):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics;  level: atom | residue | domain | symmetry-atom
-    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob);  green / red: blob colours
+    mode: cloud | density | difference | blob | statistics | peak;  level: atom | residue | domain | symmetry-atom
+    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob and peak);  green / red: blob / peak colours
     (neither = blue);  numSD default 3.0 for green / red / difference, else 1.5 (singleStructure.py:65-67)."""
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % (MODES,))
-    key = (mode, None if mode == "blob" else level)
+    key = (mode, None if mode in ("blob", "peak") else level)
     if key not in TABLES:
         raise ValueError("%s mode has the levels %s" % (mode, ", ".join(lv for md, lv in TABLES if md == mode and lv)))
     options = {"radius": float(radius), "numSD": float(numSD if numSD is not None else (3.0 if green or red or mode == "difference" else 1.5)),
