@@ -263,7 +263,11 @@ static hipError_t ctx_wait(pdbeda_ctx *ctx) {
 // upload engine has queued (up to 0.46 ms), and each hop between the compute queue and the copy engine is a semaphore: the analysis of a resident
 // entry 0.48 -> 0.44 ms alone, 0.68-0.80 -> 0.60 beside two uploading threads; four workers 41.6 k -> 44.5 k entries/min.  PDBEDA_COPY_KERNELS=0: the
 // runtime's copies (A/B).
-static bool copy_kernels() { static const bool v = [] { const char *e = getenv("PDBEDA_COPY_KERNELS"); return !(e && e[0] == '0'); }(); return v; }
+// The two kinds of PDBEDA_* switch (a caller keeps the answer in a function-local static: read once per process, on first use): an A/B switch is on
+// unless it is set to 0; a debug / trace hook is off unless it is set to something else than 0.
+static bool env_unless_0(const char *name) { const char *e = getenv(name); return !(e && e[0] == '0'); }
+static bool env_set(const char *name) { const char *e = getenv(name); return e && e[0] && e[0] != '0'; }
+static bool copy_kernels() { static const bool v = env_unless_0("PDBEDA_COPY_KERNELS"); return v; }
 static hipError_t copy_by_kernel(pdbeda_ctx *ctx, void *dst, const void *src, size_t bytes) {
     hipLaunchKernelGGL(k_copy_bytes, dim3((unsigned)std::min<size_t>((bytes >> 12) + 1, 64)), dim3(256), 0, ctx->stream, (const unsigned char *)src, (unsigned char *)dst,
                        (unsigned long long)bytes);
@@ -280,17 +284,41 @@ static hipError_t ctx_sync(pdbeda_ctx *ctx) {
     return e;
 }
 
+// The pinned block's ONE allocator: everything staged in it -- inputs the host writes, results kernels write -- is a take, handed out until the next
+// ctx_sync() rewinds the block.  A take occupies whole 64-byte lines ((bytes + 63) & ~63: an EMPTY take occupies none and shares its address with the
+// next one; a caller whose kernel wants a place of its own for an empty item takes a byte), so the room left is always a multiple of 64 and "N bytes
+// fit" is plainly N <= pinned_room().
+static inline size_t pinned_span(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+static inline size_t pinned_room(const pdbeda_ctx *ctx) { return ctx->pinned_cap - ctx->pinned_used; }      // (0 without a block)
+// The next ctx_sync() delivers `bytes` at `from` (inside a take) to `dst`.
+static inline void pinned_deliver(pdbeda_ctx *ctx, const char *from, void *dst, size_t bytes) { ctx->pending.push_back({dst, (size_t)(from - ctx->pinned), bytes}); }
+// nullptr: no block, or no room.  deliver_to: where the next ctx_sync() copies the take's bytes (nothing for an empty take).
+static char *pinned_take(pdbeda_ctx *ctx, size_t bytes, void *deliver_to = nullptr) {
+    if (!ctx->pinned || pinned_span(bytes) > pinned_room(ctx)) return nullptr;
+    char *p = ctx->pinned + ctx->pinned_used;
+    if (deliver_to && bytes) pinned_deliver(ctx, p, deliver_to, bytes);
+    ctx->pinned_used += pinned_span(bytes);
+    return p;
+}
+// A caller whose launch failed (or that found it cannot use what it took) hands back `first` and every take after it, deliveries included: the block
+// and the pending list are as they were before `first` was taken -- a failed call delivers nothing.
+static void pinned_untake(pdbeda_ctx *ctx, const char *first) {
+    ctx->pinned_used = (size_t)(first - ctx->pinned);
+    while (!ctx->pending.empty() && ctx->pending.back().off >= ctx->pinned_used) ctx->pending.pop_back();
+}
+// The copy between a take and device memory (by kernel, or PDBEDA_COPY_KERNELS=0: by the runtime); a take whose copy could not be launched is handed back.
+static hipError_t stage_copy(pdbeda_ctx *ctx, char *stage, void *dev, size_t bytes, bool to_device) {
+    void *dst = to_device ? dev : stage, *src = to_device ? stage : dev;
+    const hipError_t e = copy_kernels() ? copy_by_kernel(ctx, dst, src, bytes) : hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, ctx->stream);
+    if (e != hipSuccess) pinned_untake(ctx, stage);
+    return e;
+}
+
 // Device -> host copy of a result, complete after the next ctx_sync(): staged through the pinned buffer when it fits,
 // otherwise the stream is drained first (timed) so that the blocking copy into pageable memory has nothing to wait for.
 static hipError_t d2h(pdbeda_ctx *ctx, void *dst, const void *src, size_t bytes) {
     if (bytes == 0) return hipSuccess;
-    const size_t need = (bytes + 63) & ~(size_t)63;
-    if (ctx->pinned && ctx->pinned_used + need <= ctx->pinned_cap) {
-        const hipError_t e = copy_kernels() ? copy_by_kernel(ctx, ctx->pinned + ctx->pinned_used, src, bytes)
-                                            : hipMemcpyAsync(ctx->pinned + ctx->pinned_used, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) { ctx->pending.push_back({dst, ctx->pinned_used, bytes}); ctx->pinned_used += need; }
-        return e;
-    }
+    if (char *stage = pinned_take(ctx, bytes, dst)) return stage_copy(ctx, stage, const_cast<void *>(src), bytes, false);
     hipError_t e = ctx_sync(ctx);
     if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
     return e;
@@ -388,14 +416,11 @@ static hipError_t h2d_row(pdbeda_ctx *ctx, const H2DItem *items, int n, size_t m
         if (!hi || d + items[k].bytes > hi) hi = d + items[k].bytes;
     }
     if (!lo) return hipSuccess;
-    const size_t span = (size_t)(hi - lo), need = (span + 63) & ~(size_t)63;
-    if (ctx->pinned && span <= max_span && ctx->pinned_used + need <= ctx->pinned_cap) {
-        char *stage = ctx->pinned + ctx->pinned_used;
+    const size_t span = (size_t)(hi - lo);
+    if (char *stage = span <= max_span ? pinned_take(ctx, span) : nullptr) {
         for (int k = 0; k < n; ++k)
             if (items[k].bytes) memcpy(stage + ((char *)items[k].dst - lo), items[k].src, items[k].bytes);
-        const hipError_t e = copy_kernels() ? copy_by_kernel(ctx, lo, stage, span) : hipMemcpyAsync(lo, stage, span, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) ctx->pinned_used += need;
-        return e;
+        return stage_copy(ctx, stage, lo, span, true);
     }
     for (int k = 0; k < n; ++k) {
         if (items[k].bytes == 0) continue;
@@ -421,30 +446,30 @@ static hipError_t d2h_many(pdbeda_ctx *ctx, const D2HItem *items, int n_items) {
         if (!items[k].dst || items[k].bytes == 0) continue;
         if (n == 8 || (items[k].bytes & 3u) || ((uintptr_t)items[k].src & 3u)) { packable = false; break; }
         live[n++] = k;
-        total += (items[k].bytes + 63) & ~(size_t)63;
+        total += pinned_span(items[k].bytes);
     }
     const bool via_dev_stage = !copy_kernels();      // (with copy kernels k_pack writes straight into the pinned block: nothing is staged on the device)
-    if (packable && n >= 2 && (!via_dev_stage || ctx->dev_stage_used + total <= ctx->dev_stage_cap) && ctx->pinned_used + total <= ctx->pinned_cap) {
+    if (packable && n >= 2 && (!via_dev_stage || ctx->dev_stage_used + total <= ctx->dev_stage_cap) && total <= pinned_room(ctx)) {
         PackArgs a;
         memset(&a, 0, sizeof a);
         a.n = n;
-        size_t off = 0, words = 0;
+        size_t words = 0;
+        char *pack = nullptr;      // (the items' takes lie in a row: `total` bytes from the first)
         for (int j = 0; j < n; ++j) {
             const D2HItem &it = items[live[j]];
+            char *p = pinned_take(ctx, it.bytes, it.dst);
+            if (j == 0) pack = p;
             a.seg[j].src = reinterpret_cast<const uint32_t *>(it.src);
             a.seg[j].words = it.bytes / 4;
-            a.seg[j].dst_word = off / 4;
-            ctx->pending.push_back({it.dst, ctx->pinned_used + off, it.bytes});
-            off += (it.bytes + 63) & ~(size_t)63;
+            a.seg[j].dst_word = (size_t)(p - pack) / 4;
             words = std::max<size_t>(words, it.bytes / 4);
         }
-        char *block = copy_kernels() ? ctx->pinned + ctx->pinned_used : ctx->dev_stage + ctx->dev_stage_used;   // (packed straight into the pinned block)
+        char *block = copy_kernels() ? pack : ctx->dev_stage + ctx->dev_stage_used;   // (packed straight into the pinned block)
         hipLaunchKernelGGL(k_pack, dim3(grid_for((int64_t)words, 256, 256)), dim3(256), 0, ctx->stream, a, reinterpret_cast<uint32_t *>(block));
         hipError_t e = hipGetLastError();
-        if (e == hipSuccess && !copy_kernels()) e = hipMemcpyAsync(ctx->pinned + ctx->pinned_used, block, total, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) { for (int j = 0; j < n; ++j) ctx->pending.pop_back(); return e; }
+        if (e == hipSuccess && !copy_kernels()) e = hipMemcpyAsync(pack, block, total, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) { pinned_untake(ctx, pack); return e; }
         if (via_dev_stage) ctx->dev_stage_used += total;
-        ctx->pinned_used += total;
         return hipSuccess;
     }
     for (int k = 0; k < n_items; ++k) {
@@ -464,21 +489,17 @@ static hipError_t d2h_many(pdbeda_ctx *ctx, const D2HItem *items, int n_items) {
 // (An input that threads read many times -- the atoms of a nearest-atom search -- belongs in device memory: a copy launch is cheaper than the link.)
 template <typename T>
 static T *pinned_out(pdbeda_ctx *ctx, T *dst, size_t count) {
-    const size_t bytes = sizeof(T) * count, need = (bytes + 63) & ~(size_t)63;
-    if (!copy_kernels() || !ctx->pinned || !dst || bytes == 0 || ctx->pinned_used + need > ctx->pinned_cap) return nullptr;
-    T *p = reinterpret_cast<T *>(ctx->pinned + ctx->pinned_used);
-    ctx->pending.push_back({dst, ctx->pinned_used, bytes});
-    ctx->pinned_used += need;
-    return p;
+    const size_t bytes = sizeof(T) * count;
+    if (!copy_kernels() || !dst || bytes == 0) return nullptr;
+    return reinterpret_cast<T *>(pinned_take(ctx, bytes, dst));
 }
 template <typename T>
 static const T *pinned_in(pdbeda_ctx *ctx, const T *src, size_t count) {
-    const size_t bytes = sizeof(T) * count, need = (bytes + 63) & ~(size_t)63;
-    if (!copy_kernels() || !ctx->pinned || !src || bytes == 0 || ctx->pinned_used + need > ctx->pinned_cap) return nullptr;
-    T *p = reinterpret_cast<T *>(ctx->pinned + ctx->pinned_used);
-    memcpy(p, src, bytes);
-    ctx->pinned_used += need;
-    return p;
+    const size_t bytes = sizeof(T) * count;
+    if (!copy_kernels() || !src || bytes == 0) return nullptr;
+    char *p = pinned_take(ctx, bytes);
+    if (p) memcpy(p, src, bytes);
+    return reinterpret_cast<const T *>(p);
 }
 
 template <typename Fn>
@@ -538,10 +559,10 @@ extern "C" int pdbeda_ctx_create_on_stream(int device_id, void *hip_stream, pdbe
     if (hipHostMalloc((void **)&ctx->pinned, 4 << 20, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) ctx->pinned_cap = 4 << 20;   // (without it results are copied directly)
     else (void)hipGetLastError();
     if (ctx->pinned_cap && hipMalloc((void **)&ctx->dev_stage, 2 << 20) == hipSuccess) ctx->dev_stage_cap = 2 << 20; else { ctx->dev_stage = nullptr; (void)hipGetLastError(); }
-    if (const char *v = getenv("PDBEDA_DEBUG_POISON")) ctx->debug_poison = v[0] && v[0] != '0';
-    if (const char *v = getenv("PDBEDA_DEBUG_SHRINK_TOTALS")) ctx->debug_shrink_totals = v[0] && v[0] != '0';
+    ctx->debug_poison = env_set("PDBEDA_DEBUG_POISON");
+    ctx->debug_shrink_totals = env_set("PDBEDA_DEBUG_SHRINK_TOTALS");
     if (const char *v = getenv("PDBEDA_DEBUG_EDGE_CAP")) ctx->debug_edge_cap = atoll(v);
-    if (const char *v = getenv("PDBEDA_DEBUG_WORST_CASE_ARENA")) ctx->debug_worst_case_arena = v[0] && v[0] != '0';
+    ctx->debug_worst_case_arena = env_set("PDBEDA_DEBUG_WORST_CASE_ARENA");
     if (const char *v = getenv("PDBEDA_POOL_CAP_MB")) ctx->pool_cap = (size_t)std::max<long long>(atoll(v), 0) << 20;
     reap_abandoned();   // (what the watchdog left behind earlier may have drained by now)
     {
@@ -1052,11 +1073,10 @@ static int stats_enqueue(pdbeda_map *m, double *chunk_sums, double host[2], doub
     hipStream_t st = ctx->stream;
     // the results' place in the pinned block (kernels write host memory only with PDBEDA_COPY_KERNELS, the default)
     double *host_out = nullptr;
-    if (want_range && copy_kernels() && ctx->pinned && ctx->pinned_used + 64 <= ctx->pinned_cap) {
-        host_out = reinterpret_cast<double *>(ctx->pinned + ctx->pinned_used);
-        ctx->pending.push_back({host, ctx->pinned_used, 2 * sizeof(double)});
-        ctx->pending.push_back({range, ctx->pinned_used + 4 * sizeof(double), 2 * sizeof(double)});
-        ctx->pinned_used += 64;
+    if (want_range && copy_kernels()) host_out = reinterpret_cast<double *>(pinned_take(ctx, 6 * sizeof(double)));      // (the six doubles of res: one 64-byte line)
+    if (host_out) {
+        pinned_deliver(ctx, (char *)host_out, host, 2 * sizeof(double));
+        pinned_deliver(ctx, (char *)(host_out + 4), range, 2 * sizeof(double));
     }
     double *r_sum = want_range ? chunk_sums + n_chunks : nullptr, *r_max = want_range ? chunk_sums + 2 * n_chunks : nullptr;
     for (int mode = 0; mode < 2; ++mode) {
@@ -1075,12 +1095,10 @@ static int stats_enqueue(pdbeda_map *m, double *chunk_sums, double host[2], doub
         return 0;
     }
     // (no room in the pinned block, or the runtime's copies asked for: one copy of the six doubles, or two)
-    if (ctx->pinned && ctx->pinned_used + 64 <= ctx->pinned_cap) {
-        HIP_TRY(ctx, copy_kernels() ? copy_by_kernel(ctx, ctx->pinned + ctx->pinned_used, res, 6 * sizeof(double))
-                                    : hipMemcpyAsync(ctx->pinned + ctx->pinned_used, res, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        ctx->pending.push_back({host, ctx->pinned_used, 2 * sizeof(double)});
-        ctx->pending.push_back({range, ctx->pinned_used + 4 * sizeof(double), 2 * sizeof(double)});
-        ctx->pinned_used += 64;
+    if (char *stage = pinned_take(ctx, 6 * sizeof(double))) {
+        HIP_TRY(ctx, stage_copy(ctx, stage, res, 6 * sizeof(double), false));
+        pinned_deliver(ctx, stage, host, 2 * sizeof(double));
+        pinned_deliver(ctx, stage + 4 * sizeof(double), range, 2 * sizeof(double));
         return 0;
     }
     HIP_TRY(ctx, d2h(ctx, host, res, 2 * sizeof(double)));
@@ -1658,7 +1676,7 @@ static int list_stats_one_trip(pdbeda_bloblist *bl, int64_t guess, std::vector<i
     guess = std::min<int64_t>(guess, (int64_t)job.blob_cap);
     const bool whole_job = !bl->whole_map && bl->vol_lo == 0 && bl->vol_hi == job.n_vols;
     const int64_t extra_bytes = extra ? (int64_t)extra->bytes + 64 : 0;
-    if (!bl->have_counts && whole_job && guess > 0 && 44 * guess + 4096 + extra_bytes < (int64_t)ctx->pinned_cap - (int64_t)ctx->pinned_used) {
+    if (!bl->have_counts && whole_job && guess > 0 && 44 * guess + 4096 + extra_bytes < (int64_t)pinned_room(ctx)) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         n.resize((size_t)guess); tot.resize((size_t)guess); cen.resize(3 * (size_t)guess); grp.resize((size_t)guess);
         Counters ctr;
@@ -2147,6 +2165,16 @@ static int group_alloc(pdbeda_ctx *ctx, int64_t n_items, int64_t n_groups, Group
     return 0;
 }
 
+// Every path that sizes a sphere / list batch ends here -- the device's totals after their round trip, the host's without one: the totals onto the
+// setup, and the one limit on them.
+static int group_sized(pdbeda_ctx *ctx, GroupSetup *gs, int64_t words, int64_t keys, bool by_host) {
+    gs->total_words = words;
+    gs->total_keys = keys;
+    gs->host_totals = by_host;
+    if (words >= (1ll << 31) * 2) return fail(ctx, PDBEDA_ERR_ARGUMENT, "sphere batch too large (%lld mask words)", (long long)words);
+    return 0;
+}
+
 // Inputs are on the device (d_xyz + d_radii, or d_crs; d_item_group): group bounding volumes, volume descriptors, and the
 // totals read back (the one host round trip of a sphere / list batch).
 static int group_bounds(pdbeda_map *m, GroupSetup *gs, int64_t n_items, int64_t n_groups, bool spheres, const int64_t *host_totals = nullptr) {
@@ -2165,20 +2193,57 @@ static int group_bounds(pdbeda_map *m, GroupSetup *gs, int64_t n_items, int64_t 
     { PROF(ctx, "k_make_vols"); hipLaunchKernelGGL(k_make_vols, dim3(1), dim3(1024), 0, st, gs->g_lo, gs->g_hi, (int)n_groups, gs->d_vols, gs->d_ctr,
                                                    host_totals ? (long long)host_totals[0] : LLONG_MAX, host_totals ? (long long)host_totals[1] : LLONG_MAX); }
     HIP_TRY(ctx, hipGetLastError());
-    if (host_totals) {   // sized by the host: no round trip (the kernel holds the device's totals against these)
-        gs->total_words = host_totals[0];
-        gs->total_keys = host_totals[1];
-        gs->host_totals = true;
-        if (gs->total_words >= (1ll << 31) * 2) return fail(ctx, PDBEDA_ERR_ARGUMENT, "sphere batch too large (%lld mask words)", (long long)gs->total_words);
-        return 0;
-    }
+    if (host_totals) return group_sized(ctx, gs, host_totals[0], host_totals[1], true);   // sized by the host: no round trip (the kernel holds the device's totals against these)
     Counters ctr;
     HIP_TRY(ctx, d2h(ctx, &ctr, gs->d_ctr, sizeof ctr));
     HIP_TRY(ctx, ctx_sync(ctx));  // (host-side staging vectors of the caller are also safe to drop now)
-    gs->total_words = ctr.total_words;
-    gs->total_keys = ctr.total_keys;
-    if (gs->total_words >= (1ll << 31) * 2) return fail(ctx, PDBEDA_ERR_ARGUMENT, "sphere batch too large (%lld mask words)", (long long)gs->total_words);
-    return 0;
+    return group_sized(ctx, gs, ctr.total_words, ctr.total_keys, false);
+}
+
+// The host's twin of k_init_bounds + k_atom_boxes + k_make_vols, built on the same statements (sphere_half_widths, atom_box, vol_from_bounds:
+// pdbeda_kernels.h): every atom's box, the box around the boxes of each group's atoms, the groups' volume descriptors and the batch's totals.
+// item_group == nullptr: a group per atom -- atom a's volume is its box.  *small_boxes: every volume is one mask word a row and at most ATOM_WORDS rows.
+// false: a volume, or the totals, beyond what a job addresses (the caller leaves the batch to the device, which sizes and reports).
+static bool host_sphere_volumes(const Geom &geom, const double *xyz, const float *radii, const int32_t *item_group, int64_t n_items, int64_t n_groups,
+                                AtomBox *boxes, VolDesc *vols, int64_t totals[2], bool *small_boxes) {
+    int64_t words = 0, keys = 0;
+    bool fits = true, small = true;
+    auto add_vol = [&](const int32_t *lo, const int32_t *hi, int64_t g) {
+        VolDesc vd;
+        int64_t w = 0, k = 0;
+        fits = vol_from_bounds(lo, hi, (int32_t)g, words, keys, &vd, &w, &k) && fits;
+        vols[g] = vd;
+        small = small && vd.row_words <= 1 && (int64_t)vd.dim[1] * vd.dim[2] <= ATOM_WORDS;
+        words += w;
+        keys += k;
+        fits = fits && words < (1ll << 40) && keys < (1ll << 46);
+    };
+    std::vector<int32_t> glo, ghi;
+    if (item_group) { glo.assign(3 * (size_t)n_groups, INT32_MAX); ghi.assign(3 * (size_t)n_groups, INT32_MIN); }
+    float cached_rad = NAN;      // (a handful of distinct radii, one per atom type: the half-widths are made once per run of equal radii)
+    int32_t R[3] = {0, 0, 0};
+    for (int64_t a = 0; a < n_items; ++a) {
+        if (!(radii[a] == cached_rad)) {
+            sphere_half_widths(geom, (double)radii[a], R);
+            cached_rad = radii[a];
+        }
+        int32_t C[3];
+        xyz2crs(geom, xyz + 3 * a, C);
+        AtomBox bx;
+        const bool empty = !atom_box(C, R, &bx);
+        boxes[a] = bx;
+        if (!item_group) {
+            add_vol(bx.lo, bx.hi, a);
+        } else if (!empty) {
+            const size_t g = (size_t)item_group[(size_t)a];
+            for (int k = 0; k < 3; ++k) { glo[3 * g + k] = std::min(glo[3 * g + k], bx.lo[k]); ghi[3 * g + k] = std::max(ghi[3 * g + k], bx.hi[k]); }
+        }
+    }
+    for (int64_t g = 0; item_group && g < n_groups; ++g) add_vol(&glo[3 * (size_t)g], &ghi[3 * (size_t)g], g);
+    totals[0] = words;
+    totals[1] = keys;
+    *small_boxes = small;
+    return fits;
 }
 
 // Upload atoms (or explicit voxels), then group_bounds.
@@ -2189,7 +2254,13 @@ static int group_setup(pdbeda_map *m, const double *xyz, const float *radii, con
     if (expand_groups(group_offsets, n_groups, n_items, item_group)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "bad group_offsets");
     int rc = group_alloc(ctx, n_items, n_groups, gs);
     if (rc) return rc;
-    hipStream_t st = ctx->stream;
+    // (a staged block mirrors the head of the scratch arena: `staged` is the block's twin of a device pointer)
+    auto staged = [&](char *stage, const void *dev) { return stage + ((const char *)dev - gs->in_arena.base); };
+    auto stage_inputs = [&](char *stage) {      // coordinates, radii and groups at their arena offsets
+        memcpy(staged(stage, gs->d_xyz), xyz, 24 * (size_t)n_items);
+        memcpy(staged(stage, gs->d_radii), radii, 4 * (size_t)n_items);
+        memcpy(staged(stage, gs->d_item_group), item_group.data(), 4 * (size_t)n_items);
+    };
     // Per-atom spheres (a group per atom: the clouds of aggregateCloud, the per-atom region tables): an atom's box is
     // [C - R - 1, C + R] with R = xyz2crs(origin + radius) -- its SIZE follows from the radius alone, so the host knows the
     // job's mask words and keys without asking the device (the round trip for the totals was one of an entry's host waits).
@@ -2198,80 +2269,32 @@ static int group_setup(pdbeda_map *m, const double *xyz, const float *radii, con
     // volume is the box around its atoms' boxes, which is what k_atom_boxes' atomic min / max and k_make_vols make of them on the device (the same
     // xyz2crs, the same int32 arithmetic): k_init_bounds, k_atom_boxes, k_make_vols, the copy of their totals and the WAIT for it go (four launches and
     // one of an entry's waits per grouped call).  PDBEDA_HOST_BOXES=0: the device makes them, as for the per-atom batches.
+    static const bool host_boxes = env_unless_0("PDBEDA_HOST_BOXES");
+    // The row the host makes: inputs, boxes, volumes and counters, as they sit at the head of the scratch arena (group_alloc), staged in the pinned
+    // block.  nullptr, and nothing taken: not allowed, no room, or volumes that do not fit.  made[2]: the batch's mask words and keys.
+    const size_t row = (size_t)((char *)(gs->d_ctr + 1) - gs->in_arena.base);
+    auto host_row = [&](const int32_t *groups, int64_t made[2], bool *small_boxes) -> char * {
+        if (!host_boxes || ctx->debug_shrink_totals || (char *)gs->d_xyz != gs->in_arena.base || row > ((size_t)1 << 20)) return nullptr;
+        char *stage = pinned_take(ctx, row);
+        if (!stage) return nullptr;
+        stage_inputs(stage);
+        if (!host_sphere_volumes(m->geom, xyz, radii, groups, n_items, n_groups, reinterpret_cast<AtomBox *>(staged(stage, gs->d_boxes)),
+                                 reinterpret_cast<VolDesc *>(staged(stage, gs->d_vols)), made, small_boxes)) { pinned_untake(ctx, stage); return nullptr; }
+        Counters *ctr0 = reinterpret_cast<Counters *>(staged(stage, gs->d_ctr));
+        memset(ctr0, 0, sizeof *ctr0);
+        ctr0->total_words = made[0];
+        ctr0->total_keys = made[1];
+        return stage;
+    };
+    auto leave_to_job = [&](char *stage) { gs->pend_src = stage; gs->pend_dst = gs->in_arena.base; gs->pend_bytes = (row + 15) & ~(size_t)15; };   // (copied by the job's first launch; whole 16-byte units: the stage and the carve are padded)
+    int64_t made[2] = {0, 0};
+    bool small_boxes = false;
     if (xyz && n_items > 0 && n_groups > 0 && n_groups < n_items) {
-        static const bool host_boxes_g = [] { const char *e = getenv("PDBEDA_HOST_BOXES"); return !(e && e[0] == '0'); }();
         bool sane = true;
         for (int64_t a = 0; a < n_items && sane; ++a) sane = radii[a] >= 0.0f && std::isfinite(radii[a]);
-        const size_t row = (size_t)((char *)(gs->d_ctr + 1) - gs->in_arena.base), row_need = (row + 63) & ~(size_t)63;
-        if (sane && host_boxes_g && copy_kernels() && !ctx->debug_shrink_totals && (char *)gs->d_xyz == gs->in_arena.base && ctx->pinned && row <= ((size_t)1 << 20) &&
-            ctx->pinned_used + row_need <= ctx->pinned_cap) {
-            char *stage = ctx->pinned + ctx->pinned_used;
-            memcpy(stage + ((char *)gs->d_xyz - gs->in_arena.base), xyz, 24 * (size_t)n_items);
-            memcpy(stage + ((char *)gs->d_radii - gs->in_arena.base), radii, 4 * (size_t)n_items);
-            memcpy(stage + ((char *)gs->d_item_group - gs->in_arena.base), item_group.data(), 4 * (size_t)n_items);
-            AtomBox *boxes = reinterpret_cast<AtomBox *>(stage + ((char *)gs->d_boxes - gs->in_arena.base));
-            VolDesc *vols = reinterpret_cast<VolDesc *>(stage + ((char *)gs->d_vols - gs->in_arena.base));
-            Counters *ctr0 = reinterpret_cast<Counters *>(stage + ((char *)gs->d_ctr - gs->in_arena.base));
-            std::vector<int32_t> glo(3 * (size_t)n_groups, INT32_MAX), ghi(3 * (size_t)n_groups, INT32_MIN);
-            float cached_rad = NAN;
-            int32_t R[3] = {0, 0, 0};
-            for (int64_t a = 0; a < n_items; ++a) {
-                if (!(radii[a] == cached_rad)) {
-                    const double rad = (double)radii[a];
-                    const double o[3] = {m->geom.origin[0] + rad, m->geom.origin[1] + rad, m->geom.origin[2] + rad};
-                    xyz2crs(m->geom, o, R);
-                    cached_rad = radii[a];
-                }
-                int32_t C[3];
-                xyz2crs(m->geom, xyz + 3 * a, C);
-                AtomBox bx;
-                bool empty = false;
-                for (int k = 0; k < 3; ++k) {      // (int32 arithmetic as in k_atom_boxes)
-                    bx.lo[k] = C[k] - R[k] - 1;
-                    bx.hi[k] = C[k] + R[k];
-                    empty = empty || bx.hi[k] < bx.lo[k];
-                }
-                if (empty) { for (int k = 0; k < 3; ++k) { bx.lo[k] = 0; bx.hi[k] = -1; } }
-                boxes[a] = bx;
-                if (!empty) {
-                    const size_t g = (size_t)item_group[(size_t)a];
-                    for (int k = 0; k < 3; ++k) { glo[3 * g + k] = std::min(glo[3 * g + k], bx.lo[k]); ghi[3 * g + k] = std::max(ghi[3 * g + k], bx.hi[k]); }
-                }
-            }
-            int64_t words = 0, keys = 0;
-            bool fits = true;
-            for (int64_t g = 0; g < n_groups; ++g) {      // (k_make_vols)
-                VolDesc vd;
-                memset(&vd, 0, sizeof vd);
-                bool empty = false;
-                for (int k = 0; k < 3; ++k) empty = empty || ghi[3 * (size_t)g + k] < glo[3 * (size_t)g + k];
-                for (int k = 0; k < 3 && !empty; ++k) {
-                    const int64_t d = (int64_t)ghi[3 * (size_t)g + k] - glo[3 * (size_t)g + k] + 1;
-                    fits = fits && d < (1ll << 30);
-                    vd.org[k] = glo[3 * (size_t)g + k];
-                    vd.dim[k] = (int32_t)d;
-                }
-                vd.row_words = (vd.dim[0] + 63) / 64;
-                vd.group = (int32_t)g;
-                vd.word_base = words;
-                vd.key_base = keys;
-                vols[g] = vd;
-                words += (int64_t)vd.row_words * vd.dim[1] * vd.dim[2];
-                keys += (int64_t)vd.dim[0] * vd.dim[1] * vd.dim[2];
-                fits = fits && words < (1ll << 40) && keys < (1ll << 46);
-            }
-            if (fits) {
-                memset(ctr0, 0, sizeof *ctr0);
-                ctr0->total_words = words;
-                ctr0->total_keys = keys;
-                gs->pend_src = stage; gs->pend_dst = gs->in_arena.base; gs->pend_bytes = (row + 15) & ~(size_t)15;
-                ctx->pinned_used += row_need;
-                gs->total_words = words;
-                gs->total_keys = keys;
-                gs->host_totals = true;
-                if (gs->total_words >= (1ll << 31) * 2) return fail(ctx, PDBEDA_ERR_ARGUMENT, "sphere batch too large (%lld mask words)", (long long)gs->total_words);
-                return 0;
-            }
+        if (char *stage = sane && copy_kernels() ? host_row(item_group.data(), made, &small_boxes) : nullptr) {
+            leave_to_job(stage);
+            return group_sized(ctx, gs, made[0], made[1], true);
         }
     }
     if (xyz && n_items > 0 && n_groups == n_items) {
@@ -2284,9 +2307,8 @@ static int group_setup(pdbeda_map *m, const double *xyz, const float *radii, con
             const float rad = radii[a];
             if (!(rad >= 0.0f) || !std::isfinite(rad)) { per_atom = false; break; }
             if (!(rad == last_rad)) {   // (a handful of distinct radii: one per atom type)
-                const double o[3] = {m->geom.origin[0] + (double)rad, m->geom.origin[1] + (double)rad, m->geom.origin[2] + (double)rad};
                 int32_t R[3];
-                xyz2crs(m->geom, o, R);
+                sphere_half_widths(m->geom, (double)rad, R);
                 int64_t dim[3];
                 bool empty = false;
                 for (int k = 0; k < 3; ++k) { dim[k] = 2 * (int64_t)R[k] + 2; empty = empty || dim[k] <= 0; }
@@ -2302,81 +2324,23 @@ static int group_setup(pdbeda_map *m, const double *xyz, const float *radii, con
         // the same order) -- k_init_bounds, k_atom_boxes and k_make_vols were three launches in front of every per-atom batch (the clouds of
         // aggregateCloud, the region tables), and a launch costs several times its 5 us when other processes' uploads hold the link.
         // PDBEDA_HOST_BOXES=0: the device makes them (A/B, and what the test of the two paths' equality runs against).
-        static const bool host_boxes = [] { const char *e = getenv("PDBEDA_HOST_BOXES"); return !(e && e[0] == '0'); }();
-        const size_t row = (size_t)((char *)(gs->d_ctr + 1) - gs->in_arena.base), row_need = (row + 63) & ~(size_t)63;
-        if (per_atom && host_boxes && !ctx->debug_shrink_totals && (char *)gs->d_xyz == gs->in_arena.base && ctx->pinned && row <= ((size_t)1 << 20) &&
-            ctx->pinned_used + row_need <= ctx->pinned_cap) {
-            char *stage = ctx->pinned + ctx->pinned_used;
-            memcpy(stage + ((char *)gs->d_xyz - gs->in_arena.base), xyz, 24 * (size_t)n_items);
-            memcpy(stage + ((char *)gs->d_radii - gs->in_arena.base), radii, 4 * (size_t)n_items);
-            memcpy(stage + ((char *)gs->d_item_group - gs->in_arena.base), item_group.data(), 4 * (size_t)n_items);
-            AtomBox *boxes = reinterpret_cast<AtomBox *>(stage + ((char *)gs->d_boxes - gs->in_arena.base));
-            VolDesc *vols = reinterpret_cast<VolDesc *>(stage + ((char *)gs->d_vols - gs->in_arena.base));
-            Counters *ctr0 = reinterpret_cast<Counters *>(stage + ((char *)gs->d_ctr - gs->in_arena.base));
-            int64_t words = 0, keys = 0;
-            float cached_rad = NAN;
-            int32_t R[3] = {0, 0, 0};
-            bool small_boxes = true;
-            gs->host_boxes.resize((size_t)n_items);
-            for (int64_t a = 0; a < n_items; ++a) {
-                if (!(radii[a] == cached_rad)) {
-                    const double rad = (double)radii[a];
-                    const double o[3] = {m->geom.origin[0] + rad, m->geom.origin[1] + rad, m->geom.origin[2] + rad};
-                    xyz2crs(m->geom, o, R);
-                    cached_rad = radii[a];
-                }
-                int32_t C[3];
-                xyz2crs(m->geom, xyz + 3 * a, C);
-                AtomBox bx;
-                bool empty = false;
-                for (int k = 0; k < 3; ++k) {      // (int32 arithmetic as in k_atom_boxes)
-                    bx.lo[k] = C[k] - R[k] - 1;
-                    bx.hi[k] = C[k] + R[k];
-                    empty = empty || bx.hi[k] < bx.lo[k];
-                }
-                if (empty) { for (int k = 0; k < 3; ++k) { bx.lo[k] = 0; bx.hi[k] = -1; } }
-                boxes[a] = bx;
-                gs->host_boxes[(size_t)a] = bx;
-                VolDesc vd;
-                memset(&vd, 0, sizeof vd);
-                for (int k = 0; k < 3 && !empty; ++k) { vd.org[k] = bx.lo[k]; vd.dim[k] = bx.hi[k] - bx.lo[k] + 1; }
-                vd.row_words = (vd.dim[0] + 63) / 64;
-                vd.group = (int32_t)a;
-                vd.word_base = words;
-                vd.key_base = keys;
-                vols[a] = vd;
-                small_boxes = small_boxes && vd.row_words <= 1 && (int64_t)vd.dim[1] * vd.dim[2] <= ATOM_WORDS;
-                words += (int64_t)vd.row_words * vd.dim[1] * vd.dim[2];
-                keys += (int64_t)vd.dim[0] * vd.dim[1] * vd.dim[2];
-            }
-            if (!(words == totals[0] && keys == totals[1])) gs->host_boxes.clear();
-            if (words == totals[0] && keys == totals[1]) {      // (they are: both follow from the radii; a mismatch takes the device's path below)
-                memset(ctr0, 0, sizeof *ctr0);
-                ctr0->total_words = words;
-                ctr0->total_keys = keys;
-                if (copy_kernels()) { gs->pend_src = stage; gs->pend_dst = gs->in_arena.base; gs->pend_bytes = (row + 15) & ~(size_t)15; }   // (copied by the job's first launch; whole 16-byte units: the stage and the carve are padded)
-                else HIP_TRY(ctx, hipMemcpyAsync(gs->in_arena.base, stage, row, hipMemcpyHostToDevice, st));
-                ctx->pinned_used += row_need;
-                gs->total_words = words;
-                gs->total_keys = keys;
-                gs->host_totals = true;
-                static const bool atom_engine_on = [] { const char *e = getenv("PDBEDA_ATOM_ENGINE"); return !(e && e[0] == '0'); }();   // (A/B switch)
-                gs->atom_engine = small_boxes && atom_engine_on && n_items < (1ll << 31);
-                if (gs->total_words >= (1ll << 31) * 2) return fail(ctx, PDBEDA_ERR_ARGUMENT, "sphere batch too large (%lld mask words)", (long long)gs->total_words);
-                return 0;
-            }
+        char *stage = per_atom ? host_row(nullptr, made, &small_boxes) : nullptr;
+        if (stage && !(made[0] == totals[0] && made[1] == totals[1])) { pinned_untake(ctx, stage); stage = nullptr; }   // (they are equal: both follow from the radii; a mismatch takes the device's path below)
+        if (stage) {
+            const AtomBox *boxes = reinterpret_cast<const AtomBox *>(staged(stage, gs->d_boxes));
+            gs->host_boxes.assign(boxes, boxes + n_items);
+            if (copy_kernels()) leave_to_job(stage);
+            else HIP_TRY(ctx, stage_copy(ctx, stage, gs->in_arena.base, row, true));
+            static const bool atom_engine_on = env_unless_0("PDBEDA_ATOM_ENGINE");   // (A/B switch)
+            gs->atom_engine = small_boxes && atom_engine_on && n_items < (1ll << 31);
+            return group_sized(ctx, gs, made[0], made[1], true);
         }
         if (ctx->debug_shrink_totals) { totals[0] /= 2; totals[1] /= 2; }
         // (coordinates, radii and groups sit in a row at the head of the scratch arena: one staged block, one copy)
         const size_t block = (size_t)((char *)(gs->d_item_group + n_items) - gs->in_arena.base);
-        const size_t need = (block + 63) & ~(size_t)63;
-        if (per_atom && (char *)gs->d_xyz == gs->in_arena.base && ctx->pinned && ctx->pinned_used + need <= ctx->pinned_cap) {
-            char *stage = ctx->pinned + ctx->pinned_used;
-            memcpy(stage + ((char *)gs->d_xyz - gs->in_arena.base), xyz, 24 * (size_t)n_items);
-            memcpy(stage + ((char *)gs->d_radii - gs->in_arena.base), radii, 4 * (size_t)n_items);
-            memcpy(stage + ((char *)gs->d_item_group - gs->in_arena.base), item_group.data(), 4 * (size_t)n_items);
-            HIP_TRY(ctx, copy_kernels() ? copy_by_kernel(ctx, gs->in_arena.base, stage, block) : hipMemcpyAsync(gs->in_arena.base, stage, block, hipMemcpyHostToDevice, st));
-            ctx->pinned_used += need;
+        if (char *stage = per_atom && (char *)gs->d_xyz == gs->in_arena.base ? pinned_take(ctx, block) : nullptr) {
+            stage_inputs(stage);
+            HIP_TRY(ctx, stage_copy(ctx, stage, gs->in_arena.base, block, true));
             return group_bounds(m, gs, n_items, n_groups, true, totals);
         }
     }
@@ -2502,18 +2466,22 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
     if (rc) { arena_put(ctx, gs.in_arena); return rc; }
     std::vector<unsigned long long> h_cnt(n_groups);
     std::vector<unsigned int> h_inv(n_groups);
+    auto deliver_counts = [&] {      // (both paths end here, behind their wait)
+        for (int64_t g = 0; g < n_groups; ++g) {
+            if (n_region) n_region[g] = (int64_t)h_cnt[g];
+            if (valid) valid[g] = h_inv[g] ? 0 : 1;
+        }
+        return PDBEDA_OK;
+    };
     {   // a group per atom whose inputs the host staged (coordinates, radii, host-made volumes in the pinned block): ONE launch, no mask (k_atom_region)
-        static const bool atom_region_on = [] { const char *e = getenv("PDBEDA_ATOM_REGION"); return !(e && e[0] == '0'); }();      // (A/B switch)
-        const size_t out_bytes = 3 * align_up(8 * (size_t)n_groups, 64) + align_up(4 * (size_t)n_groups, 64);
-        if (atom_region_on && n_groups == n_atoms && gs.pend_bytes && !gs.host_boxes.empty() && copy_kernels() && ctx->pinned && ctx->pinned_used + out_bytes <= ctx->pinned_cap) {
-            char *blk = ctx->pinned + ctx->pinned_used;
-            size_t off = 0;
-            auto take = [&](void *dst, size_t bytes) { char *p = blk + off; if (dst && bytes) ctx->pending.push_back({dst, ctx->pinned_used + off, bytes}); off += align_up(std::max<size_t>(bytes, 1), 64); return p; };
-            double *o_pos = reinterpret_cast<double *>(take(pos, 8 * (size_t)n_groups));
-            double *o_neg = reinterpret_cast<double *>(take(neg, 8 * (size_t)n_groups));
-            unsigned long long *o_cnt = reinterpret_cast<unsigned long long *>(take(h_cnt.data(), 8 * (size_t)n_groups));
-            unsigned int *o_inv = reinterpret_cast<unsigned int *>(take(h_inv.data(), 4 * (size_t)n_groups));
-            ctx->pinned_used += off;
+        static const bool atom_region_on = env_unless_0("PDBEDA_ATOM_REGION");      // (A/B switch)
+        const size_t out_bytes = 3 * pinned_span(8 * (size_t)n_groups) + pinned_span(4 * (size_t)n_groups);
+        if (atom_region_on && n_groups == n_atoms && gs.pend_bytes && !gs.host_boxes.empty() && copy_kernels() && out_bytes <= pinned_room(ctx)) {
+            // (n_groups > 0: no take is empty.  As before a failed launch below keeps the takes until the next wait and, through fail(), delivers nothing)
+            double *o_pos = reinterpret_cast<double *>(pinned_take(ctx, 8 * (size_t)n_groups, pos));
+            double *o_neg = reinterpret_cast<double *>(pinned_take(ctx, 8 * (size_t)n_groups, neg));
+            unsigned long long *o_cnt = reinterpret_cast<unsigned long long *>(pinned_take(ctx, 8 * (size_t)n_groups, h_cnt.data()));
+            unsigned int *o_inv = reinterpret_cast<unsigned int *>(pinned_take(ctx, 4 * (size_t)n_groups, h_inv.data()));
             // (the staged row mirrors the scratch arena: the same offsets)
             const char *stage = gs.pend_src;
             const double *s_xyz = reinterpret_cast<const double *>(stage + ((char *)gs.d_xyz - gs.in_arena.base));
@@ -2526,11 +2494,7 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
             if (e1 == hipSuccess) e1 = ctx_sync(ctx);
             arena_put(ctx, gs.in_arena);
             if (e1 != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: %s", hipGetErrorString(e1));
-            for (int64_t g = 0; g < n_groups; ++g) {
-                if (n_region) n_region[g] = (int64_t)h_cnt[g];
-                if (valid) valid[g] = h_inv[g] ? 0 : 1;
-            }
-            return PDBEDA_OK;
+            return deliver_counts();
         }
     }
     const int64_t tw = std::max<int64_t>(gs.total_words, 1);
@@ -2572,11 +2536,7 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
     arena_put(ctx, gs.in_arena);
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: %s", hipGetErrorString(e));
     if (setup.overflow != 0u) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: the device's volumes outgrew what the host sized the batch for");
-    for (int64_t g = 0; g < n_groups; ++g) {
-        if (n_region) n_region[g] = (int64_t)h_cnt[g];
-        if (valid) valid[g] = h_inv[g] ? 0 : 1;
-    }
-    return PDBEDA_OK;
+    return deliver_counts();
 }
 
 // ------------------------------------------------------------------------------------
@@ -2705,7 +2665,7 @@ extern "C" int pdbeda_nearest_atom(pdbeda_ctx *ctx, const double *centroids, int
 // room there costs a wait of its own).
 static size_t pinned_room_beside(const pdbeda_ctx *ctx, size_t results) {
     const size_t reserve = results + (size_t)(4 << 10);
-    return ctx->pinned_cap > ctx->pinned_used + reserve ? ctx->pinned_cap - ctx->pinned_used - reserve : 0;
+    return pinned_room(ctx) > reserve ? pinned_room(ctx) - reserve : 0;
 }
 
 static bool all_finite(const double *v, int64_t n) {
@@ -3052,7 +3012,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     if (n == 0) return PDBEDA_OK;
     hipStream_t st = ctx->stream;
     // PDBEDA_CLOUD_TRACE=1 (experiments): the sizes of the two jobs and the host-side phases of this call on stderr
-    static const bool cloud_trace = [] { const char *e = getenv("PDBEDA_CLOUD_TRACE"); return e && e[0] && e[0] != '0'; }();
+    static const bool cloud_trace = env_set("PDBEDA_CLOUD_TRACE");
     const double t_call = now_s();
     double t_wait1 = 0.0, t_pooled = 0.0, t_marks[6] = {0, 0, 0, 0, 0, 0};
 
@@ -3192,50 +3152,35 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         const bool have_boxes = (int64_t)cow->host_boxes.size() == n;      // (the sphere job's own boxes, made by the host with the same statements: two xyz2crs per pooled cloud were 0.06 ms here)
         int64_t last_a = -1;
         bool cur_empty = false;
-        int64_t blo[3] = {0, 0, 0}, bhi[3] = {0, 0, 0};
+        AtomBox bx = {{0, 0, 0}, {-1, -1, -1}};
         for (int64_t p = 0; p < n_pool; ++p) {
             const int64_t a = at->alias[pool_atom[(size_t)p]];          // (the clouds are those of the coordinate's last atom: its coordinate, its radius)
             if (a != last_a) {
                 if (have_boxes) {
-                    const AtomBox &bx = cow->host_boxes[(size_t)a];
-                    for (int k = 0; k < 3; ++k) { blo[k] = bx.lo[k]; bhi[k] = bx.hi[k]; }
-                    cur_empty = bx.hi[0] < bx.lo[0];      // (an empty box holds no voxel: it has no cloud, it is not pooled -- unreachable)
+                    bx = cow->host_boxes[(size_t)a];
                 } else {
-                    cur_empty = false;
-                    const double rad = (double)at->radius[a];
-                    const double o[3] = {m->geom.origin[0] + rad, m->geom.origin[1] + rad, m->geom.origin[2] + rad};
                     int32_t C[3], R[3];
                     xyz2crs(m->geom, at->xyz + 3 * a, C);
-                    xyz2crs(m->geom, o, R);
-                    for (int k = 0; k < 3; ++k) { blo[k] = (int64_t)C[k] - R[k] - 1; bhi[k] = (int64_t)C[k] + R[k]; }
+                    sphere_half_widths(m->geom, (double)at->radius[a], R);
+                    (void)atom_box(C, R, &bx);
                 }
+                cur_empty = bx.hi[0] < bx.lo[0];      // (an empty box holds no voxel: it has no cloud, it is not pooled -- unreachable)
                 last_a = a;
             }
             if (cur_empty) continue;
             for (int g : {(int)pool_group[(size_t)p], n_rg})
                 for (int k = 0; k < 3; ++k) {
-                    lo[3 * (size_t)g + k] = std::min<int64_t>(lo[3 * (size_t)g + k], blo[k]);
-                    hi[3 * (size_t)g + k] = std::max<int64_t>(hi[3 * (size_t)g + k], bhi[k]);
+                    lo[3 * (size_t)g + k] = std::min<int64_t>(lo[3 * (size_t)g + k], bx.lo[k]);
+                    hi[3 * (size_t)g + k] = std::max<int64_t>(hi[3 * (size_t)g + k], bx.hi[k]);
                 }
         }
         for (int g = 0; g < n_groups; ++g) {
-            VolDesc &vd = union_vols[(size_t)g];
-            memset(&vd, 0, sizeof vd);
-            vd.group = g;
-            vd.word_base = union_totals[0];
-            vd.key_base = union_totals[1];
-            if (hi[3 * (size_t)g] < lo[3 * (size_t)g]) continue;
-            bool fits = true;
-            for (int k = 0; k < 3; ++k) {
-                const int64_t d = hi[3 * (size_t)g + k] - lo[3 * (size_t)g + k] + 1;
-                fits = fits && d < (1ll << 30) && lo[3 * (size_t)g + k] > INT32_MIN && hi[3 * (size_t)g + k] < INT32_MAX;
-                vd.org[k] = (int32_t)lo[3 * (size_t)g + k];
-                vd.dim[k] = (int32_t)d;
-            }
+            int64_t words = 0, keys = 0;
+            bool fits = vol_from_bounds(&lo[3 * (size_t)g], &hi[3 * (size_t)g], g, union_totals[0], union_totals[1], &union_vols[(size_t)g], &words, &keys);
+            for (int k = 0; k < 3; ++k) fits = fits && lo[3 * (size_t)g + k] > INT32_MIN && hi[3 * (size_t)g + k] < INT32_MAX;      // (an empty group's sentinels pass)
             if (!fits) { union_totals[0] = INT64_MAX / 2; break; }
-            vd.row_words = (vd.dim[0] + 63) / 64;
-            union_totals[0] += (int64_t)vd.row_words * vd.dim[1] * vd.dim[2];
-            union_totals[1] += (int64_t)vd.dim[0] * vd.dim[1] * vd.dim[2];
+            union_totals[0] += words;
+            union_totals[1] += keys;
         }
     }
     t_marks[4] = now_s();
@@ -3253,11 +3198,9 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         if (host_sized) put(d_union_vols, union_vols.data(), sizeof(VolDesc) * (size_t)n_groups);
     }
     {
-        const size_t span16 = (upload_bytes + 15) & ~(size_t)15, need = (span16 + 63) & ~(size_t)63;      // (upload_bytes is a carve boundary: a multiple of 256)
-        if (copy_kernels() && ctx->pinned && span16 <= ((size_t)1 << 20) && ctx->pinned_used + need <= ctx->pinned_cap) {
-            char *stage = ctx->pinned + ctx->pinned_used;      // staged now, copied by the union job's first launch (k_job_init)
+        const size_t span16 = (upload_bytes + 15) & ~(size_t)15;      // (upload_bytes is a carve boundary: a multiple of 256)
+        if (char *stage = copy_kernels() && span16 <= ((size_t)1 << 20) ? pinned_take(ctx, span16) : nullptr) {      // staged now, copied by the union job's first launch (k_job_init)
             memcpy(stage, block.data(), upload_bytes);
-            ctx->pinned_used += need;
             gs.pend_src = stage; gs.pend_dst = aux.base; gs.pend_bytes = span16;
             e = hipSuccess;
         } else {
@@ -3283,10 +3226,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     }
     if (host_sized) {
         gs.d_vols = d_union_vols;          // (in the aux block, which outlives the job's enqueue)
-        gs.total_words = union_totals[0];
-        gs.total_keys = union_totals[1];
-        gs.host_totals = true;
-        rc = 0;
+        rc = group_sized(ctx, &gs, union_totals[0], union_totals[1], true);
     } else {
         rc = group_bounds(m, &gs, 2 * V, n_groups, false);      // (synchronises)
     }
@@ -3303,31 +3243,28 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     std::vector<int64_t> u_n;
     std::vector<double> u_tot, u_cen;
     std::vector<int32_t> u_grp;
-    const size_t fin_bytes = align_up(sizeof(Counters), 64) + align_up(8 * (size_t)u_cap, 64) * 2 + align_up(24 * (size_t)u_cap, 64) + align_up(4 * (size_t)u_cap, 64) +
-                             align_up(4 * (size_t)std::max<int64_t>(n_pairs, 1), 64) + align_up(8 * (size_t)n_pool, 64);
-    static const bool unordered_on = [] { const char *e = getenv("PDBEDA_UNORDERED_UNION"); return !(e && e[0] == '0'); }();      // (A/B switch)
-    const bool unordered = unordered_on && fused_paint && copy_kernels() && ctx->pinned && ctx->pinned_used + fin_bytes <= ctx->pinned_cap;
+    const size_t fin_bytes = pinned_span(sizeof(Counters)) + pinned_span(8 * (size_t)u_cap) * 2 + pinned_span(24 * (size_t)u_cap) + pinned_span(4 * (size_t)u_cap) +
+                             pinned_span(4 * (size_t)np1) + pinned_span(8 * (size_t)n_pool);
+    static const bool unordered_on = env_unless_0("PDBEDA_UNORDERED_UNION");      // (A/B switch)
+    const bool unordered = unordered_on && fused_paint && copy_kernels() && fin_bytes <= pinned_room(ctx);
     rc = grouped_job(m, gs, 2 * V, n_groups, false, 0.0f, &uni, fused_paint ? &paint : nullptr, unordered);
     if (rc) { arena_put(ctx, aux); return bail(rc, clouds, nullptr); }
     if (unordered) {
         u_n.resize((size_t)u_cap); u_tot.resize((size_t)u_cap); u_cen.resize(3 * (size_t)u_cap); u_grp.resize((size_t)u_cap);
         Counters u_ctr;
         memset(&u_ctr, 0, sizeof u_ctr);
-        char *blk = ctx->pinned + ctx->pinned_used;
-        size_t off = 0;
-        auto take = [&](void *dst, size_t bytes) { char *p = blk + off; if (bytes) ctx->pending.push_back({dst, ctx->pinned_used + off, bytes}); off += align_up(std::max<size_t>(bytes, 1), 64); return p; };
         UnionFinish fin;
         memset(&fin, 0, sizeof fin);
         fin.src_crs = cow->crs_dev; fin.src_off = cow->offsets_dev; fin.pool_cloud = d_pool_cloud; fin.pool_group = d_pool_group;
         fin.n_pool = (int)n_pool; fin.domain_group = n_rg; fin.touch = d_touch; fin.n_pairs = (int)n_pairs; fin.cap = (unsigned int)u_cap;
-        fin.out_ctr = reinterpret_cast<Counters *>(take(&u_ctr, sizeof u_ctr));
-        fin.out_n = reinterpret_cast<long long *>(take(u_n.data(), 8 * (size_t)u_cap));
-        fin.out_total = reinterpret_cast<double *>(take(u_tot.data(), 8 * (size_t)u_cap));
-        fin.out_centroid = reinterpret_cast<double *>(take(u_cen.data(), 24 * (size_t)u_cap));
-        fin.out_group = reinterpret_cast<int32_t *>(take(u_grp.data(), 4 * (size_t)u_cap));
-        fin.out_touch = reinterpret_cast<unsigned int *>(take(touch.data(), 4 * (size_t)n_pairs));
-        fin.out_comp = reinterpret_cast<int32_t *>(take(comp.data(), 8 * (size_t)n_pool));
-        ctx->pinned_used += off;
+        // (the takes fin_bytes made room for; as before a failed launch below keeps them until the next wait and, through fail(), delivers nothing)
+        fin.out_ctr = reinterpret_cast<Counters *>(pinned_take(ctx, sizeof u_ctr, &u_ctr));
+        fin.out_n = reinterpret_cast<long long *>(pinned_take(ctx, 8 * (size_t)u_cap, u_n.data()));
+        fin.out_total = reinterpret_cast<double *>(pinned_take(ctx, 8 * (size_t)u_cap, u_tot.data()));
+        fin.out_centroid = reinterpret_cast<double *>(pinned_take(ctx, 24 * (size_t)u_cap, u_cen.data()));
+        fin.out_group = reinterpret_cast<int32_t *>(pinned_take(ctx, 4 * (size_t)u_cap, u_grp.data()));
+        fin.out_touch = reinterpret_cast<unsigned int *>(pinned_take(ctx, 4 * (size_t)np1, n_pairs ? touch.data() : nullptr));      // (no pair: a line of its own all the same, nothing delivered)
+        fin.out_comp = reinterpret_cast<int32_t *>(pinned_take(ctx, 8 * (size_t)n_pool, comp.data()));
         const int64_t fin_threads = std::max<int64_t>(std::max<int64_t>(uni->job.run_cap, 2 * n_pool), n_pairs);
         { PROF(ctx, "k_union_finish"); hipLaunchKernelGGL(k_union_finish, dim3(grid_for(fin_threads, 256, 1024)), dim3(256), 0, st, uni->job, m->geom_dev, fin); }
         e = hipGetLastError();

@@ -1256,19 +1256,15 @@ struct AtomBox {
     int32_t hi[3];  // inclusive; hi < lo => empty
 };
 
-// Thread per atom: centre C = xyz2crs(xyz), R = xyz2crs(origin + r); box [C-R-1, C+R] (Q4).
-__global__ void k_atom_boxes(const Geom *__restrict__ gp, const double *__restrict__ xyz, const float *__restrict__ radii,
-                             const int32_t *__restrict__ atom_group, int64_t n_atoms, AtomBox *__restrict__ boxes,
-                             int32_t *__restrict__ g_lo, int32_t *__restrict__ g_hi) {
-    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= n_atoms) return;
-    const Geom &g = *gp;
-    const double p[3] = {xyz[3 * a], xyz[3 * a + 1], xyz[3 * a + 2]};
-    const double rad = (double)radii[a];
-    int32_t C[3], R[3];
-    xyz2crs(g, p, C);
+// The sphere box and volume rule, stated ONCE for host and device (like xyz2crs: the same IEEE / int32 operations in the same order on both sides, so
+// the host may size and lay out a batch without asking the device -- group_setup, pdbeda_aggregate_cloud -- and k_make_vols' check of its totals holds).
+// R = xyz2crs(origin + radius): the box's half-widths follow from the radius alone.
+__host__ __device__ inline void sphere_half_widths(const Geom &g, double rad, int32_t R[3]) {
     const double o[3] = {g.origin[0] + rad, g.origin[1] + rad, g.origin[2] + rad};
     xyz2crs(g, o, R);
+}
+// An atom's box is [C - R - 1, C + R] in int32, C = xyz2crs(centre) (Q4); a box empty along any axis becomes lo 0 / hi -1 along all.  false: empty.
+__host__ __device__ inline bool atom_box(const int32_t C[3], const int32_t R[3], AtomBox *out) {
     AtomBox bx;
     bool empty = false;
     for (int k = 0; k < 3; ++k) {
@@ -1277,6 +1273,46 @@ __global__ void k_atom_boxes(const Geom *__restrict__ gp, const double *__restri
         empty = empty || (bx.hi[k] < bx.lo[k]);
     }
     if (empty) { for (int k = 0; k < 3; ++k) { bx.lo[k] = 0; bx.hi[k] = -1; } }
+    *out = bx;
+    return !empty;
+}
+// A group's inclusive bounds (int32, or the int64 of aggregateCloud's unions; hi < lo along any axis: no voxel) -> its volume descriptor at the running
+// word / key bases, and the mask words and keys it adds to them.  An empty group is an all-zero volume.  A width is taken in int64 and stored as int32,
+// which IS k_make_vols' int32 `hi - lo + 1` for every input; false: a width of 2^30 voxels or more (the host's builders then leave the batch to the device).
+template <typename B>
+__host__ __device__ inline bool vol_from_bounds(const B *lo, const B *hi, int32_t group, int64_t word_base, int64_t key_base, VolDesc *out, int64_t *words, int64_t *keys) {
+    VolDesc vd;
+    bool empty = false, fits = true;
+    for (int k = 0; k < 3; ++k) empty = empty || hi[k] < lo[k];
+    for (int k = 0; k < 3; ++k) {
+        const int64_t d = empty ? 0 : (int64_t)hi[k] - (int64_t)lo[k] + 1;
+        fits = fits && d < (1ll << 30);
+        vd.org[k] = empty ? 0 : (int32_t)lo[k];
+        vd.dim[k] = (int32_t)d;
+    }
+    vd.row_words = (vd.dim[0] + 63) / 64;
+    vd.group = group;
+    vd.word_base = word_base;
+    vd.key_base = key_base;
+    *out = vd;
+    *words = (int64_t)vd.row_words * vd.dim[1] * vd.dim[2];
+    *keys = (int64_t)vd.dim[0] * vd.dim[1] * vd.dim[2];
+    return fits;
+}
+
+// Thread per atom: centre C = xyz2crs(xyz), R = xyz2crs(origin + r); box [C-R-1, C+R] (Q4).
+__global__ void k_atom_boxes(const Geom *__restrict__ gp, const double *__restrict__ xyz, const float *__restrict__ radii,
+                             const int32_t *__restrict__ atom_group, int64_t n_atoms, AtomBox *__restrict__ boxes,
+                             int32_t *__restrict__ g_lo, int32_t *__restrict__ g_hi) {
+    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_atoms) return;
+    const Geom &g = *gp;
+    const double p[3] = {xyz[3 * a], xyz[3 * a + 1], xyz[3 * a + 2]};
+    int32_t C[3], R[3];
+    xyz2crs(g, p, C);
+    sphere_half_widths(g, (double)radii[a], R);
+    AtomBox bx;
+    const bool empty = !atom_box(C, R, &bx);
     boxes[a] = bx;
     if (!empty) {
         const int gidx = atom_group[a];
@@ -1365,7 +1401,7 @@ __global__ void k_init_bounds(int32_t *g_lo, int32_t *g_hi, int64_t n3, Counters
 
 // Single block: group bounding boxes -> volume descriptors with word / key offsets.
 // cap_words / cap_keys: what the HOST sized the job for when it did not wait for these totals (group_setup: per-atom spheres, whose
-// box sizes follow from the radius alone).  The two agree by construction (the same IEEE arithmetic on both sides); should they
+// box sizes follow from the radius alone).  The two agree by construction (sphere_half_widths / atom_box / vol_from_bounds above are the one statement both sides run); should they
 // ever not, every volume is emptied before anything is painted and the flag makes the call fail -- nothing is written out of bounds.
 __global__ void __launch_bounds__(1024) k_make_vols(const int32_t *__restrict__ g_lo, const int32_t *__restrict__ g_hi,
                                                      int n_groups, VolDesc *__restrict__ vols, Counters *__restrict__ ctr,
@@ -1378,21 +1414,8 @@ __global__ void __launch_bounds__(1024) k_make_vols(const int32_t *__restrict__ 
     for (int base = 0; base < n_groups; base += 1024) {
         const int i = base + tid;
         VolDesc vd;
-        long long words = 0, keys = 0;
-        if (i < n_groups) {
-            bool empty = false;
-            for (int k = 0; k < 3; ++k) {
-                int lo = g_lo[3 * i + k], hi = g_hi[3 * i + k];
-                empty = empty || hi < lo;
-                vd.org[k] = lo;
-                vd.dim[k] = hi - lo + 1;
-            }
-            if (empty) { for (int k = 0; k < 3; ++k) { vd.org[k] = 0; vd.dim[k] = 0; } }
-            vd.row_words = (vd.dim[0] + 63) / 64;
-            vd.group = i;
-            words = (long long)vd.row_words * vd.dim[1] * vd.dim[2];
-            keys = (long long)vd.dim[0] * vd.dim[1] * vd.dim[2];
-        }
+        int64_t words = 0, keys = 0;
+        if (i < n_groups) (void)vol_from_bounds(g_lo + 3 * i, g_hi + 3 * i, i, 0, 0, &vd, &words, &keys);      // (the bases: below, from the scan)
         long long xw = words, xk = keys;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
