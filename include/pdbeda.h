@@ -254,6 +254,32 @@ int pdbeda_region_sums(pdbeda_map *map, const double *xyz, const float *radii, i
                        const int64_t *group_offsets, int64_t n_groups, float cutoff,
                        double *pos, double *neg, int64_t *n_region, uint8_t *valid);
 
+/* ---- radial profiles -------------------------------------------------------------- */
+/* The density around an atom by distance (no reference counterpart: the reference answers "what is inside ONE radius" --
+ * getSphereCrsFromXyz, cutils.pyx:220-248 -- and the curve its radii were read from takes one call per candidate radius).
+ * Per atom, ONE pass over the sphere box of `radius` -- [C - R - 1, C + R] per axis, C = xyz2crsCoord(atom),
+ * R = xyz2crsCoord(origin + radius): the box of pdbeda_region_sums, which under-covers the sphere on skewed cells (Q4) and is
+ * not widened here.  A voxel of the box is INSIDE when d <= (double)radius (float32 radius), d = sqrt((dx*dx + dy*dy) + dz*dz)
+ * in unfused fp64 from crs2xyzCoord (ccp4.py:304-316) -- the sphere test of pdbeda_region_sums.  Its shell is
+ *     k = min((int)floor(d / w), n_shells - 1),   w = (double)radius / (double)n_shells      (IEEE fp64 divisions)
+ * so d == 0 lies in shell 0 and d == radius in the last shell.  Its density is utils.getPointDensityFromCrs (periodic wrap, 0
+ * where nothing is stored).  Per atom and shell, [n_atoms][n_shells] row major:
+ *   n        voxels of the shell, no density filter;
+ *   sum      their density;
+ *   n_sig, sum_sig   the same over the voxels that pass the strict filter of getSphereCrsFromXyz (cutils.pyx:245): density >
+ *            cutoff for cutoff > 0, density < cutoff for cutoff < 0 (float32 cutoff); cutoff == 0: every voxel passes, so
+ *            n_sig == n and sum_sig == sum;
+ * and per atom: valid = utils.testValidXyzList of the sphere (0 when a voxel of it is not stored), as in pdbeda_region_sums.
+ * A voxel's density enters a sum rounded once to the map's fixed-point quantum (<= 2^-38 max |rho| on maps of up to 2^22
+ * voxels; the quantum of the blob sums, doubled per doubling of the largest box of the call beyond 2^22 voxels) and the sums are
+ * folded as integers: bit-identical from run to run, within quantum / 2 per voxel of the exact sum; an empty shell is exactly 0.  Atoms do not see
+ * each other: bonded atoms share voxels once radius exceeds half a bond length -- a profile is per atom, not a partition.
+ * n_atoms == 0 succeeds and touches nothing.  PDBEDA_ERR_ARGUMENT before any launch: n_shells outside [1, PDBEDA_MAX_SHELLS],
+ * a radius that is not finite or <= 0, a NaN cutoff, a non-finite coordinate, a box of 2^31 voxels or more.  Synchronous. */
+#define PDBEDA_MAX_SHELLS 64
+int pdbeda_radial_profiles(pdbeda_map *map, const double *xyz, int64_t n_atoms, float radius, int32_t n_shells, float cutoff,
+                           int64_t *n, double *sum, int64_t *n_sig, double *sum_sig, uint8_t *valid); /* any output may be NULL */
+
 /* ---- aggregateCloud ------------------------------------------------------------------ */
 /* DensityAnalysis.aggregateCloud up to its statistics tail (densityAnalysis.py:571-731) as ONE call: the clouds of every
  * eligible atom (findAberrantBlobs, 603), the centroid-distance cut-off over all atoms (607), the best cloud and the pooled

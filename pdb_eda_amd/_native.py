@@ -115,6 +115,7 @@ _SIGS = {
     "pdbeda_peaklist_counters": (C.c_int, [_p, _p]),
     "pdbeda_peaklist_free": (C.c_int, [_p]),
     "pdbeda_region_sums": (C.c_int, [_p, _p, _p, _i64, _p, _i64, C.c_float, _p, _p, _p, _p]),
+    "pdbeda_radial_profiles": (C.c_int, [_p, _p, _i64, C.c_float, C.c_int32, C.c_float, _p, _p, _p, _p, _p]),
     "pdbeda_aggregate_cloud": (C.c_int, [_p, C.POINTER(CloudAtoms), C.c_float, C.c_double, C.POINTER(_p)]),
     "pdbeda_cloud_counts": (C.c_int, [_p, _p, _p]),
     "pdbeda_cloud_atom_rows": (C.c_int, [_p, _p, _p, _p, _p, _p]),
@@ -652,6 +653,18 @@ class DeviceMap(object):
         self._ctx.check(self._ctx._lib.pdbeda_region_sums(self._h, _ptr(xyz), _ptr(radii), len(xyz), _ptr(off), ng, C.c_float(cutoff),
                                                           _ptr(pos), _ptr(neg), _ptr(cnt), _ptr(valid)), "pdbeda_region_sums")
         return pos, neg, cnt, valid.astype(bool)
+
+    def radial_profiles(self, xyz, radius, n_shells, cutoff):
+        """pdbeda_radial_profiles: per atom, the voxels and the density of ``n_shells`` concentric shells out to ``radius``.
+        A dict of (n_atoms, n_shells) arrays ``n``, ``sum``, ``nSig``, ``sumSig`` and the (n_atoms,) flags ``valid``."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        shape = (len(xyz), max(int(n_shells), 0))
+        n, n_sig = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+        total, total_sig = np.zeros(shape), np.zeros(shape)
+        valid = np.zeros(len(xyz), dtype=np.uint8)
+        self._ctx.check(self._ctx._lib.pdbeda_radial_profiles(self._h, _ptr(xyz), len(xyz), C.c_float(radius), int(n_shells), C.c_float(cutoff),
+                                                              _ptr(n), _ptr(total), _ptr(n_sig), _ptr(total_sig), _ptr(valid)), "pdbeda_radial_profiles")
+        return {"n": n, "sum": total, "nSig": n_sig, "sumSig": total_sig, "valid": valid.astype(bool)}
 
     def aggregate_cloud(self, xyz, radius, weight, residue, alias, key, bonded_off, bonded, owner_key, cutoff, min_cloud_electrons):
         """pdbeda_aggregate_cloud: everything of aggregateCloud that touches voxels, in one call.  Returns a dict of arrays:

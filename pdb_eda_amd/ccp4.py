@@ -401,6 +401,16 @@ class DensityMatrix(object):
         bl = self._map.sphere_blobs(xyz, radii, np.array([0, len(xyz)], dtype=np.int64), densityCutoff)
         return DensityBlob.listFromDevice(bl, self)
 
+    # -- radial profiles (no reference counterpart) ----------------------------------
+    def radialProfiles(self, xyzCoordList, maxRadius, nShells=20, densityCutoff=0):
+        """The density around every coordinate by distance, in ONE device call (``pdbeda_radial_profiles`` in include/pdbeda.h
+        has the contract): the sphere of ``maxRadius`` around a coordinate -- the voxels of ``getSphereCrsFromXyz`` -- is cut into
+        ``nShells`` concentric shells of equal width.  A dict of (n, nShells) arrays ``n`` / ``sum`` (voxels and density of a shell,
+        no filter), ``nSig`` / ``sumSig`` (the voxels that pass ``densityCutoff``, strict, as ``getSphereCrsFromXyz``) and the (n,)
+        flags ``valid``.  Coordinates do not see each other: spheres that overlap count the shared voxels once each."""
+        xyz = np.asarray(xyzCoordList, dtype=np.float64).reshape(-1, 3)
+        return self._map.radial_profiles(xyz, maxRadius, nShells, densityCutoff)
+
     # -- whole-map blobs ------------------------------------------------------------
     def createFullBlobList(self, cutoff):
         """ref ccp4.py:463-473: threshold the non-repeating box and cluster (None for cutoff == 0)."""

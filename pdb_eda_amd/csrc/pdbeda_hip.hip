@@ -29,6 +29,7 @@
 #include "pdbeda_upload.h"
 #include "pdbeda_contacts.h"
 #include "pdbeda_peaks.h"
+#include "pdbeda_profiles.h"
 
 using namespace pdbeda;
 
@@ -2537,6 +2538,115 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: %s", hipGetErrorString(e));
     if (setup.overflow != 0u) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: the device's volumes outgrew what the host sized the batch for");
     return deliver_counts();
+}
+
+// ------------------------------------------------------------------------------------
+// Radial profiles (no reference counterpart; the contract: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// One launch per chunk of atoms, and a chunk is every atom whenever the pinned block holds the batch (48 bytes of inputs and 32 n_shells + 1 of
+// results an atom: 2 000 atoms x 20 shells are 1.4 MB of its 4 MiB).  The host makes the boxes -- the library's one sphere-box rule, as for the
+// per-atom region sums -- and refuses what the contract refuses before anything is launched; the kernel reads coordinates and boxes where the host
+// staged them and writes the rows straight into the block (pinned_take: delivered by the wait).  Without copy kernels, or without a block, the same
+// launch runs on device scratch and the runtime copies.
+extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t n_atoms, float radius, int32_t n_shells, float cutoff,
+                                      int64_t *n, double *sum, int64_t *n_sig, double *sum_sig, uint8_t *valid) {
+    if (!m || n_atoms < 0 || (n_atoms > 0 && !xyz)) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = m->ctx;
+    if (n_shells < 1 || n_shells > PDBEDA_MAX_SHELLS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: n_shells %d outside [1, %d]", (int)n_shells, PDBEDA_MAX_SHELLS);
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: the radius must be finite and > 0");
+    if (std::isnan(cutoff)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: the cutoff is NaN");
+    if (n_atoms == 0) return PDBEDA_OK;
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    if (n_atoms >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: batch too large");
+    std::vector<AtomBox> boxes((size_t)n_atoms);
+    int64_t largest = 0;
+    {
+        int32_t R[3];
+        sphere_half_widths(m->geom, (double)radius, R);
+        for (int64_t a = 0; a < n_atoms; ++a) {
+            const double *p = xyz + 3 * a;
+            if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: atom %lld has a non-finite coordinate", (long long)a);
+            int32_t C[3];
+            xyz2crs(m->geom, p, C);
+            int64_t vox = atom_box(C, R, &boxes[(size_t)a]) ? 1 : 0;
+            for (int k = 0; k < 3 && vox; ++k) {
+                vox *= (int64_t)boxes[(size_t)a].hi[k] - (int64_t)boxes[(size_t)a].lo[k] + 1;      // (each width < 2^32: checked after every factor)
+                if (vox >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: the sphere box of atom %lld has 2^31 voxels or more", (long long)a);
+            }
+            largest = std::max(largest, vox);
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc_fix = map_fix_mul(m);      // (a wait when the map's range is not known yet: before anything is staged)
+    if (rc_fix) return rc_fix;
+    // |fix_of(rho)| < 2^39 (map_fix_mul keeps 2^22 max |rho| inside 61 bits), so the integer sum of a shell of up to 2^22 voxels cannot leave 64
+    // bits; a larger box takes a quantum coarser by the factor it is larger by.
+    double fix_mul = m->fix_mul;
+    for (int64_t room = 1ll << 22; room < largest; room <<= 1) fix_mul *= 0.5;
+    const double fix_inv = 1.0 / fix_mul;      // (powers of two: exact)
+    const size_t cells = (size_t)n_shells, per_atom = 48 + 32 * cells + 1, slack = 7 * 64;
+    const bool direct = copy_kernels() && ctx->pinned && pinned_room(ctx) >= per_atom + slack;
+    const int64_t chunk = std::max<int64_t>(1, direct ? (int64_t)((pinned_room(ctx) - slack) / per_atom) : (int64_t)(((size_t)8 << 20) / per_atom));
+    Arena scratch;
+    for (int64_t a0 = 0; a0 < n_atoms; a0 += chunk) {
+        const size_t na = (size_t)std::min<int64_t>(chunk, n_atoms - a0), rows = na * cells;
+        const double *k_xyz;
+        const AtomBox *k_box;
+        long long *k_n, *k_nsig;
+        double *k_sum, *k_sumsig;
+        uint8_t *k_valid;
+        char *first = nullptr;
+        hipError_t e = hipSuccess;
+        if (direct) {      // (the chunk was sized to fit: no take fails)
+            first = pinned_take(ctx, 24 * na);
+            memcpy(first, xyz + 3 * a0, 24 * na);
+            char *b = pinned_take(ctx, sizeof(AtomBox) * na);
+            memcpy(b, &boxes[(size_t)a0], sizeof(AtomBox) * na);
+            k_xyz = reinterpret_cast<const double *>(first);
+            k_box = reinterpret_cast<const AtomBox *>(b);
+            k_n = reinterpret_cast<long long *>(pinned_take(ctx, 8 * rows, n ? n + (size_t)a0 * cells : nullptr));
+            k_sum = reinterpret_cast<double *>(pinned_take(ctx, 8 * rows, sum ? sum + (size_t)a0 * cells : nullptr));
+            k_nsig = reinterpret_cast<long long *>(pinned_take(ctx, 8 * rows, n_sig ? n_sig + (size_t)a0 * cells : nullptr));
+            k_sumsig = reinterpret_cast<double *>(pinned_take(ctx, 8 * rows, sum_sig ? sum_sig + (size_t)a0 * cells : nullptr));
+            k_valid = reinterpret_cast<uint8_t *>(pinned_take(ctx, na, valid ? valid + a0 : nullptr));
+        } else {
+            if (!scratch.base) {
+                const size_t nc = (size_t)std::min<int64_t>(chunk, n_atoms);
+                const int rc = arena_get(ctx, align_up(24 * nc) + align_up(sizeof(AtomBox) * nc) + 4 * align_up(8 * nc * cells) + align_up(nc), &scratch);
+                if (rc) return rc;
+            }
+            Carver cv(scratch.base);
+            double *d_xyz = cv.take<double>(3 * na);
+            AtomBox *d_box = cv.take<AtomBox>(na);
+            k_n = cv.take<long long>(rows); k_sum = cv.take<double>(rows); k_nsig = cv.take<long long>(rows); k_sumsig = cv.take<double>(rows);
+            k_valid = cv.take<uint8_t>(na);
+            k_xyz = d_xyz;
+            k_box = d_box;
+            const H2DItem in[2] = {{d_xyz, xyz + 3 * a0, 24 * na}, {d_box, &boxes[(size_t)a0], sizeof(AtomBox) * na}};
+            e = h2d_row(ctx, in, 2, (size_t)1 << 20);
+        }
+        if (e == hipSuccess) {
+            PROF(ctx, "k_atom_shells");
+            const dim3 grid((unsigned)std::min<size_t>(na, 65536)), block(256);
+            hipLaunchKernelGGL(k_atom_shells, grid, block, 0, ctx->stream, m->geom_dev, m->dens, k_xyz, k_box, (int)na, radius, (int)n_shells, cutoff, fix_mul, fix_inv, k_n, k_sum, k_nsig, k_sumsig, k_valid);
+            e = hipGetLastError();
+            if (e != hipSuccess && first) pinned_untake(ctx, first);      // (nothing was queued that reads or writes the takes: the block and the deliveries are as before)
+        }
+        if (e == hipSuccess && !direct) {
+            const D2HItem parts[5] = {{n ? n + (size_t)a0 * cells : nullptr, k_n, 8 * rows}, {sum ? sum + (size_t)a0 * cells : nullptr, k_sum, 8 * rows},
+                                      {n_sig ? n_sig + (size_t)a0 * cells : nullptr, k_nsig, 8 * rows}, {sum_sig ? sum_sig + (size_t)a0 * cells : nullptr, k_sumsig, 8 * rows},
+                                      {valid ? valid + a0 : nullptr, k_valid, na}};
+            for (int k = 0; k < 5 && e == hipSuccess; ++k)
+                if (parts[k].dst) e = d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes);
+        }
+        if (e == hipSuccess) e = ctx_sync(ctx);      // (delivers the chunk's rows and rewinds the block for the next chunk)
+        if (e != hipSuccess) {
+            arena_put(ctx, scratch);
+            return fail(ctx, PDBEDA_ERR_DEVICE, "radial profiles: %s", hipGetErrorString(e));
+        }
+    }
+    arena_put(ctx, scratch);
+    return PDBEDA_OK;
 }
 
 // ------------------------------------------------------------------------------------

@@ -325,6 +325,9 @@ class DensityAnalysis(object):
     atomRegionDiscrepancyHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy"] + regionDiscrepancyHeader
     symmetryAtomRegionDiscrepancyHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "symmetry", "atom_xyz", "fully_within_density_map"] + regionDiscrepancyHeader
     residueRegionDiscrepancyHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy"] + regionDiscrepancyHeader
+    atomRadialProfileHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'atom_type', 'electrons', 'bfactor', 'valid',
+                               'shell_voxels', 'shell_density', 'shell_significant_voxels', 'shell_significant_density']
+    atomTypeRadialProfileHeader = ['atom_type', 'num_atoms', 'optimized_radius', 'shell_outer_radius', 'median_cumulative_density_per_electron', 'profile_radius']
 
     def __init__(self, pdbid, densityObj=None, diffDensityObj=None, biopdbObj=None, pdbObj=None):
         self.pdbid = pdbid
@@ -1100,3 +1103,58 @@ class DensityAnalysis(object):
         cols, lead, atom_rows, off = self._residuePick(type, keep, False)
         columns, _ = self._discrepancyColumns(cols.coord[atom_rows], np.full(len(atom_rows), radius, dtype=np.float32), off, numSD)
         return self._rows(*lead, *columns)
+
+    # ---- radial profiles (no reference counterpart) ---------------------------------------------
+    def _radialProfileColumns(self, cols, pick, maxRadius, nShells, numSD):
+        """The shells of the atoms ``pick`` of the structure columns over the 2Fo-Fc map at mean + numSD * std (ONE device call), and what
+        the parameter tables say about the atoms: (profile dict, atom type per atom -- None without one --, electrons per atom -- NaN without)."""
+        _requireParams()
+        dm = self.densityObj
+        prof = dm.radialProfiles(cols.coord[pick], maxRadius, nShells, dm.meanDensity + numSD * dm.stdDensity)
+        tables = _pairTables(cols.pair_names, max(len(cols.pair_names), 1))
+        pair = cols.pair_of_atom[pick]
+        atom_type = [tables["pair_type"][k] for k in pair.tolist()]
+        return prof, atom_type, tables["electrons"][pair] if len(pair) else np.zeros(0)
+
+    def calculateAtomRadialProfiles(self, maxRadius=2.0, nShells=20, numSD=1.5, type=""):
+        """One row per atom (``atomRadialProfileHeader``; the atoms and leading columns of ``calculateAtomRegionDensity``): the sphere of
+        ``maxRadius`` around the atom cut into ``nShells`` concentric shells of equal width, over the 2Fo-Fc map, in ONE device call
+        (``pdbeda_radial_profiles`` in include/pdbeda.h has the contract).  shell_voxels / shell_density: the voxels of a shell and their
+        density; shell_significant_*: those above mean + numSD * std (strict) -- each a list of nShells values, innermost shell first.
+        atom_type and electrons are None for an atom whose full name the parameter tables do not type.
+        A profile is per atom, NOT a partition of the map: bonded atoms share voxels once maxRadius exceeds half a bond length, and
+        a shared voxel counts in the profile of each."""
+        cols, pick, lead = self._atomPick(type)
+        prof, atom_type, electrons = self._radialProfileColumns(cols, pick, maxRadius, nShells, numSD)
+        electrons = [None if (t is None or e != e) else e for t, e in zip(atom_type, electrons.tolist())]
+        return self._rows(*lead, atom_type, electrons, cols.bfactor[pick], prof["valid"].astype(bool), prof["n"].tolist(), prof["sum"].tolist(),
+                          prof["nSig"].tolist(), prof["sumSig"].tolist())
+
+    def atomTypeRadialProfiles(self, maxRadius=2.0, nShells=20, numSD=1.5):
+        """One row per atom type present (``atomTypeRadialProfileHeader``), types in sorted order: over the type's atoms that aggregateCloud
+        takes (typed, occupancy != 0, in residues with id[0] == ' ') the median, shell by shell, of the cumulative significant density
+        around the atom per electron -- the curve the type's radius is read from -- beside ``optimized_radius`` (the parameter tables')
+        and ``profile_radius``: the smallest shell outer radius ((k + 1) * maxRadius / nShells) at which that median reaches
+        ``densityElectronRatio`` (RuntimeError without a ratio), None when it never does.
+        The profiles are per atom, NOT a partition of the map: bonded atoms share voxels once maxRadius exceeds half a bond length, so
+        the curve keeps growing past an atom's own density."""
+        ratio = self._needRatio()
+        cols = _structure.columns(self.biopdbObj)
+        tables = _pairTables(cols.pair_names, max(len(cols.pair_names), 1))
+        n_atoms = len(cols.atoms)
+        eligible = (~cols.res_het)[cols.res_of_atom] & tables["known"][cols.pair_of_atom] & (cols.occupancy != 0) if n_atoms else np.zeros(0, dtype=bool)
+        pick = np.nonzero(eligible)[0]
+        prof, atom_type, electrons = self._radialProfileColumns(cols, pick, maxRadius, nShells, numSD)
+        if len(pick) and np.isnan(electrons).any():      # (aggregateCloud's electronsMap[name] raises the same KeyError)
+            raise KeyError(cols.pair_names[int(cols.pair_of_atom[pick][np.isnan(electrons)][0])])
+        width = float(np.float32(maxRadius)) / float(nShells)
+        outer = [(k + 1) * width for k in range(nShells)]
+        per_electron = np.cumsum(prof["sumSig"], axis=1) / electrons[:, None] if len(pick) else np.zeros((0, nShells))
+        types = np.asarray(atom_type, dtype=object)
+        table = []
+        for t in sorted(set(atom_type)):
+            rows = np.nonzero(types == t)[0]
+            median = np.median(per_electron[rows], axis=0)
+            reached = np.nonzero(median >= ratio)[0]
+            table.append([t, len(rows), radiiGlobal.get(t), list(outer), median.tolist(), outer[int(reached[0])] if len(reached) else None])
+        return table

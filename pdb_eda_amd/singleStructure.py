@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile")
 
 
 def numpyConverter(obj):
@@ -97,25 +97,29 @@ TABLES = {
                                       lambda an, o: _plainColumns(an.calculateSymmetryAtomRegionDiscrepancies(o["radius"], o["numSD"], o["type"]), **_SYM)),
     ("blob", None): (lambda an: _DA.blobStatisticsHeader, _blobTable),
     ("peak", None): (lambda an: _DA.peakStatisticsHeader, _peakTable),
+    # (no reference counterpart; the shell columns are lists, carried as the peak table's list columns are)
+    ("profile", "atom"): (lambda an: _DA.atomRadialProfileHeader, lambda an, o: an.calculateAtomRadialProfiles(o["radius"], o["shells"], o["numSD"], o["type"])),
+    ("profile", "atom-type"): (lambda an: _DA.atomTypeRadialProfileHeader, lambda an, o: an.atomTypeRadialProfiles(o["radius"], o["shells"], o["numSD"])),
     ("statistics", "residue"): (lambda an: an.residueMetricsHeaderList, lambda an, o: an.residueMetrics()),
     ("statistics", "atom"): (lambda an: an.atomMetricsHeaderList, lambda an, o: _plainColumns(an.atomMetrics(), **_SYM)),
 }
 
 
 def rows(analyzer, mode, level="atom", radius=3.5, numSD=None, type="", atomMask=None, optimizedRadii=False, green=False, red=False,
-         includePdbid=False):
+         includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak;  level: atom | residue | domain | symmetry-atom
-    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob and peak);  green / red: blob / peak colours
-    (neither = blue);  numSD default 3.0 for green / red / difference, else 1.5 (singleStructure.py:65-67)."""
+    mode: cloud | density | difference | blob | statistics | peak | profile;  level: atom | residue | domain | symmetry-atom
+    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob and peak) | atom-type (profile);  green / red:
+    blob / peak colours (neither = blue);  numSD default 3.0 for green / red / difference, else 1.5 (singleStructure.py:65-67);
+    profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells."""
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % (MODES,))
     key = (mode, None if mode in ("blob", "peak") else level)
     if key not in TABLES:
         raise ValueError("%s mode has the levels %s" % (mode, ", ".join(lv for md, lv in TABLES if md == mode and lv)))
     options = {"radius": float(radius), "numSD": float(numSD if numSD is not None else (3.0 if green or red or mode == "difference" else 1.5)),
-               "type": type, "atomMask": atomMask, "optimizedRadii": optimizedRadii, "green": green, "red": red}
+               "type": type, "atomMask": atomMask, "optimizedRadii": optimizedRadii, "green": green, "red": red, "shells": int(shells)}
     if mode == "cloud":
         analyzer.aggregateCloud()
     header, table = TABLES[key]
