@@ -10,7 +10,7 @@ The CCP4 byte layout written by :func:`ccp4_bytes` is the one the reference pars
 import numpy as np
 
 __all__ = ["ccp4_bytes", "ccp4_header_bytes", "synthetic_params", "noise_grid", "MapSpec", "chain_structure", "gaussian_sum_grid", "smooth_noise",
-           "sweep_param_sets", "SyntheticEntryFiles", "write_entry_files"]
+           "sweep_param_sets", "SyntheticEntryFiles", "write_entry_files", "draw_group_sizes"]
 
 
 class MapSpec(object):
@@ -82,6 +82,18 @@ def smooth_noise(shape, seed, sigma_voxels=1.5):
 def noise_grid(spec, seed, sigma_voxels=1.5):
     nc, nr, ns = spec.ncrs
     return smooth_noise((ns, nr, nc), seed, sigma_voxels)
+
+
+def draw_group_sizes(rng, n_atoms, choices=(1, 1, 2, 5, 9)):
+    """Sizes of consecutive groups that cover ``n_atoms`` atoms: each drawn from ``choices`` (one ``rng.choice`` a group), the last
+    cut to what is left -- the sphere batches' groups of the soak tool and of the batch-limit tests."""
+    sizes = []
+    left = int(n_atoms)
+    while left > 0:
+        s = int(min(left, rng.choice(list(choices))))
+        sizes.append(s)
+        left -= s
+    return sizes
 
 
 # ---- synthetic model: poly-ALA random-walk chain ---------------------------------------

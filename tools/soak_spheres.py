@@ -41,12 +41,7 @@ for k in range(n_cases):
     radii = rng.choice([0.2, 0.9, 1.7, 2.6, 3.5, 5.0], n_atoms).astype(np.float32)
     cuts = [0.0, float(dm.meanDensity + 1.0 * dm.stdDensity), -float(dm.meanDensity + 1.2 * dm.stdDensity)]
     # groups: singles, then random runs
-    sizes = []
-    left = n_atoms
-    while left > 0:
-        s = int(min(left, rng.choice([1, 1, 2, 5, 9])))
-        sizes.append(s)
-        left -= s
+    sizes = synthetic.draw_group_sizes(rng, n_atoms)
     goff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     for cut in cuts:
         bl = dm._map.sphere_blobs(xyz, radii, goff, cut)
