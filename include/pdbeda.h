@@ -280,6 +280,40 @@ int pdbeda_region_sums(pdbeda_map *map, const double *xyz, const float *radii, i
 int pdbeda_radial_profiles(pdbeda_map *map, const double *xyz, int64_t n_atoms, float radius, int32_t n_shells, float cutoff,
                            int64_t *n, double *sum, int64_t *n_sig, double *sum_sig, uint8_t *valid); /* any output may be NULL */
 
+/* ---- nearest-atom map partition ----------------------------------------------------- */
+/* Every voxel of the map to the atom nearest to it, counted ONCE (no reference counterpart: every per-atom number of the
+ * reference, and pdbeda_region_sums / pdbeda_radial_profiles here, is a sphere around one atom, so a voxel beside a bond is
+ * counted for a dozen atoms and the per-atom numbers add up to nothing).
+ * Domain: the voxels of the non-repeating box header.uniqueNcrs -- the domain of createFullCrsList (ccp4.py:262-269, 452-461), of
+ * the whole-map blob lists and of the peaks.  Nothing wraps and no voxel is counted twice.
+ * Owner of voxel v: p = crs2xyzCoord(v) (ccp4.py:304-316); d2_a = (dx*dx + dy*dy) + dz*dz in unfused fp64 for every atom a; the
+ * owner is the atom with the smallest d2, ties go to the LOWEST atom index (coincident atoms are allowed: the first owns).  The
+ * owner counts only if sqrt(d2) <= (double)max_distance (IEEE sqrt, inclusive, float32 max_distance) -- the sphere test of
+ * pdbeda_region_sums; if it does not, the voxel is UNOWNED (owner -1).  An atom far from the map simply owns nothing.
+ * Per atom, [n_atoms] each:
+ *   n                 voxels owned;
+ *   sum               their density;
+ *   n_pos / sum_pos   the owned voxels with density > cutoff;
+ *   n_neg / sum_neg   the owned voxels with density < -cutoff      (strict, float32 cutoff >= 0: the filters of pdbeda_region_sums).
+ * Over the unowned voxels: unowned_n = {n, n_pos, n_neg}, unowned_sum = {sum, sum_pos, sum_neg, sum_sq}; sum_sq is the fp64 sum of
+ * the squares, folded in a fixed order (per workgroup, then over the workgroups in index order): n, sum and sum_sq give the mean
+ * and the deviation of the map where there is no model.
+ * owner: the box's voxels, [s][r][c] of the box, c fastest (uniqueNcrs[2] x uniqueNcrs[1] x uniqueNcrs[0]), the owner's index in
+ * `xyz` or -1.
+ * A NaN voxel (and an infinite one) is owned like any other and counted in n; it enters no density sum and neither filter.
+ * A voxel's density enters a sum rounded once to the map's fixed-point quantum (the quantum of the blob sums: <= 2^-36 max |rho|)
+ * and the sums are folded as integers: bit-identical from run to run, independent of the order of the atomics and -- apart from
+ * the tie rule -- of the order of the atom list; within quantum / 2 per voxel of the exact sum; an atom that owns nothing gets
+ * exact zeros.
+ * n_atoms == 0 succeeds: everything is unowned.  PDBEDA_ERR_ARGUMENT before any launch: a max_distance that is not finite or
+ * <= 0, a cutoff that is NaN or < 0, a non-finite coordinate, n_atoms >= 2^31.  Synchronous; a failing call leaves the context
+ * usable. */
+int pdbeda_map_partition(pdbeda_map *map, const double *xyz, int64_t n_atoms, float max_distance, float cutoff,
+                         int64_t *n, double *sum, int64_t *n_pos, double *sum_pos, int64_t *n_neg, double *sum_neg, /* [n_atoms] each */
+                         int64_t unowned_n[3], double unowned_sum[4],   /* n, n_pos, n_neg; sum, sum_pos, sum_neg, sum_sq */
+                         int32_t *owner);                               /* box voxels, [s][r][c] of the box, c fastest; -1 = unowned */
+                         /* any output may be NULL */
+
 /* ---- aggregateCloud ------------------------------------------------------------------ */
 /* DensityAnalysis.aggregateCloud up to its statistics tail (densityAnalysis.py:571-731) as ONE call: the clouds of every
  * eligible atom (findAberrantBlobs, 603), the centroid-distance cut-off over all atoms (607), the best cloud and the pooled

@@ -116,6 +116,7 @@ _SIGS = {
     "pdbeda_peaklist_free": (C.c_int, [_p]),
     "pdbeda_region_sums": (C.c_int, [_p, _p, _p, _i64, _p, _i64, C.c_float, _p, _p, _p, _p]),
     "pdbeda_radial_profiles": (C.c_int, [_p, _p, _i64, C.c_float, C.c_int32, C.c_float, _p, _p, _p, _p, _p]),
+    "pdbeda_map_partition": (C.c_int, [_p, _p, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pdbeda_aggregate_cloud": (C.c_int, [_p, C.POINTER(CloudAtoms), C.c_float, C.c_double, C.POINTER(_p)]),
     "pdbeda_cloud_counts": (C.c_int, [_p, _p, _p]),
     "pdbeda_cloud_atom_rows": (C.c_int, [_p, _p, _p, _p, _p, _p]),
@@ -665,6 +666,23 @@ class DeviceMap(object):
         self._ctx.check(self._ctx._lib.pdbeda_radial_profiles(self._h, _ptr(xyz), len(xyz), C.c_float(radius), int(n_shells), C.c_float(cutoff),
                                                               _ptr(n), _ptr(total), _ptr(n_sig), _ptr(total_sig), _ptr(valid)), "pdbeda_radial_profiles")
         return {"n": n, "sum": total, "nSig": n_sig, "sumSig": total_sig, "valid": valid.astype(bool)}
+
+    def partition(self, xyz, max_distance, cutoff, owners=False):
+        """pdbeda_map_partition: every voxel of the non-repeating box to its nearest atom within ``max_distance`` (or to nobody).
+        A dict of (n_atoms,) arrays ``n``, ``sum``, ``nPos``, ``sumPos``, ``nNeg``, ``sumNeg``, the unowned totals ``unownedN`` (n, n_pos,
+        n_neg) and ``unownedSum`` (sum, sum_pos, sum_neg, sum_sq) and, with ``owners``, the int32 volume ``owner`` (-1 = unowned)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        na = len(xyz)
+        out = {"n": np.zeros(na, np.int64), "sum": np.zeros(na), "nPos": np.zeros(na, np.int64), "sumPos": np.zeros(na),
+               "nNeg": np.zeros(na, np.int64), "sumNeg": np.zeros(na), "unownedN": np.zeros(3, np.int64), "unownedSum": np.zeros(4)}
+        owner = np.full(self.unique_shape, -1, dtype=np.int32) if owners else None
+        self._ctx.check(self._ctx._lib.pdbeda_map_partition(self._h, _ptr(xyz) if na else None, na, C.c_float(max_distance), C.c_float(cutoff),
+                                                            _ptr(out["n"]), _ptr(out["sum"]), _ptr(out["nPos"]), _ptr(out["sumPos"]), _ptr(out["nNeg"]),
+                                                            _ptr(out["sumNeg"]), _ptr(out["unownedN"]), _ptr(out["unownedSum"]),
+                                                            _ptr(owner) if owners else None), "pdbeda_map_partition")
+        if owners:
+            out["owner"] = owner
+        return out
 
     def aggregate_cloud(self, xyz, radius, weight, residue, alias, key, bonded_off, bonded, owner_key, cutoff, min_cloud_electrons):
         """pdbeda_aggregate_cloud: everything of aggregateCloud that touches voxels, in one call.  Returns a dict of arrays:

@@ -411,6 +411,17 @@ class DensityMatrix(object):
         xyz = np.asarray(xyzCoordList, dtype=np.float64).reshape(-1, 3)
         return self._map.radial_profiles(xyz, maxRadius, nShells, densityCutoff)
 
+    # -- nearest-atom partition (no reference counterpart) -----------------------------
+    def partition(self, xyzList, maxDistance, cutoff=0.0, owners=False):
+        """Every voxel of the non-repeating box (the domain of ``createFullCrsList``) to the coordinate nearest to it within
+        ``maxDistance`` -- ties to the lowest index -- or to nobody, each voxel counted ONCE, in one device call
+        (``pdbeda_map_partition`` in include/pdbeda.h has the contract).  A dict of (n,) arrays ``n`` / ``sum`` (voxels owned and their
+        density), ``nPos`` / ``sumPos`` (density > cutoff), ``nNeg`` / ``sumNeg`` (density < -cutoff; strict, cutoff >= 0), the totals
+        over the unowned voxels ``unownedN`` (n, n_pos, n_neg) and ``unownedSum`` (sum, sum_pos, sum_neg, sum of squares) and, with
+        ``owners``, ``owner``: an (ns', nr', nc') int32 array of the box, -1 where nobody owns the voxel."""
+        xyz = np.asarray(xyzList, dtype=np.float64).reshape(-1, 3)
+        return self._map.partition(xyz, maxDistance, cutoff, owners)
+
     # -- whole-map blobs ------------------------------------------------------------
     def createFullBlobList(self, cutoff):
         """ref ccp4.py:463-473: threshold the non-repeating box and cluster (None for cutoff == 0)."""
@@ -576,6 +587,17 @@ class DeviceBlobs(collections.abc.Sequence):
 
     def __repr__(self):
         return "DeviceBlobs(%d blobs)" % len(self)
+
+    def voxelLists(self):
+        """(crs[N, 3] int32 grouped by blob in list order, offsets[len + 1]): the voxels of every blob, a device list at a time."""
+        parts = [seg.bl.voxels() for seg in self._segments]
+        if not parts:
+            return np.zeros((0, 3), dtype=np.int32), np.zeros(1, dtype=np.int64)
+        offsets, base = [np.zeros(1, dtype=np.int64)], 0
+        for crs, off in parts:
+            offsets.append(off[1:] + base)
+            base += len(crs)
+        return np.concatenate([crs for crs, off in parts]), np.concatenate(offsets)
 
     def columns(self):
         """{"centroid", "totalDensity", "n", "volume"} of all blobs as arrays -- or None once any of the objects exists (they

@@ -30,6 +30,7 @@
 #include "pdbeda_contacts.h"
 #include "pdbeda_peaks.h"
 #include "pdbeda_profiles.h"
+#include "pdbeda_partition.h"
 
 using namespace pdbeda;
 
@@ -3025,6 +3026,112 @@ extern "C" int pdbeda_image_coords(pdbeda_ctx *ctx, const double *poly_xyz, int6
         { PROF(ctx, "k_image_emit"); hipLaunchKernelGGL(k_image_emit, dim3(grid_for(total, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, r_out ? r_out : d_out); }
         HIP_TRY(ctx, hipGetLastError());
         if (!r_out) HIP_TRY(ctx, d2h(ctx, out_xyz, d_out, 24 * (size_t)total));
+        return 0;
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// Nearest-atom partition of a map (no reference counterpart; the contract: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// The launch graph: memset of the cell counts and the integer tables; k_grid_count_points / k_grid_scan (the contacts grid's) and
+// k_grid_scatter_indexed over the atoms inside the crop box -- the xyz bounding box of the map's box grown by the maximum distance: an atom
+// outside it owns nothing, and the grid never grows with atoms that lie far from the map; k_partition_tile, a workgroup per voxel tile;
+// k_partition_finish.  One wait.  make_cell_grid counts cells in fp64 and enlarges the EDGE until they number at most 2^22, so a box that is
+// huge beside the maximum distance costs longer cell lists, never an overflowing dimension.
+// Measured and removed: the same tile walking the 27 cells around every voxel in global memory instead of staging.
+extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_atoms, float max_distance, float cutoff,
+                                    int64_t *n, double *sum, int64_t *n_pos, double *sum_pos, int64_t *n_neg, double *sum_neg,
+                                    int64_t unowned_n[3], double unowned_sum[4], int32_t *owner) {
+    if (!m || n_atoms < 0 || (n_atoms > 0 && !xyz)) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = m->ctx;
+    if (!std::isfinite(max_distance) || !(max_distance > 0.0f)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map partition: the maximum distance must be finite and > 0");
+    if (std::isnan(cutoff) || cutoff < 0.0f) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map partition: the cutoff must be >= 0");
+    if (n_atoms >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map partition: 2^31 atoms or more");
+    if (!all_finite(xyz, 3 * n_atoms)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map partition: non-finite coordinate");
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    const Geom &g = m->geom;
+    const int uc = g.unique_ncrs[0], ur = g.unique_ncrs[1], us = g.unique_ncrs[2];
+    const int64_t nbox = (int64_t)uc * ur * us;
+    const int tiles_c = (uc + PT_C - 1) / PT_C, tiles_r = (ur + PT_R - 1) / PT_R, tiles_s = (us + PT_S - 1) / PT_S;
+    const int64_t n_tiles = (int64_t)tiles_c * tiles_r * tiles_s;
+    if (nbox <= 0 || n_tiles >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map partition: the box is empty or has 2^31 tiles or more");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (m->fix_mul == 0.0 && !m->fix_refused) {      // (a wait when the map's range is not known yet: before anything is staged)
+        const int rc = map_fix_mul(m);
+        if (rc && !m->fix_refused) return rc;
+    }
+    const double maxd = (double)max_distance;
+    // the crop box, and the grid over its intersection with the atoms' bounding box
+    double crop_lo[3] = {INFINITY, INFINITY, INFINITY}, crop_hi[3] = {-INFINITY, -INFINITY, -INFINITY}, alo[3], ahi[3], glo[3], ghi[3];
+    for (int k = 0; k < 8; ++k) {
+        double p[3];
+        crs2xyz(g, (k & 1) ? uc - 1 : 0, (k & 2) ? ur - 1 : 0, (k & 4) ? us - 1 : 0, p);
+        for (int q = 0; q < 3; ++q) { crop_lo[q] = std::min(crop_lo[q], p[q]); crop_hi[q] = std::max(crop_hi[q], p[q]); }
+    }
+    bbox3(xyz, n_atoms, alo, ahi);
+    bool empty = n_atoms == 0;
+    for (int q = 0; q < 3; ++q) {
+        const double pad = maxd * (1.0 + 1e-5) + 1e-8 * (std::fabs(crop_lo[q]) + std::fabs(crop_hi[q]) + 1.0);      // (wider than a tile's own margin)
+        crop_lo[q] -= pad; crop_hi[q] += pad;
+        glo[q] = std::max(crop_lo[q], alo[q]); ghi[q] = std::min(crop_hi[q], ahi[q]);
+        if (!(glo[q] <= ghi[q])) empty = true;
+    }
+    if (empty)
+        for (int q = 0; q < 3; ++q) glo[q] = ghi[q] = crop_lo[q];      // (one cell, and no atom in it)
+    const CellGrid grid = make_cell_grid(glo, ghi, maxd, n_atoms, crop_lo, crop_hi);
+    const int64_t cells = grid.n_cells;
+    const size_t na = (size_t)n_atoms, tables = 6 * na + 8;
+    const size_t bytes = align_up(24 * na) + 2 * align_up(4 * cells) + align_up(4 * (cells + 1)) + align_up(24 * na) + align_up(4 * na) + align_up(8 * tables) +
+                         align_up(8 * n_tiles) + 2 * align_up(24 * na) + align_up(64) + (owner ? align_up(4 * nbox) : 0);
+    return with_scratch(ctx, bytes, [&](char *base) -> int {
+        Carver cv(base);
+        double *d_xyz = cv.take<double>(3 * na);
+        unsigned *d_count = cv.take<unsigned>(cells);
+        unsigned *d_cursor = cv.take<unsigned>(cells);
+        unsigned *d_start = cv.take<unsigned>(cells + 1);
+        double *d_sorted = cv.take<double>(3 * na);
+        int *d_sidx = cv.take<int>(na);
+        unsigned long long *d_tab = cv.take<unsigned long long>(tables);      // atom_n [3][n] | atom_sum [3][n] | unowned [6] | range [1]
+        double *d_tsq = cv.take<double>(n_tiles);
+        long long *d_on = cv.take<long long>(3 * na);
+        double *d_os = cv.take<double>(3 * na);
+        long long *d_un = cv.take<long long>(8);      // unowned_n [3] | (as doubles) unowned_sum [4]
+        double *d_us = reinterpret_cast<double *>(d_un + 3);
+        int32_t *d_owner = owner ? cv.take<int32_t>(nbox) : nullptr;
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 4 * (size_t)cells, st));
+        HIP_TRY(ctx, hipMemsetAsync(d_tab, 0, 8 * tables, st));
+        double fix_mul = m->fix_mul;
+        if (m->fix_refused) {      // NaN / infinite voxels: they enter no sum, and the quantum comes from the finite voxels of the box
+            unsigned long long bits = 0;
+            { PROF(ctx, "k_partition_range"); hipLaunchKernelGGL(k_partition_range, dim3(grid_for(nbox, 256, 4096)), dim3(256), 0, st, m->dens, g.ncrs[0], g.ncrs[1], uc, ur, us, d_tab + tables - 1); }
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, d2h(ctx, &bits, d_tab + tables - 1, 8));
+            HIP_TRY(ctx, ctx_sync(ctx));
+            double top;
+            memcpy(&top, &bits, 8);
+            int S = 40, e = 0;
+            if (top > 0.0) { (void)frexp(top * (double)std::max<int64_t>(nbox, 1ll << 22), &e); S = 61 - e; }      // (|sum| <= voxels x max |rho| < 2^61)
+            fix_mul = ldexp(1.0, std::max(-900, std::min(S, 900)));
+        }
+        if (n_atoms > 0) HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, 24 * na));
+        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_atoms, 256)), dim3(256), 0, st, d_xyz, n_atoms, grid, d_count); }
+        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count, (int)cells, d_start, d_cursor, nullptr); }
+        { PROF(ctx, "k_grid_scatter_indexed"); hipLaunchKernelGGL(k_grid_scatter_indexed, dim3(grid_for(n_atoms, 256)), dim3(256), 0, st, d_xyz, n_atoms, grid, d_cursor, d_sorted, d_sidx, n_atoms); }
+        PartitionArgs a;
+        a.geom = m->geom_dev; a.dens = m->dens;
+        a.uc = uc; a.ur = ur; a.us = us; a.tiles_c = tiles_c; a.tiles_r = tiles_r;
+        a.grid = grid; a.sorted = d_sorted; a.sorted_index = d_sidx; a.start = d_start;
+        a.max_distance = maxd; a.cutoff = (double)cutoff; a.fix_mul = fix_mul;
+        a.atom_n = d_tab; a.atom_sum = d_tab + 3 * na; a.n_atoms = n_atoms; a.unowned = d_tab + 6 * na;
+        a.tile_sq = d_tsq; a.owner = d_owner;
+        { PROF(ctx, "k_partition_tile"); hipLaunchKernelGGL(k_partition_tile, dim3((unsigned)n_tiles), dim3(256), 0, st, a); }
+        { PROF(ctx, "k_partition_finish"); hipLaunchKernelGGL(k_partition_finish, dim3(grid_for(3 * n_atoms, 256, 1024) + 1), dim3(256), 0, st, a.atom_n, a.atom_sum, n_atoms, a.unowned, d_tsq, n_tiles, 1.0 / fix_mul, d_on, d_os, d_un, d_us); }
+        HIP_TRY(ctx, hipGetLastError());
+        const D2HItem parts[9] = {{n, d_on, 8 * na}, {n_pos, d_on + na, 8 * na}, {n_neg, d_on + 2 * na, 8 * na}, {sum, d_os, 8 * na}, {sum_pos, d_os + na, 8 * na},
+                                  {sum_neg, d_os + 2 * na, 8 * na}, {unowned_n, d_un, 24}, {unowned_sum, d_us, 32}, {owner, d_owner, 4 * (size_t)nbox}};
+        for (int k = 0; k < 9; ++k)
+            if (parts[k].dst && parts[k].bytes) HIP_TRY(ctx, d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes));
         return 0;
     });
 }

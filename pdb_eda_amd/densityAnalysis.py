@@ -293,6 +293,47 @@ def _segmentMeans(values, counts):
     return out
 
 
+def _partitionRollup(columns, offsets):
+    """Per-residue sums of per-atom partition columns: ``columns`` are arrays over the picked atoms in residue order, residue k has the
+    atoms offsets[k] .. offsets[k + 1] (none: zeros).  Integer columns stay integers."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    out = []
+    for column in columns:
+        column = np.asarray(column)
+        running = np.concatenate([np.zeros(1, dtype=column.dtype), np.cumsum(column)]) if column.dtype.kind in "iu" else None
+        if running is not None:
+            out.append(running[offsets[1:]] - running[offsets[:-1]])
+        else:      # (floats: each residue summed on its own, not a difference of running sums)
+            out.append(np.array([math.fsum(column[a:b].tolist()) for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())], dtype=np.float64))
+    return out
+
+
+def _blobOwners(owner, crs, offsets):
+    """Who owns the voxels of every blob: ``owner`` is the partition's int32 volume ([s][r][c] of the box, -1 = unowned), ``crs`` the blobs'
+    voxels (n x 3, columns c, r, s) grouped by blob, blob k having rows offsets[k] .. offsets[k + 1].  Arrays over the blobs: num_voxels,
+    unowned_voxels, num_owner_atoms, main_owner (the atom that owns most of the blob's voxels, ties to the lowest index; -1 when
+    nobody owns any) and main_owner_voxels."""
+    crs, offsets = np.asarray(crs, dtype=np.int64).reshape(-1, 3), np.asarray(offsets, dtype=np.int64)
+    n_blobs = len(offsets) - 1
+    sizes = np.diff(offsets)
+    who = np.asarray(owner)[crs[:, 2], crs[:, 1], crs[:, 0]].astype(np.int64)
+    blob = np.repeat(np.arange(n_blobs, dtype=np.int64), sizes)
+    span = int(who.max()) + 2 if len(who) else 1
+    pair, count = np.unique(blob * span + (who + 1), return_counts=True)
+    pair_blob, pair_who = pair // span, pair % span - 1
+    unowned = np.zeros(n_blobs, dtype=np.int64)
+    unowned[pair_blob[pair_who < 0]] = count[pair_who < 0]
+    held = pair_who >= 0
+    pair_blob, pair_who, count = pair_blob[held], pair_who[held], count[held]
+    n_owners = np.bincount(pair_blob, minlength=n_blobs).astype(np.int64)
+    order = np.lexsort((pair_who, -count, pair_blob))      # per blob: most voxels first, then the lowest atom index
+    first = order[np.concatenate([[True], np.diff(pair_blob[order]) != 0])] if len(order) else order
+    main, main_voxels = np.full(n_blobs, -1, dtype=np.int64), np.zeros(n_blobs, dtype=np.int64)
+    main[pair_blob[first]] = pair_who[first]
+    main_voxels[pair_blob[first]] = count[first]
+    return sizes.astype(np.int64), unowned, n_owners, main, main_voxels
+
+
 def _norm3(x):
     """np.linalg.norm of a 1-D float64 vector, as numpy computes it (sqrt(x.dot(x))), without the dispatch overhead."""
     return math.sqrt(float(x.dot(x)))
@@ -325,6 +366,12 @@ class DensityAnalysis(object):
     atomRegionDiscrepancyHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy"] + regionDiscrepancyHeader
     symmetryAtomRegionDiscrepancyHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "symmetry", "atom_xyz", "fully_within_density_map"] + regionDiscrepancyHeader
     residueRegionDiscrepancyHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy"] + regionDiscrepancyHeader
+    partitionHeader = ['num_voxels', 'positive_discrepancy', 'num_electrons_positive_discrepancy', 'negative_discrepancy', 'num_electrons_negative_discrepancy',
+                       'abs_discrepancy', 'num_electrons_abs_discrepancy', 'net_discrepancy', 'num_electrons_net_discrepancy']
+    atomPartitionHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy"] + partitionHeader
+    residuePartitionHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy"] + partitionHeader
+    blobOwnershipHeader = ['num_voxels', 'unowned_voxels', 'num_owner_atoms', 'chain', 'residue_number', 'residue_name', 'atom_name', 'atom_symmetry',
+                           'main_owner_voxels']
     atomRadialProfileHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'atom_type', 'electrons', 'bfactor', 'valid',
                                'shell_voxels', 'shell_density', 'shell_significant_voxels', 'shell_significant_density']
     atomTypeRadialProfileHeader = ['atom_type', 'num_atoms', 'optimized_radius', 'shell_outer_radius', 'median_cumulative_density_per_electron', 'profile_radius']
@@ -342,6 +389,7 @@ class DensityAnalysis(object):
         self._symmetryOnlyAtomCoords = None
         self._asymmetryAtomCoords = None
         self._greenBlobList = None
+        self._partitions = {}
         self._redBlobList = None
         self._blueBlobList = None
         self._greenPeakList = None
@@ -1158,3 +1206,109 @@ class DensityAnalysis(object):
             reached = np.nonzero(median >= ratio)[0]
             table.append([t, len(rows), radiiGlobal.get(t), list(outer), median.tolist(), outer[int(reached[0])] if len(reached) else None])
         return table
+
+    # ---- nearest-atom partition of the Fo-Fc map (no reference counterpart) ----------------------
+    def _partition(self, maxDistance, numSD):
+        """The partition of the Fo-Fc map among ALL symmetry atoms at mean + numSD * std (``pdbeda_map_partition`` in include/pdbeda.h
+        has the contract), with the owner volume: computed once per (maxDistance, numSD) and kept, like the blob lists."""
+        key = (float(np.float32(maxDistance)), float(numSD))
+        if key not in self._partitions:
+            coords = self.symmetryAtomCoords
+            if len(coords) == 0:
+                raise ValueError("XB must be a 2-dimensional array.")       # (the blob table's failure for a file without operators)
+            dm = self.diffDensityObj
+            self._partitions[key] = dm.partition(np.asarray(coords, dtype=np.float64), maxDistance, dm.meanDensity + numSD * dm.stdDensity, owners=True)
+        return self._partitions[key]
+
+    def _partitionColumns(self, atom_rows, maxDistance, numSD):
+        """(num_voxels, pos, neg) of the structure's atoms ``atom_rows`` as themselves (the identity images of the symmetry list); an atom
+        the list does not hold -- it lies outside the map's box -- owns nothing."""
+        ratio = self._needRatio()
+        part = self._partition(maxDistance, numSD)
+        symmetryAtoms = self.symmetryAtoms
+        cols = _structure.columns(self.biopdbObj)
+        listed = np.full(len(cols.atoms), -1, dtype=np.int64)
+        own = np.nonzero(symmetryAtoms._ident)[0]
+        listed[symmetryAtoms._idx[own]] = own
+        where = listed[atom_rows]
+        have = where >= 0
+        pick = lambda column: np.where(have, column[np.where(have, where, 0)], 0).astype(column.dtype) if len(column) else np.zeros(len(where), dtype=column.dtype)
+        return ratio, pick(part["n"]), pick(part["sumPos"]), pick(part["sumNeg"])
+
+    @staticmethod
+    def _partitionTableColumns(ratio, n, pos, neg):
+        absd, net = pos - neg, pos + neg
+        return [n, pos, pos / ratio, neg, neg / ratio, absd, absd / ratio, net, net / ratio]
+
+    def calculateAtomPartitionDiscrepancies(self, maxDistance=3.5, numSD=3.0, type=""):
+        """One row per atom (``atomPartitionHeader``; the atoms and leading columns of ``calculateAtomRegionDiscrepancies``): the voxels of
+        the Fo-Fc map that are nearer to this atom than to any other atom or symmetry image, within ``maxDistance``, and their density
+        beyond mean +- numSD * std.  Every voxel is counted for ONE atom, so the rows add up."""
+        cols, pick, lead = self._atomPick(type)
+        ratio, n, pos, neg = self._partitionColumns(pick, maxDistance, numSD)
+        return self._rows(*lead, *self._partitionTableColumns(ratio, n, pos, neg))
+
+    def calculateResiduePartitionDiscrepancies(self, maxDistance=3.5, numSD=3.0, type=""):
+        """One row per residue (``residuePartitionHeader``; the leading columns of ``calculateResidueRegionDiscrepancies``): its atoms' rows
+        of ``calculateAtomPartitionDiscrepancies`` summed."""
+        cols, lead, atom_rows, off = self._residuePick(type, None, False)
+        ratio, n, pos, neg = self._partitionColumns(atom_rows, maxDistance, numSD)
+        n, pos, neg = _partitionRollup([n, pos, neg], off)
+        return self._rows(*lead, *self._partitionTableColumns(ratio, n, pos, neg))
+
+    def partitionSummary(self, maxDistance=3.5, numSD=3.0):
+        """The Fo-Fc map's box in three classes -- voxels owned by atoms of the asymmetric unit, by symmetry images, by nobody (farther
+        than ``maxDistance`` from every atom: solvent) -- with the noise level where there is no model beside the whole map's."""
+        ratio = self._needRatio()
+        part = self._partition(maxDistance, numSD)
+        dm = self.diffDensityObj
+        own = np.asarray(self.symmetryAtoms._ident, dtype=bool)
+        box = int(np.prod(part["owner"].shape))
+        n_un = int(part["unownedN"][0])
+        total, total_pos, total_neg, total_sq = part["unownedSum"].tolist()
+        mean = total / n_un if n_un else float("nan")
+        std = math.sqrt(max(total_sq / n_un - mean * mean, 0.0)) if n_un else float("nan")
+        out = {"max_distance": float(np.float32(maxDistance)), "num_sd": float(numSD), "box_voxels": box,
+               "asymmetric_unit_voxels": int(part["n"][own].sum()), "symmetry_voxels": int(part["n"][~own].sum()), "unowned_voxels": n_un,
+               "unowned_fraction": n_un / box, "unowned_mean": mean, "unowned_std": std, "map_mean": dm.meanDensity, "map_std": dm.stdDensity}
+        for name, pos, neg in (("asymmetric_unit", math.fsum(part["sumPos"][own].tolist()), math.fsum(part["sumNeg"][own].tolist())),
+                               ("symmetry", math.fsum(part["sumPos"][~own].tolist()), math.fsum(part["sumNeg"][~own].tolist())), ("unowned", total_pos, total_neg)):
+            out[name + "_positive_discrepancy"], out[name + "_negative_discrepancy"] = pos, neg
+            out["num_electrons_" + name + "_positive_discrepancy"], out["num_electrons_" + name + "_negative_discrepancy"] = pos / ratio, neg / ratio
+        return out
+
+    def _partitionOwners(self, maxDistance):
+        """The owner volume at ``maxDistance``: it does not depend on the cutoff, so any partition kept for that distance serves (one at
+        numSD 3.0 is made when there is none)."""
+        distance = float(np.float32(maxDistance))
+        for (d, _), part in self._partitions.items():
+            if d == distance:
+                return part["owner"]
+        return self._partition(maxDistance, 3.0)["owner"]
+
+    def calculateBlobOwnership(self, blobList, maxDistance=3.5):
+        """One row per blob of a whole-map list of the Fo-Fc map (``blobOwnershipHeader``): how many of its voxels nobody owns
+        (unmodelled density), how many atoms share the rest, and the atom that owns most of them (ties: the lowest symmetry-atom
+        index; None columns when nobody owns a voxel).  Host glue over the partition's owner volume."""
+        self._needRatio()
+        owner = self._partitionOwners(maxDistance)
+        if not blobList:
+            return []
+        if isinstance(blobList, ccp4.DeviceBlobs):
+            crs, off = blobList.voxelLists()
+        else:
+            lists = [sorted(blob.crsList) for blob in blobList]
+            crs = np.array([v for one in lists for v in one], dtype=np.int64).reshape(-1, 3)
+            off = np.concatenate([[0], np.cumsum([len(one) for one in lists])]).astype(np.int64)
+        sizes, unowned, n_owners, main, main_voxels = _blobOwners(owner, crs, off)
+        held = np.nonzero(main >= 0)[0]
+        atom_rows, symmetry, _ = self.symmetryAtoms.columns(main[held])
+        cols = _structure.columns(self.biopdbObj)
+        names = {"chain": cols.atom_lists("chain"), "number": cols.atom_lists("number"), "resname": cols.atom_lists("resname"), "name": list(cols.name)}
+        columns = {k: [None] * len(sizes) for k in ("chain", "number", "resname", "name", "symmetry")}
+        for k, row, sym in zip(held.tolist(), atom_rows.tolist(), symmetry.tolist()):
+            for which in names:
+                columns[which][k] = names[which][row]
+            columns["symmetry"][k] = tuple(sym)
+        return [list(row) for row in zip(sizes.tolist(), unowned.tolist(), n_owners.tolist(), columns["chain"], columns["number"], columns["resname"], columns["name"],
+                                         columns["symmetry"], main_voxels.tolist())]

@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition")
 
 
 def numpyConverter(obj):
@@ -68,6 +68,30 @@ def _peakTable(analyzer, o):
     return _plainColumns(table, listColumns=(10,), floatColumns=(11, 12))
 
 
+def _partitionBlobTable(analyzer, o):
+    """partition / blob: who owns the voxels of the green and / or red Fo-Fc blobs (green when neither is asked for)."""
+    diffObj, numSD = analyzer.diffDensityObj, o["numSD"]
+    cut = diffObj.meanDensity + numSD * diffObj.stdDensity
+    if o["green"] and o["red"]:
+        lists = diffObj.createFullBlobLists(cut)
+    else:
+        lists = [diffObj.createFullBlobList(-cut if o["red"] else cut)]
+    table = [row for blobs in lists for row in analyzer.calculateBlobOwnership(blobs, o["radius"])]
+    for row in table:      # (the owner's symmetry tag as a list, like the blob table's; None where nobody owns a voxel of the blob)
+        row[7] = None if row[7] is None else list(row[7])
+    return table
+
+
+def _partitionSummaryTable(analyzer, o):
+    summary = analyzer.partitionSummary(o["radius"], o["numSD"])
+    return [[summary[name] for name in _PARTITION_SUMMARY]]
+
+
+_PARTITION_SUMMARY = ["max_distance", "num_sd", "box_voxels", "asymmetric_unit_voxels", "symmetry_voxels", "unowned_voxels", "unowned_fraction", "unowned_mean",
+                      "unowned_std", "map_mean", "map_std"] + [prefix + cls + "_" + sign + "_discrepancy" for cls in ("asymmetric_unit", "symmetry", "unowned")
+                                                              for sign in ("positive", "negative") for prefix in ("", "num_electrons_")]
+
+
 def _cloudTable(attribute):
     def table(analyzer, o):
         return [[numpyConverter(v) for v in item] + [analyzer.densityElectronRatio] for item in getattr(analyzer, attribute)]
@@ -100,6 +124,11 @@ TABLES = {
     # (no reference counterpart; the shell columns are lists, carried as the peak table's list columns are)
     ("profile", "atom"): (lambda an: _DA.atomRadialProfileHeader, lambda an, o: an.calculateAtomRadialProfiles(o["radius"], o["shells"], o["numSD"], o["type"])),
     ("profile", "atom-type"): (lambda an: _DA.atomTypeRadialProfileHeader, lambda an, o: an.atomTypeRadialProfiles(o["radius"], o["shells"], o["numSD"])),
+    # (no reference counterpart: the Fo-Fc map partitioned among the symmetry atoms; ``radius`` is the maximum distance)
+    ("partition", "atom"): (lambda an: _DA.atomPartitionHeader, lambda an, o: an.calculateAtomPartitionDiscrepancies(o["radius"], o["numSD"], o["type"])),
+    ("partition", "residue"): (lambda an: _DA.residuePartitionHeader, lambda an, o: an.calculateResiduePartitionDiscrepancies(o["radius"], o["numSD"], o["type"])),
+    ("partition", "summary"): (lambda an: list(_PARTITION_SUMMARY), _partitionSummaryTable),
+    ("partition", "blob"): (lambda an: _DA.blobOwnershipHeader, _partitionBlobTable),
     ("statistics", "residue"): (lambda an: an.residueMetricsHeaderList, lambda an, o: an.residueMetrics()),
     ("statistics", "atom"): (lambda an: an.atomMetricsHeaderList, lambda an, o: _plainColumns(an.atomMetrics(), **_SYM)),
 }
@@ -109,16 +138,17 @@ def rows(analyzer, mode, level="atom", radius=3.5, numSD=None, type="", atomMask
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile;  level: atom | residue | domain | symmetry-atom
-    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob and peak) | atom-type (profile);  green / red:
-    blob / peak colours (neither = blue);  numSD default 3.0 for green / red / difference, else 1.5 (singleStructure.py:65-67);
-    profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells."""
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition;  level: atom | residue | domain | symmetry-atom
+    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob and peak) | atom-type (profile) | summary | blob
+    (partition);  green / red: blob / peak colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
+    (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
+    maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default)."""
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % (MODES,))
     key = (mode, None if mode in ("blob", "peak") else level)
     if key not in TABLES:
         raise ValueError("%s mode has the levels %s" % (mode, ", ".join(lv for md, lv in TABLES if md == mode and lv)))
-    options = {"radius": float(radius), "numSD": float(numSD if numSD is not None else (3.0 if green or red or mode == "difference" else 1.5)),
+    options = {"radius": float(radius), "numSD": float(numSD if numSD is not None else (3.0 if green or red or mode in ("difference", "partition") else 1.5)),
                "type": type, "atomMask": atomMask, "optimizedRadii": optimizedRadii, "green": green, "red": red, "shells": int(shells)}
     if mode == "cloud":
         analyzer.aggregateCloud()
