@@ -194,6 +194,30 @@ int pdbeda_bloblist_stats(pdbeda_bloblist *bl, int64_t *n, double *total_density
 /* Voxel membership: crs (N x 3, raw coordinates) grouped by blob in blob order;
  * blob_offsets has count+1 entries. */
 int pdbeda_bloblist_voxels(pdbeda_bloblist *bl, int32_t *crs, int64_t *blob_offsets);
+/* The shape of every blob (no reference counterpart: a reference blob knows its voxel count, total density and two centres, and
+ * nothing about its extent, its elongation or its strongest voxel).  Works on every kind of list (whole-map, either list of a fused
+ * _pm call, pdbeda_sphere_blobs, pdbeda_list_blobs); rows in the list's blob order, the order of pdbeda_bloblist_stats; any output
+ * pointer may be NULL.  Synchronous.
+ * A voxel's density is utils.getPointDensityFromCrs of its raw crs (periodic wrap, 0 where nothing is stored: the density of the
+ * blob sums); w = |density|.  Per blob:
+ *   box_lo[3], box_hi[3]   the smallest and the largest raw c, r, s over the blob's voxels (inclusive);
+ *   extreme_crs[3], extreme   the voxel with the largest w and its signed value; among voxels of equal w the one that comes first in
+ *                          (c, r, s) order of raw crs, c most significant (the c-major order of the peaks): a strict total order, so
+ *                          the answer does not depend on the order of the voxel list;
+ *   s1[3], s2[6]           exact integer sums of the offsets d = crs - box_lo: sum d_c, d_r, d_s and sum d_c d_c, d_c d_r, d_c d_s,
+ *                          d_r d_r, d_r d_s, d_s d_s;
+ *   sw, sw1[3], sw2[6]     the same sums weighted by w: sum w, sum w d, sum w d d'.  w is rounded once to the map's fixed-point quantum
+ *                          (the quantum of the blob sums: <= 2^-36 max |rho|), the products with the integer offsets are taken exactly
+ *                          and the sums are folded as integers and converted once: bit-identical from run to run, within
+ *                          quantum / 2 * d d' per voxel of the exact sum (d d' = 1 for sw).  A one-voxel blob has exact zeros in s1, s2,
+ *                          sw1 and sw2.
+ * Central moments, the conversion to Angstrom and the principal axes are the caller's (a few fp64 operations per row).
+ * A list with no blobs succeeds and touches nothing.  PDBEDA_ERR_ARGUMENT: a NULL or freed list; a list that holds a blob whose box is
+ * 2^15 voxels or more wide along an axis (found by the first of the two passes, before any moment is summed); a sphere / list batch of
+ * 2^24 voxels or more, any list of 2^31 voxels or more (what the integer accumulators hold).  The rows are kept with the list: a second call copies them without a launch.  A failing call leaves the
+ * context usable. */
+int pdbeda_bloblist_moments(pdbeda_bloblist *bl, int32_t *box_lo, int32_t *box_hi, int32_t *extreme_crs, float *extreme,
+                            int64_t *s1, int64_t *s2, double *sw, double *sw1, double *sw2);
 /* Dense labels of a full-map list: int32 [us][ur][uc] over header.uniqueNcrs, blob index or
  * -1.  Computed on first use unless PDBEDA_FLAG_LABELS was given. */
 int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host);

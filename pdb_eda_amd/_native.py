@@ -105,6 +105,7 @@ _SIGS = {
     "pdbeda_bloblist_num_voxels": (_i64, [_p]),
     "pdbeda_bloblist_stats": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p]),
     "pdbeda_bloblist_voxels": (C.c_int, [_p, _p, _p]),
+    "pdbeda_bloblist_moments": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pdbeda_bloblist_labels": (C.c_int, [_p, _p]),
     "pdbeda_bloblist_free": (C.c_int, [_p]),
     "pdbeda_bloblist_counters": (C.c_int, [_p, _p]),
@@ -384,6 +385,17 @@ class BlobList(object):
     def voxels_of(self, i):
         crs, off = self.voxels()
         return crs[off[i]:off[i + 1]]
+
+    def moments(self):
+        """pdbeda_bloblist_moments: per blob, in list order, ``boxLo`` / ``boxHi`` / ``extremeCrs`` (n x 3 int32), ``extreme`` (float32),
+        the exact offset sums ``s1`` (n x 3) / ``s2`` (n x 6, int64) and the |density|-weighted ``sw`` (n), ``sw1`` (n x 3), ``sw2`` (n x 6)."""
+        n = len(self)
+        out = {"boxLo": np.zeros((n, 3), np.int32), "boxHi": np.zeros((n, 3), np.int32), "extremeCrs": np.zeros((n, 3), np.int32),
+               "extreme": np.zeros(n, np.float32), "s1": np.zeros((n, 3), np.int64), "s2": np.zeros((n, 6), np.int64),
+               "sw": np.zeros(n, np.float64), "sw1": np.zeros((n, 3), np.float64), "sw2": np.zeros((n, 6), np.float64)}
+        self._ctx.check(self._ctx._lib.pdbeda_bloblist_moments(self._h, *[_ptr(out[k]) for k in ("boxLo", "boxHi", "extremeCrs", "extreme", "s1", "s2", "sw", "sw1", "sw2")]),
+                        "pdbeda_bloblist_moments")
+        return out
 
     def labels(self, shape):
         out = np.zeros(shape, dtype=np.int32)

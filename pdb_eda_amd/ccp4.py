@@ -427,12 +427,12 @@ class DensityMatrix(object):
         """ref ccp4.py:463-473: threshold the non-repeating box and cluster (None for cutoff == 0)."""
         if np.float32(cutoff) == 0:
             return None
-        return DensityBlob.listFromDevice(self._map.full_blobs(cutoff), self)
+        return DensityBlob.listFromDevice(self._map.full_blobs(cutoff), self, wholeMap=True)
 
     def createFullBlobLists(self, cutoff):
         """Fused green (+cutoff) and red (-cutoff) lists from ONE pass over the grid."""
         green, red = self._map.full_blobs_pm(abs(cutoff), -abs(cutoff))
-        return DensityBlob.listFromDevice(green, self), DensityBlob.listFromDevice(red, self)
+        return DensityBlob.listFromDevice(green, self, wholeMap=True), DensityBlob.listFromDevice(red, self, wholeMap=True)
 
     def createBlobList(self, crsList):
         """ref ccp4.py:475-485: cluster an explicit (raw) crs list into blobs."""
@@ -517,13 +517,94 @@ class DevicePeaks(collections.abc.Sequence):
         return "DevicePeaks(%d peaks)" % len(self)
 
 
+SHAPE_COLUMNS = ("boxLo", "boxHi", "boxExtent", "onBorder", "extremeCrs", "extremeXyz", "extremeDensity", "weightedCentroid", "secondMomentCrs",
+                 "weightedSecondMomentCrs", "secondMomentXyz", "weightedSecondMomentXyz", "principalLengths", "principalAxes", "weightedPrincipalLengths",
+                 "weightedPrincipalAxes", "anisotropy", "equivalentRadii")
+_PAIRS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))      # the order of the six second sums: cc cr cs rr rs ss
+
+
+def _symmetric(six):
+    """(n, 6) upper triangles in ``_PAIRS`` order -> (n, 3, 3) symmetric tensors."""
+    out = np.zeros((len(six), 3, 3), dtype=np.float64)
+    for k, (i, j) in enumerate(_PAIRS):
+        out[:, i, j] = out[:, j, i] = six[:, k]
+    return out
+
+
+def _principal(tensor):
+    """Batched ``eigh`` of (n, 3, 3) symmetric tensors: (lengths (n, 3) = sqrt of the principal variances, descending; axes (n, 3, 3), row k the
+    unit vector of length k).  A tensor that holds a NaN (a blob without density has no weighted moments) gives NaN rows."""
+    lengths, axes = np.full((len(tensor), 3), np.nan), np.full((len(tensor), 3, 3), np.nan)
+    ok = np.isfinite(tensor).all(axis=(1, 2))
+    if ok.any():
+        values, vectors = np.linalg.eigh(tensor[ok])                  # ascending; vectors in columns
+        lengths[ok] = np.sqrt(np.maximum(values[:, ::-1], 0.0))       # (a variance of a flat blob may come out as -1e-17)
+        axes[ok] = np.transpose(vectors, (0, 2, 1))[:, ::-1, :]
+    return lengths, axes
+
+
+def blobShapeFinish(header, numVoxels, moments, wholeMap=False):
+    """The shape columns of a blob list from the integer / fixed-point sums of ``pdbeda_bloblist_moments`` (``BlobList.moments()``) and the
+    blobs' voxel counts -- a few vectorised fp64 operations per row, no voxel is touched.  A dict of arrays, one row per blob:
+
+    ``boxLo`` / ``boxHi`` (raw crs, inclusive), ``boxExtent`` (the box's edges in A along the column, row and section axes: whole voxels,
+    (hi - lo + 1) steps), ``onBorder`` (whole-map lists: the box touches a face of the non-repeating box ``header.uniqueNcrs`` -- the stored
+    box begins at ``crsStart`` -- so the blob may go on in the next cell; False for every other list);
+    ``extremeCrs`` / ``extremeXyz`` / ``extremeDensity`` (the voxel of largest |density| and its signed value);
+    ``weightedCentroid`` (xyz of box_lo + sum w d / sum w, w = |density|);
+    ``secondMomentCrs`` / ``weightedSecondMomentCrs`` ((n, 3, 3) central second moments of the voxel positions in voxels: the geometric one
+    is (n sum d d' - sum d sum d') / n^2 with the numerator formed in exact integers) and the same in A^2, ``secondMomentXyz`` /
+    ``weightedSecondMomentXyz`` = M C M^T with M the linear part of ``crs2xyzCoord`` (permuted axes and skewed cells included);
+    ``principalLengths`` (RMS extent along the principal axes in A, descending) and ``principalAxes`` (row k: unit vector of length k) of
+    the geometric tensor, ``weightedPrincipalLengths`` / ``weightedPrincipalAxes`` of the weighted one;
+    ``anisotropy`` = 1 - l3 / l1 (0 for a single voxel) and ``equivalentRadii`` = sqrt(5) lengths: the semi-axes of the solid ellipsoid with
+    these moments."""
+    n = np.asarray(numVoxels, dtype=np.int64)
+    count = len(n)
+    s1, s2 = np.asarray(moments["s1"], dtype=np.int64).reshape(count, 3), np.asarray(moments["s2"], dtype=np.int64).reshape(count, 6)
+    lo, hi = np.asarray(moments["boxLo"]).reshape(count, 3), np.asarray(moments["boxHi"]).reshape(count, 3)
+    # n sum d d' - sum d sum d' in exact integers: int64 while every product stays below 2^62, Python integers beyond
+    exact = np.int64 if count == 0 or (float(n.max()) * float(s2.max()) < 2.0 ** 62 and float(s1.max()) ** 2 < 2.0 ** 62) else object
+    ne, s1e, s2e = n.astype(exact), s1.astype(exact), s2.astype(exact)
+    numerator = np.stack([ne * s2e[:, k] - s1e[:, i] * s1e[:, j] for k, (i, j) in enumerate(_PAIRS)], axis=1) if count else np.zeros((0, 6))
+    nn = (ne * ne).astype(np.float64) if count else np.zeros(0)
+    geometric = _symmetric(numerator.astype(np.float64) / nn[:, None])
+    sw = np.asarray(moments["sw"], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.asarray(moments["sw1"], dtype=np.float64).reshape(count, 3) / sw[:, None]
+        second = np.asarray(moments["sw2"], dtype=np.float64).reshape(count, 6) / sw[:, None]
+    weighted = _symmetric(np.stack([second[:, k] - mean[:, i] * mean[:, j] for k, (i, j) in enumerate(_PAIRS)], axis=1) if count else np.zeros((0, 6)))
+    M = (header.crs2xyz_array(np.eye(3)) - header.crs2xyz_array(np.zeros((1, 3)))).T          # column k: the xyz step of crs axis k
+    geometricXyz, weightedXyz = np.einsum("ij,njk,lk->nil", M, geometric, M), np.einsum("ij,njk,lk->nil", M, weighted, M)
+    lengths, axes = _principal(geometricXyz)
+    weightedLengths, weightedAxes = _principal(weightedXyz)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        anisotropy = np.where(lengths[:, 0] > 0, 1.0 - lengths[:, 2] / lengths[:, 0], 0.0)
+    unique = np.asarray(header.uniqueNcrs, dtype=np.int64)
+    border = ((lo <= 0) | (hi >= unique - 1)).any(axis=1) if wholeMap else np.zeros(count, dtype=bool)
+    extremeCrs = np.asarray(moments["extremeCrs"]).reshape(count, 3)
+    return {"boxLo": lo, "boxHi": hi, "boxExtent": (hi.astype(np.int64) - lo + 1) * np.linalg.norm(M, axis=0), "onBorder": border,
+            "extremeCrs": extremeCrs, "extremeXyz": header.crs2xyz_array(extremeCrs).reshape(count, 3),
+            "extremeDensity": np.asarray(moments["extreme"], dtype=np.float64), "weightedCentroid": header.crs2xyz_array(lo + mean).reshape(count, 3),
+            "secondMomentCrs": geometric, "weightedSecondMomentCrs": weighted, "secondMomentXyz": geometricXyz, "weightedSecondMomentXyz": weightedXyz,
+            "principalLengths": lengths, "principalAxes": axes, "weightedPrincipalLengths": weightedLengths, "weightedPrincipalAxes": weightedAxes,
+            "anisotropy": anisotropy, "equivalentRadii": np.sqrt(5.0) * lengths}
+
+
 class _DeviceBlobSegment(object):
     """One device blob list behind a ``DeviceBlobs`` sequence: its statistics columns and, once somebody asked, its objects."""
 
-    def __init__(self, bl, densityMatrix):
-        self.bl, self.densityMatrix = bl, densityMatrix
+    def __init__(self, bl, densityMatrix, wholeMap=False):
+        self.bl, self.densityMatrix, self.wholeMap = bl, densityMatrix, wholeMap
         self.stats = bl.stats()
         self.blobs = None
+        self._shape = None
+
+    def shape(self):
+        """The shape columns of this list (``blobShapeFinish`` of ONE ``pdbeda_bloblist_moments`` call), made on first use."""
+        if self._shape is None:
+            self._shape = blobShapeFinish(self.densityMatrix.header, self.stats["n"], self.bl.moments(), self.wholeMap)
+        return self._shape
 
     def __len__(self):
         return len(self.stats["n"])
@@ -538,7 +619,7 @@ class _DeviceBlobSegment(object):
             for i, (centroid, center, total, volume, n, key) in enumerate(columns):
                 blob = new(DensityBlob)                          # same fields as __init__ sets, without a call per field
                 blob.__dict__ = {"centroid": centroid, "coordCenter": center, "totalDensity": total, "volume": volume, "_crsList": None, "_numVoxels": n,
-                                 "_list": bl, "_index": i, "densityMatrix": densityMatrix, "firstKey": key}
+                                 "_list": bl, "_index": i, "densityMatrix": densityMatrix, "firstKey": key, "_segment": self}
                 out.append(blob)
             self.blobs = out
         return self.blobs
@@ -599,6 +680,14 @@ class DeviceBlobs(collections.abc.Sequence):
             base += len(crs)
         return np.concatenate([crs for crs, off in parts]), np.concatenate(offsets)
 
+    def shapeColumns(self):
+        """The shape of every blob, in list order: the ``SHAPE_COLUMNS`` of ``blobShapeFinish`` as arrays, from ONE device call per device
+        list (``pdbeda_bloblist_moments`` in include/pdbeda.h has the contract) -- no voxel list comes to the host."""
+        if not self._segments:
+            return {k: np.zeros(0) for k in SHAPE_COLUMNS}
+        parts = [seg.shape() for seg in self._segments]
+        return parts[0] if len(parts) == 1 else {k: np.concatenate([part[k] for part in parts]) for k in SHAPE_COLUMNS}
+
     def columns(self):
         """{"centroid", "totalDensity", "n", "volume"} of all blobs as arrays -- or None once any of the objects exists (they
         are ordinary mutable objects: from then on they are the truth)."""
@@ -631,10 +720,18 @@ class DensityBlob(object):
             self.atoms = atoms
 
     @classmethod
-    def listFromDevice(cls, bl, densityMatrix):
+    def listFromDevice(cls, bl, densityMatrix, wholeMap=False):
         """The blobs of a device list, in its order: a sequence that makes the DensityBlob objects when somebody reads one
         (``DeviceBlobs``) -- the tables over thousands of blobs read the list's columns and never touch an object."""
-        return DeviceBlobs([_DeviceBlobSegment(bl, densityMatrix)])
+        return DeviceBlobs([_DeviceBlobSegment(bl, densityMatrix, wholeMap)])
+
+    def _shapeValue(self, name):
+        segment = self.__dict__.get("_segment")
+        if segment is None or self._list is None:
+            raise AttributeError("%s is known only for a blob that comes from a device list (createFullBlobList, findAberrantBlobs, createBlobList) "
+                                 "and has not been merged since" % name)
+        value = segment.shape()[name][self._index]
+        return value.tolist() if isinstance(value, np.ndarray) else value.item()
 
     @property
     def crsList(self):
@@ -707,3 +804,12 @@ class DensityBlob(object):
         """ref ccp4.py:588-594."""
         return DensityBlob(self.centroid, self.coordCenter, self.totalDensity, self.volume, self.crsList,
                            self.densityMatrix, self.atoms.copy())
+
+
+def _shapeAttribute(name):
+    return property(lambda self: self._shapeValue(name), doc="``%s`` of ``blobShapeFinish`` for this blob (read-only; made on first use for the whole list)." % name)
+
+
+for _name in SHAPE_COLUMNS:
+    setattr(DensityBlob, _name, _shapeAttribute(_name))
+del _name

@@ -31,6 +31,7 @@
 #include "pdbeda_peaks.h"
 #include "pdbeda_profiles.h"
 #include "pdbeda_partition.h"
+#include "pdbeda_blobshape.h"
 
 using namespace pdbeda;
 
@@ -214,6 +215,11 @@ struct pdbeda_bloblist {
     std::vector<int64_t> spec_n, spec_key;
     std::vector<double> spec_total, spec_centroid, spec_center, spec_volume;
     std::vector<int32_t> spec_group;
+    // pdbeda_bloblist_moments: the rows of THIS list, made by the first call and kept until the list is freed
+    bool shape_done = false;
+    std::vector<int32_t> shape_i;      // [blobs][10]: box_lo, box_hi, extreme crs, bits of the extreme value
+    std::vector<int64_t> shape_l;      // [blobs][9]: sum d, sum d d'
+    std::vector<double> shape_d;       // [blobs][10]: sum w, sum w d, sum w d d'
 };
 
 static const int N_PARTIAL = 2048;
@@ -1771,6 +1777,98 @@ extern "C" int pdbeda_bloblist_voxels(pdbeda_bloblist *bl, int32_t *crs, int64_t
     return PDBEDA_OK;
 }
 
+// ------------------------------------------------------------------------------------
+// Blob shape descriptors (pdbeda_blobshape.h; no reference counterpart; the contract: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// The launch graph of a list's FIRST call: two fills (box records INT_MIN, sums records 0), k_blobshape_box, k_blobshape_widths and a wait
+// for the widest box (a list with a box of 2^15 voxels or more is refused here, in front of the moment launches); k_blobshape_sums,
+// k_blobshape_finish, and the three row tables in one pack and one wait.  The scratch arena goes back to the pool in stream order whatever
+// happens; results are registered for delivery (d2h_many) only behind the last launch.
+static int list_moments_compute(pdbeda_bloblist *bl) {
+    const int64_t nv = pdbeda_bloblist_num_voxels(bl);      // (resolves the counts and materialises the voxel lists)
+    if (nv < 0) return (int)nv;
+    pdbeda_ctx *ctx = bl->ctx;
+    const int64_t cnt = bl->rank_hi - bl->rank_lo;
+    if (cnt == 0 || nv == 0) { bl->shape_done = true; return PDBEDA_OK; }
+    // What the accumulators hold: F = fix_of(|rho|) < 2^39 (map_fix_mul keeps 2^22 max |rho| inside 61 bits).  The low limbs of the two-limb sums are
+    // below 2^32 per voxel and are read as signed 64-bit: fewer than 2^31 voxels in the list.  sum F is ONE 64-bit word, and the high limb of F d d' is
+    // below 2^37 per voxel: a whole-map blob counts every stored voxel at most once (nothing wraps in the unique box), so the map's sum |rho| < 2^61
+    // bounds sum F and 2^61 * 2^30 / 2^32 the high limbs; a sphere / list batch may meet a stored voxel again through the periodic wrap, so only its
+    // voxel count bounds it: below 2^24 voxels sum F < 2^63 and the high limbs < 2^61.
+    if (cnt >= (1ll << 31) || nv >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a list of 2^31 blobs or voxels, or more");
+    if (!bl->whole_map && nv >= (1ll << 24)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a sphere / list batch of 2^24 voxels or more");
+    pdbeda_map *m = bl->map;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = map_fix_mul(m)) return rc;      // (known since the labelling call, unless the map was invalidated meanwhile)
+    pdbeda_bloblist *ow = owner_of(bl);
+    const size_t nb = (size_t)cnt;
+    const size_t bytes = 2 * align_up(4 * (size_t)nv) + align_up(4 * BS_BOX * nb) + align_up(8 * BS_REC * nb) + align_up(64) + align_up(40 * nb) + align_up(72 * nb) +
+                         align_up(80 * nb);
+    Arena arena;
+    if (int rc = arena_get(ctx, bytes, &arena)) return rc;
+    auto run = [&]() -> int {
+        Carver cv(arena.base);
+        BlobShapeArgs a;
+        a.geom = m->geom_dev; a.dens = m->dens;
+        a.crs = ow->crs_dev; a.off = ow->offsets_dev + bl->rank_lo; a.cnt = cnt;
+        a.park_rho = cv.take<float>((size_t)nv); a.park_blob = cv.take<int32_t>((size_t)nv);
+        a.box = cv.take<int32_t>(BS_BOX * nb); a.rec = cv.take<unsigned long long>(BS_REC * nb);
+        a.fix_mul = m->fix_mul;
+        unsigned long long *d_widest = cv.take<unsigned long long>(8);
+        int32_t *d_i = cv.take<int32_t>(10 * nb);
+        long long *d_l = cv.take<long long>(9 * nb);
+        double *d_d = cv.take<double>(10 * nb);
+        hipStream_t st = ctx->stream;
+        const unsigned chunks = (unsigned)((nv + BS_CHUNK - 1) / BS_CHUNK);
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)a.box, (int)0x80000000u, BS_BOX * nb, st));
+        HIP_TRY(ctx, hipMemsetAsync(a.rec, 0, (size_t)((char *)(d_widest + 8) - (char *)a.rec), st));      // (the sums records and the widest box behind them)
+        { PROF(ctx, "k_blobshape_box"); hipLaunchKernelGGL(k_blobshape_box, dim3(chunks), dim3(256), 0, st, a); }
+        { PROF(ctx, "k_blobshape_widths"); hipLaunchKernelGGL(k_blobshape_widths, dim3(grid_for(cnt, 256, 1024)), dim3(256), 0, st, a.box, cnt, d_widest); }
+        HIP_TRY(ctx, hipGetLastError());
+        unsigned long long widest = 0;
+        HIP_TRY(ctx, d2h(ctx, &widest, d_widest, 8));
+        HIP_TRY(ctx, ctx_sync(ctx));
+        if (widest >= (unsigned long long)BS_MAX_WIDTH)
+            return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a blob's box is %llu voxels wide (the limit is %d)", widest, BS_MAX_WIDTH - 1);
+        { PROF(ctx, "k_blobshape_sums"); hipLaunchKernelGGL(k_blobshape_sums, dim3(chunks), dim3(256), 0, st, a); }
+        { PROF(ctx, "k_blobshape_finish"); hipLaunchKernelGGL(k_blobshape_finish, dim3(grid_for(cnt, 256)), dim3(256), 0, st, a.box, a.rec, cnt, 1.0 / m->fix_mul, d_i, d_l, d_d); }
+        HIP_TRY(ctx, hipGetLastError());
+        bl->shape_i.resize(10 * nb); bl->shape_l.resize(9 * nb); bl->shape_d.resize(10 * nb);
+        const D2HItem rows[3] = {{bl->shape_i.data(), d_i, 40 * nb}, {bl->shape_l.data(), d_l, 72 * nb}, {bl->shape_d.data(), d_d, 80 * nb}};
+        HIP_TRY(ctx, d2h_many(ctx, rows, 3));
+        HIP_TRY(ctx, ctx_sync(ctx));
+        return PDBEDA_OK;
+    };
+    const int rc = run();
+    arena_put(ctx, arena);      // (stream order: whatever is still queued on a failed call runs before the arena's next user)
+    if (rc == PDBEDA_OK) bl->shape_done = true;
+    return rc;
+}
+
+extern "C" int pdbeda_bloblist_moments(pdbeda_bloblist *bl, int32_t *box_lo, int32_t *box_hi, int32_t *extreme_crs, float *extreme, int64_t *s1, int64_t *s2,
+                                       double *sw, double *sw1, double *sw2) {
+    if (!bl || bl->freed) return PDBEDA_ERR_ARGUMENT;
+    if (bl->ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    if (!bl->shape_done)
+        if (int rc = list_moments_compute(bl)) return rc;
+    const size_t cnt = bl->shape_l.size() / 9;
+    for (size_t b = 0; b < cnt; ++b) {
+        const int32_t *ri = bl->shape_i.data() + 10 * b;
+        const int64_t *rl = bl->shape_l.data() + 9 * b;
+        const double *rd = bl->shape_d.data() + 10 * b;
+        if (box_lo) memcpy(box_lo + 3 * b, ri, 12);
+        if (box_hi) memcpy(box_hi + 3 * b, ri + 3, 12);
+        if (extreme_crs) memcpy(extreme_crs + 3 * b, ri + 6, 12);
+        if (extreme) memcpy(extreme + b, ri + 9, 4);
+        if (s1) memcpy(s1 + 3 * b, rl, 24);
+        if (s2) memcpy(s2 + 6 * b, rl + 3, 48);
+        if (sw) sw[b] = rd[0];
+        if (sw1) memcpy(sw1 + 3 * b, rd + 1, 24);
+        if (sw2) memcpy(sw2 + 6 * b, rd + 4, 48);
+    }
+    return PDBEDA_OK;
+}
+
 extern "C" int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host) {
     if (!bl || bl->freed || !labels_host) return PDBEDA_ERR_ARGUMENT;
     if (!bl->whole_map) return fail(bl->ctx, PDBEDA_ERR_STATE, "dense labels exist only for whole-map blob lists");
@@ -1809,6 +1907,8 @@ extern "C" int pdbeda_bloblist_free(pdbeda_bloblist *bl) {
     pdbeda_ctx *ctx = bl->ctx;
     bl->freed = true;
     ctx->live_handles--;
+    bl->shape_done = false;      // (the rows go with the list, also while the other list of a fused call keeps the struct alive)
+    std::vector<int32_t>().swap(bl->shape_i); std::vector<int64_t>().swap(bl->shape_l); std::vector<double>().swap(bl->shape_d);
     pdbeda_bloblist *ow = owner_of(bl);
     pdbeda_bloblist *other = bl->sibling;
     const bool other_alive = other && !other->freed;

@@ -354,6 +354,9 @@ class DensityAnalysis(object):
                             'atom_name', 'atom_symmetry', 'atom_xyz', 'centroid_xyz']
     peakStatisticsHeader = ['distance_to_atom', 'sign', 'height_in_sigma', 'height_in_electrons_per_A3', 'blob_index', 'on_border', 'chain', 'residue_number',
                             'residue_name', 'atom_name', 'symmetry', 'atom_xyz', 'peak_xyz']
+    blobShapeHeader = ['blob_index', 'num_voxels', 'volume', 'sign', 'electrons_of_discrepancy', 'extreme_in_sigma', 'extreme_in_electrons_per_A3', 'extreme_xyz',
+                       'principal_length_1', 'principal_length_2', 'principal_length_3', 'anisotropy', 'box_extent', 'on_border', 'distance_to_atom', 'chain',
+                       'residue_number', 'residue_name', 'atom_name', 'atom_symmetry', 'atom_xyz']
     regionDensityHeader = ["actual_significant_regional_density", "num_electrons_actual_significant_regional_density"]
     atomRegionDensityHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy"] + regionDensityHeader
     symmetryAtomRegionDensityHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "symmetry", "atom_xyz", "fully_within_density_map"] + regionDensityHeader
@@ -874,6 +877,42 @@ class DensityAnalysis(object):
         return self._rows(list(dist), sign, height / std, height / ratio, blob, border,
                           (chain, rows), (number, rows), (resname, rows), (cols.name if isinstance(cols.name, (list, tuple)) else list(cols.name), rows),
                           symmetry, coords, peak_xyz)
+
+    # ---- blob shape statistics (no reference counterpart; built like the two tables above) ------
+    def calculateBlobShapeStatistics(self, blobList):
+        """One row per blob of a device list (``blobShapeHeader``): size, total density, the extreme voxel (in units of the map's standard deviation
+        and in electrons per cubic Angstrom), the principal RMS lengths in A, the anisotropy 1 - l3 / l1, the box extent along the map axes,
+        whether the box touches the non-repeating box, and the symmetry atom nearest to the EXTREME voxel."""
+        symmetryAtoms = self.symmetryAtoms
+        symmetryAtomCoords = self.symmetryAtomCoords
+        if not self.densityElectronRatio:
+            raise RuntimeError("Failed to calculate densityElectronRatio, probably due to total aggregated electrons less than the minimum.")
+        ratio = self.densityElectronRatio
+        if not isinstance(blobList, ccp4.DeviceBlobs):
+            raise ValueError("blobList must be what createFullBlobList / findAberrantBlobs / createBlobList returned")
+        if not blobList:
+            return []
+        if len(symmetryAtomCoords) == 0:
+            raise ValueError("XB must be a 2-dimensional array.")       # (the blob table's failure for a file without operators)
+        shape = blobList.shapeColumns()
+        segments = blobList._segments
+        num_voxels, volume, total = (np.concatenate([np.asarray(seg.stats[k]) for seg in segments]) for k in ("n", "volume", "totalDensity"))
+        std = np.concatenate([np.full(len(seg), seg.densityMatrix.stdDensity) for seg in segments])
+        extreme = np.asarray(shape["extremeDensity"], dtype=np.float64)
+        extreme_xyz = np.ascontiguousarray(shape["extremeXyz"], dtype=np.float64)
+        idx, dist = self.densityObj._ctx.nearest_atom(extreme_xyz, np.asarray(symmetryAtomCoords, dtype=np.float64))
+        rows, symmetry, coords = symmetryAtoms.columns(idx)
+        cols = _structure.columns(self.biopdbObj)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        chain, number, resname = (cols.atom_lists(which) for which in ("chain", "number", "resname"))
+        lengths = np.asarray(shape["principalLengths"], dtype=np.float64)
+        sign = np.where(total >= 0, '+', '-').tolist()
+        return self._rows(np.arange(len(num_voxels), dtype=np.int64), np.asarray(num_voxels, dtype=np.int64), np.asarray(volume, dtype=np.float64), sign,
+                          np.abs(total / ratio), extreme / std, extreme / ratio, extreme_xyz, np.ascontiguousarray(lengths[:, 0]), np.ascontiguousarray(lengths[:, 1]),
+                          np.ascontiguousarray(lengths[:, 2]), np.asarray(shape["anisotropy"], dtype=np.float64), np.ascontiguousarray(shape["boxExtent"], dtype=np.float64),
+                          np.asarray(shape["onBorder"], dtype=np.bool_), list(dist),
+                          (chain, rows), (number, rows), (resname, rows), (cols.name if isinstance(cols.name, (list, tuple)) else list(cols.name), rows),
+                          symmetry, coords)
 
     # ---- Fo / Fc maps, RSCC / RSR (ref densityAnalysis.py:426-446, 783-882) -------------------
     @property

@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape")
 
 
 def numpyConverter(obj):
@@ -66,6 +66,20 @@ def _peakTable(analyzer, o):
         lists = [densObj.findPeaks(cut, densObj.createFullBlobList(cut))]
     table = [row for peaks in lists for row in analyzer.calculateAtomSpecificPeakStatistics(peaks)]
     return _plainColumns(table, listColumns=(10,), floatColumns=(11, 12))
+
+
+def _shapeTable(analyzer, o):
+    """shape sub-mode (no reference counterpart): extent, elongation and strongest voxel of the blobs of the blob sub-mode's lists -- the green and / or
+    red Fo-Fc blobs, else the blue 2Fo-Fc blobs -- each with the symmetry atom nearest to its strongest voxel."""
+    diffObj, densObj, numSD = analyzer.diffDensityObj, analyzer.densityObj, o["numSD"]
+    if o["green"] and o["red"]:          # one fused pass over the Fo-Fc grid gives both lists
+        lists = diffObj.createFullBlobLists(diffObj.meanDensity + numSD * diffObj.stdDensity)
+    elif o["green"] or o["red"]:
+        lists = [diffObj.createFullBlobList((1 if o["green"] else -1) * (diffObj.meanDensity + numSD * diffObj.stdDensity))]
+    else:
+        lists = [densObj.createFullBlobList(densObj.meanDensity + numSD * densObj.stdDensity)]
+    table = [row for blobs in lists for row in analyzer.calculateBlobShapeStatistics(blobs)]
+    return _plainColumns(table, listColumns=(19,), floatColumns=(7, 12, 20))
 
 
 def _partitionBlobTable(analyzer, o):
@@ -121,6 +135,7 @@ TABLES = {
                                       lambda an, o: _plainColumns(an.calculateSymmetryAtomRegionDiscrepancies(o["radius"], o["numSD"], o["type"]), **_SYM)),
     ("blob", None): (lambda an: _DA.blobStatisticsHeader, _blobTable),
     ("peak", None): (lambda an: _DA.peakStatisticsHeader, _peakTable),
+    ("shape", None): (lambda an: _DA.blobShapeHeader, _shapeTable),
     # (no reference counterpart; the shell columns are lists, carried as the peak table's list columns are)
     ("profile", "atom"): (lambda an: _DA.atomRadialProfileHeader, lambda an, o: an.calculateAtomRadialProfiles(o["radius"], o["shells"], o["numSD"], o["type"])),
     ("profile", "atom-type"): (lambda an: _DA.atomTypeRadialProfileHeader, lambda an, o: an.atomTypeRadialProfiles(o["radius"], o["shells"], o["numSD"])),
@@ -138,14 +153,14 @@ def rows(analyzer, mode, level="atom", radius=3.5, numSD=None, type="", atomMask
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile | partition;  level: atom | residue | domain | symmetry-atom
-    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob and peak) | atom-type (profile) | summary | blob
-    (partition);  green / red: blob / peak colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape;  level: atom | residue | domain | symmetry-atom
+    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak and shape) | atom-type (profile) | summary | blob
+    (partition);  green / red: blob / peak / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
     (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
     maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default)."""
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % (MODES,))
-    key = (mode, None if mode in ("blob", "peak") else level)
+    key = (mode, None if mode in ("blob", "peak", "shape") else level)
     if key not in TABLES:
         raise ValueError("%s mode has the levels %s" % (mode, ", ".join(lv for md, lv in TABLES if md == mode and lv)))
     options = {"radius": float(radius), "numSD": float(numSD if numSD is not None else (3.0 if green or red or mode in ("difference", "partition") else 1.5)),
