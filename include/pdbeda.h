@@ -179,7 +179,10 @@ int pdbeda_sphere_blobs(pdbeda_map *map, const double *xyz, const float *radii, 
 
 /* DensityMatrix.createBlobList(crsList) (ccp4.py:475-485) on explicit raw voxel sets:
  * voxels [group_offsets[g], group_offsets[g+1]) of crs (n x 3) form group g (duplicates
- * collapse, as in DensityBlob's set).  Used for DensityBlob.merge / fromCrsList and for
+ * collapse, as in DensityBlob's set; voxels that are periodic images of each other stay
+ * distinct: connectivity is on raw crs).  A group may be empty and then has no blob.  Blobs
+ * come back sorted by (group, first_key), first_key strictly increasing inside a group: the
+ * order of pdbeda_sphere_blobs.  Used for DensityBlob.merge / fromCrsList and for
  * the residue / domain cloud unions of aggregateCloud (densityAnalysis.py:646-708). */
 int pdbeda_list_blobs(pdbeda_map *map, const int32_t *crs, int64_t n, const int64_t *group_offsets,
                       int64_t n_groups, pdbeda_bloblist **out);
