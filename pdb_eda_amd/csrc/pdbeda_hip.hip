@@ -393,6 +393,8 @@ static void arena_put(pdbeda_ctx *ctx, Arena &a) {
     }
 }
 
+// The rule: an arena's layout and its size come from ONE carve -- a callable that takes a Carver & and names every piece.  arena_carve() (or
+// with_scratch() on top of it) runs the carve on a null base for the size and again on the arena's base; never size an arena by hand.
 struct Carver {
     char *base;
     size_t off = 0;
@@ -402,7 +404,25 @@ struct Carver {
         off += align_up(n * sizeof(T));
         return p;
     }
+    template <typename T> void take(T *&p, size_t n) { p = take<T>(n); }      // (T from the pointer it fills)
 };
+
+// An arena sized by `carve` and laid out by the same carve; the caller keeps it (and puts it back).  A second pass that does not end where the
+// first did -- the carve read something that changed in between -- leaves nothing behind: the arena is back in the pool, nothing was launched.
+template <typename Carve>
+static int arena_carve(pdbeda_ctx *ctx, const char *site, Arena *out, Carve carve) {
+    Carver size(nullptr);
+    carve(size);
+    if (int rc = arena_get(ctx, size.off, out)) return rc;
+    Carver cv(out->base);
+    carve(cv);
+    if (cv.off != size.off || cv.off > out->cap) {
+        const size_t cap = out->cap;
+        arena_put(ctx, *out);
+        return fail(ctx, PDBEDA_ERR_STATE, "%s: scratch carve ends at %zu, sized %zu (arena of %zu)", site, cv.off, size.off, cap);
+    }
+    return 0;
+}
 
 static inline unsigned grid_for(int64_t n, int block, int64_t cap = 1 << 20) {
     int64_t g = (n + block - 1) / block;
@@ -510,17 +530,24 @@ static const T *pinned_in(pdbeda_ctx *ctx, const T *src, size_t count) {
     return reinterpret_cast<const T *>(p);
 }
 
-template <typename Fn>
-static int with_scratch(pdbeda_ctx *ctx, size_t bytes, Fn fn) {
+// Scratch for one call, laid out by `carve` (see Carver), which fills the caller's pointers; `fn` uses them; the stream is drained before the arena goes back.
+template <typename Carve, typename Fn>
+static int with_scratch(pdbeda_ctx *ctx, const char *site, Carve carve, Fn fn) {
     Arena a;
-    int rc = arena_get(ctx, bytes, &a);
+    int rc = arena_carve(ctx, site, &a, carve);
     if (rc) return rc;
-    rc = fn(a.base);
+    rc = fn();
     hipError_t e = ctx_sync(ctx);
     arena_put(ctx, a);
     if (rc) return rc;
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "stream sync: %s", hipGetErrorString(e));
     return 0;
+}
+// One plain buffer of `bytes`: nothing to lay out.
+template <typename Fn>
+static int with_scratch(pdbeda_ctx *ctx, size_t bytes, Fn fn) {
+    char *base = nullptr;
+    return with_scratch(ctx, "scratch", [&](Carver &cv) { cv.take(base, bytes); }, [&]() -> int { return fn(base); });
 }
 
 // ------------------------------------------------------------------------------------
@@ -699,13 +726,11 @@ static int map_create(pdbeda_ctx *ctx, const float *host, const float *dev, cons
     m->n_vox = (int64_t)geom->ncrs[0] * geom->ncrs[1] * geom->ncrs[2];
     if (m->n_vox >= (1ll << 32)) { delete m; return fail(ctx, PDBEDA_ERR_ARGUMENT, "grids of 2^32 voxels or more are not supported"); }
     if (dev && ((uintptr_t)dev & 15u) != 0) { delete m; return fail(ctx, PDBEDA_ERR_ARGUMENT, "device density pointer must be 16-byte aligned"); }
-    rc = arena_get(ctx, align_up(sizeof(Geom)) + (host ? align_up(sizeof(float) * (size_t)m->n_vox) : 0), &m->arena);
+    float *d = nullptr;
+    rc = arena_carve(ctx, "map_create", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); if (host) cv.take(d, (size_t)m->n_vox); });
     if (rc) { delete m; return rc; }
-    Carver cv(m->arena.base);
-    m->geom_dev = cv.take<Geom>(1);
     hipError_t e = hipSuccess;
     if (host) {
-        float *d = cv.take<float>((size_t)m->n_vox);
         m->dens = d;
         m->own_dens = true;
         // (measured, round 5: the same grid through the upload engine -- readers memcpy chunks into their pinned slots -- takes twice as long as the runtime's
@@ -886,12 +911,10 @@ static int upload_file_impl(pdbeda_ctx *ctx, const char *path, int64_t offset, i
     pdbeda_map *m = new pdbeda_map();
     m->ctx = ctx;
     int rc = fill_geom(ctx, geom, &m->geom);
-    if (rc == 0) rc = arena_get(ctx, align_up(sizeof(Geom)) + align_up(need), &m->arena);
+    float *d = nullptr;
+    if (rc == 0) rc = arena_carve(ctx, "map upload from file", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)n_vox); });
     if (rc) { close(fd); delete m; return rc; }
     m->n_vox = n_vox;
-    Carver cv(m->arena.base);
-    m->geom_dev = cv.take<Geom>(1);
-    float *d = cv.take<float>((size_t)n_vox);
     m->dens = d;
     m->own_dens = true;
     const char *why = nullptr;
@@ -957,11 +980,9 @@ extern "C" int pdbeda_map_combine(pdbeda_map *a, pdbeda_map *b, double alpha, pd
     m->ctx = ctx;
     m->geom = a->geom;
     m->n_vox = a->n_vox;
-    int rc = arena_get(ctx, align_up(sizeof(Geom)) + align_up(sizeof(float) * (size_t)m->n_vox), &m->arena);
+    float *d = nullptr;
+    int rc = arena_carve(ctx, "map combine", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)m->n_vox); });
     if (rc) { delete m; return rc; }
-    Carver cv(m->arena.base);
-    m->geom_dev = cv.take<Geom>(1);
-    float *d = cv.take<float>((size_t)m->n_vox);
     hipError_t e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_map_combine, dim3(grid_for(m->n_vox / 4 + 1, 256, 4096)), dim3(256), 0, ctx->stream, a->dens, b->dens, alpha, m->n_vox, d);
@@ -1167,10 +1188,9 @@ extern "C" int pdbeda_point_density(pdbeda_map *m, const int32_t *crs, int64_t n
     if (n == 0) return PDBEDA_OK;
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return with_scratch(ctx, align_up(12 * n) + align_up(8 * n), [&](char *base) -> int {
-        Carver cv(base);
-        int32_t *d_crs = cv.take<int32_t>(3 * n);
-        double *d_out = cv.take<double>(n);
+    int32_t *d_crs = nullptr;
+    double *d_out = nullptr;
+    return with_scratch(ctx, "point density", [&](Carver &cv) { cv.take(d_crs, 3 * n); cv.take(d_out, n); }, [&]() -> int {
         const int32_t *in = pinned_in(ctx, crs, (size_t)(3 * n));
         if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_crs, crs, (size_t)(12 * n))); in = d_crs; }
         double *res = pinned_out(ctx, out, (size_t)n);
@@ -1185,10 +1205,9 @@ extern "C" int pdbeda_valid_crs(pdbeda_map *m, const int32_t *crs, int64_t n, ui
     if (n == 0) return PDBEDA_OK;
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return with_scratch(ctx, align_up(12 * n) + align_up(n), [&](char *base) -> int {
-        Carver cv(base);
-        int32_t *d_crs = cv.take<int32_t>(3 * n);
-        uint8_t *d_out = cv.take<uint8_t>(n);
+    int32_t *d_crs = nullptr;
+    uint8_t *d_out = nullptr;
+    return with_scratch(ctx, "valid crs", [&](Carver &cv) { cv.take(d_crs, 3 * n); cv.take(d_out, n); }, [&]() -> int {
         const int32_t *in = pinned_in(ctx, crs, (size_t)(3 * n));
         if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_crs, crs, (size_t)(12 * n))); in = d_crs; }
         uint8_t *res = pinned_out(ctx, out, (size_t)n);
@@ -1203,10 +1222,9 @@ extern "C" int pdbeda_crs2xyz(pdbeda_map *m, const int32_t *crs, int64_t n, doub
     if (n == 0) return PDBEDA_OK;
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return with_scratch(ctx, align_up(12 * n) + align_up(24 * n), [&](char *base) -> int {
-        Carver cv(base);
-        int32_t *d_crs = cv.take<int32_t>(3 * n);
-        double *d_xyz = cv.take<double>(3 * n);
+    int32_t *d_crs = nullptr;
+    double *d_xyz = nullptr;
+    return with_scratch(ctx, "crs2xyz", [&](Carver &cv) { cv.take(d_crs, 3 * n); cv.take(d_xyz, 3 * n); }, [&]() -> int {
         const int32_t *in = pinned_in(ctx, crs, (size_t)(3 * n));
         if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_crs, crs, (size_t)(12 * n))); in = d_crs; }
         double *res = pinned_out(ctx, xyz, (size_t)(3 * n));
@@ -1221,10 +1239,9 @@ extern "C" int pdbeda_xyz2crs(pdbeda_map *m, const double *xyz, int64_t n, int32
     if (n == 0) return PDBEDA_OK;
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return with_scratch(ctx, align_up(12 * n) + align_up(24 * n), [&](char *base) -> int {
-        Carver cv(base);
-        double *d_xyz = cv.take<double>(3 * n);
-        int32_t *d_crs = cv.take<int32_t>(3 * n);
+    double *d_xyz = nullptr;
+    int32_t *d_crs = nullptr;
+    return with_scratch(ctx, "xyz2crs", [&](Carver &cv) { cv.take(d_xyz, 3 * n); cv.take(d_crs, 3 * n); }, [&]() -> int {
         const double *in = pinned_in(ctx, xyz, (size_t)(3 * n));
         if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, (size_t)(24 * n))); in = d_xyz; }
         int32_t *res = pinned_out(ctx, crs, (size_t)(3 * n));
@@ -1240,11 +1257,10 @@ extern "C" int pdbeda_xyz2crs(pdbeda_map *m, const double *xyz, int64_t n, int32
 // Carve a job out of an arena.  max_runs / max_blobs are worst-case bounds (a run needs a
 // gap: <= bits/2 + 1 per word; a blob owns >= one 2x2x2 cell... we simply bound blobs by runs).
 // max_runs: run ids (comp_of_run); max_comps: component ids (every per-component array; generic jobs: == max_runs, a run is a component)
-static size_t job_carve(Job &job, char *base, int n_vols, int64_t total_words, int64_t total_keys, int64_t max_runs,
+static void job_carve(Job &job, Carver &cv, int n_vols, int64_t total_words, int64_t total_keys, int64_t max_runs,
                         int64_t max_blobs, size_t extra_labels, int32_t **labels_out, int64_t n_tiles = 0, int64_t max_comps = -1) {
     if (max_comps < 0) max_comps = max_runs;
     job.run_cap = (uint32_t)max_runs; job.comp_cap = (uint32_t)max_comps; job.blob_cap = (uint32_t)std::min<int64_t>(max_blobs, 0xffffffffll);
-    Carver cv(base);
     job.n_vols = n_vols;
     job.total_words = total_words;
     job.key_words = (total_keys + 63) / 64;
@@ -1303,7 +1319,6 @@ static size_t job_carve(Job &job, char *base, int n_vols, int64_t total_words, i
     job.b_group = cv.take<int32_t>(max_blobs);
     int32_t *lab = extra_labels ? cv.take<int32_t>(extra_labels) : nullptr;
     if (labels_out) *labels_out = lab;
-    return cv.off;
 }
 
 // Enqueue the labelling engine on a job whose masks are already painted.
@@ -1426,12 +1441,14 @@ static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool w
     Job job;
     memset(&job, 0, sizeof job);
     job.fix_mul = m->fix_mul;
-    size_t need = job_carve(job, nullptr, n_planes, total_words, total_keys, max_runs, max_blobs, lab_elems, nullptr, tiles_pp, max_comps);
+    size_t need = 0;
     Arena arena;
-    int rc = arena_get(ctx, need, &arena);
-    if (rc) return rc;
     int32_t *labels_dev = nullptr;
-    job_carve(job, arena.base, n_planes, total_words, total_keys, max_runs, max_blobs, lab_elems, &labels_dev, tiles_pp, max_comps);
+    int rc = arena_carve(ctx, "whole-map labelling", &arena, [&](Carver &cv) {
+        job_carve(job, cv, n_planes, total_words, total_keys, max_runs, max_blobs, lab_elems, &labels_dev, tiles_pp, max_comps);
+        need = cv.off;
+    });
+    if (rc) return rc;
     job.vol_sign[0] = td.sign[0];
     job.vol_sign[1] = td.sign[1];
     job.unit_form = unit_form;
@@ -1727,13 +1744,12 @@ static int list_materialise_voxels(pdbeda_bloblist *bl) {
     const int64_t nb = bl->job_blobs;
     // total voxels unknown until the offsets scan; bound by key bits
     const int64_t max_vox = job.key_words * 64;
-    size_t need = align_up(8 * (nb + 1)) + align_up(4 * std::max<int64_t>(nb, 1)) + align_up(12 * std::max<int64_t>(max_vox, 1));
-    int rc = arena_get(ctx, need, &ow->vox_arena);
+    int rc = arena_carve(ctx, "voxel lists", &ow->vox_arena, [&](Carver &cv) {
+        cv.take(ow->offsets_dev, nb + 1);
+        cv.take(ow->cursor_dev, std::max<int64_t>(nb, 1));
+        cv.take(ow->crs_dev, 3 * std::max<int64_t>(max_vox, 1));
+    });
     if (rc) return rc;
-    Carver cv(ow->vox_arena.base);
-    ow->offsets_dev = cv.take<int64_t>(nb + 1);
-    ow->cursor_dev = cv.take<unsigned int>(std::max<int64_t>(nb, 1));
-    ow->crs_dev = cv.take<int32_t>(3 * std::max<int64_t>(max_vox, 1));
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(k_blob_offsets, dim3(1), dim3(1024), 0, st, job, ow->offsets_dev, ow->cursor_dev);
     if (job.total_words > 0)
@@ -1802,22 +1818,25 @@ static int list_moments_compute(pdbeda_bloblist *bl) {
     if (int rc = map_fix_mul(m)) return rc;      // (known since the labelling call, unless the map was invalidated meanwhile)
     pdbeda_bloblist *ow = owner_of(bl);
     const size_t nb = (size_t)cnt;
-    const size_t bytes = 2 * align_up(4 * (size_t)nv) + align_up(4 * BS_BOX * nb) + align_up(8 * BS_REC * nb) + align_up(64) + align_up(40 * nb) + align_up(72 * nb) +
-                         align_up(80 * nb);
+    BlobShapeArgs a;
+    unsigned long long *d_widest = nullptr;
+    int32_t *d_i = nullptr;
+    long long *d_l = nullptr;
+    double *d_d = nullptr;
     Arena arena;
-    if (int rc = arena_get(ctx, bytes, &arena)) return rc;
+    const int rc_arena = arena_carve(ctx, "blob moments", &arena, [&](Carver &cv) {
+        cv.take(a.park_rho, (size_t)nv); cv.take(a.park_blob, (size_t)nv);
+        cv.take(a.box, BS_BOX * nb); cv.take(a.rec, BS_REC * nb);
+        cv.take(d_widest, 8);      // (right behind the sums records: ONE fill clears both)
+        cv.take(d_i, 10 * nb);
+        cv.take(d_l, 9 * nb);
+        cv.take(d_d, 10 * nb);
+    });
+    if (rc_arena) return rc_arena;
     auto run = [&]() -> int {
-        Carver cv(arena.base);
-        BlobShapeArgs a;
         a.geom = m->geom_dev; a.dens = m->dens;
         a.crs = ow->crs_dev; a.off = ow->offsets_dev + bl->rank_lo; a.cnt = cnt;
-        a.park_rho = cv.take<float>((size_t)nv); a.park_blob = cv.take<int32_t>((size_t)nv);
-        a.box = cv.take<int32_t>(BS_BOX * nb); a.rec = cv.take<unsigned long long>(BS_REC * nb);
         a.fix_mul = m->fix_mul;
-        unsigned long long *d_widest = cv.take<unsigned long long>(8);
-        int32_t *d_i = cv.take<int32_t>(10 * nb);
-        long long *d_l = cv.take<long long>(9 * nb);
-        double *d_d = cv.take<double>(10 * nb);
         hipStream_t st = ctx->stream;
         const unsigned chunks = (unsigned)((nv + BS_CHUNK - 1) / BS_CHUNK);
         HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)a.box, (int)0x80000000u, BS_BOX * nb, st));
@@ -1834,7 +1853,7 @@ static int list_moments_compute(pdbeda_bloblist *bl) {
         { PROF(ctx, "k_blobshape_finish"); hipLaunchKernelGGL(k_blobshape_finish, dim3(grid_for(cnt, 256)), dim3(256), 0, st, a.box, a.rec, cnt, 1.0 / m->fix_mul, d_i, d_l, d_d); }
         HIP_TRY(ctx, hipGetLastError());
         bl->shape_i.resize(10 * nb); bl->shape_l.resize(9 * nb); bl->shape_d.resize(10 * nb);
-        const D2HItem rows[3] = {{bl->shape_i.data(), d_i, 40 * nb}, {bl->shape_l.data(), d_l, 72 * nb}, {bl->shape_d.data(), d_d, 80 * nb}};
+        const D2HItem rows[3] = {{bl->shape_i.data(), d_i, sizeof(int32_t) * 10 * nb}, {bl->shape_l.data(), d_l, sizeof(long long) * 9 * nb}, {bl->shape_d.data(), d_d, sizeof(double) * 10 * nb}};
         HIP_TRY(ctx, d2h_many(ctx, rows, 3));
         HIP_TRY(ctx, ctx_sync(ctx));
         return PDBEDA_OK;
@@ -1884,12 +1903,11 @@ extern "C" int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host)
     // scratch: [signed volume if it was not requested at labelling time] + decoded volume
     const bool have = bl->labels_dev && bl->labels_done;
     Arena a;
-    int rc = arena_get(ctx, align_up(4 * nvox) * (have ? 1 : 2), &a);
+    int32_t *decoded = nullptr, *tmp = nullptr;
+    int rc = arena_carve(ctx, "labels", &a, [&](Carver &cv) { cv.take(decoded, nvox); if (!have) cv.take(tmp, nvox); });
     if (rc) return rc;
-    int32_t *decoded = (int32_t *)a.base;
     const int32_t *signed_vol = bl->labels_dev;
     if (!have) {
-        int32_t *tmp = (int32_t *)(a.base + align_up(4 * nvox));
         launch_labels<false>(ctx, bl->job, bl->td, tmp, bl->map->geom_dev);
         signed_vol = tmp;
     }
@@ -1966,9 +1984,7 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
     // (the two lists of ONE fused labelling job: one signed volume serves both planes)
     const bool shared = need_own[0] && need_own[1] && pj->blobs[0]->job.ctr == pj->blobs[1]->job.ctr;
     if (shared) need_own[1] = false;
-    size_t need = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        Carver cv(pass ? pj->arena.base : nullptr);
+    const int rc = arena_carve(ctx, "peak search", &pj->arena, [&](Carver &cv) {
         a.ctr = cv.take<PeakCounters>(1);
         int32_t *own[2] = {nullptr, nullptr};
         for (int p = 0; p < a.n_planes; ++p) {
@@ -1990,13 +2006,9 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
             if (need_own[p]) own[p] = cv.take<int32_t>((size_t)nvox);
             pl.labels = have[p] ? have[p] : (need_own[p] ? own[p] : ((p == 1 && shared) ? own[0] : nullptr));
         }
-        if (pass == 0) {
-            need = cv.off;
-            const int rc = arena_get(ctx, need, &pj->arena);
-            if (rc) return rc;
-        }
-    }
-    pj->bytes = need;
+        pj->bytes = cv.off;
+    });
+    if (rc) return rc;
     hipError_t e = hipSuccess;
     {   // (nothing to clear: the stencil stores every tile's counts, the scan every counter)
         for (int p = 0; p < a.n_planes; ++p)
@@ -2250,21 +2262,17 @@ static int expand_groups(const int64_t *group_offsets, int64_t n_groups, int64_t
 static int group_alloc(pdbeda_ctx *ctx, int64_t n_items, int64_t n_groups, GroupSetup *gs) {
     if (n_groups >= (1ll << 31) || n_items >= (1ll << 40)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "batch too large");
     const int64_t ni = std::max<int64_t>(n_items, 1), ng = std::max<int64_t>(n_groups, 1);
-    size_t need = align_up(24 * ni) + align_up(4 * ni) + align_up(4 * ni) + align_up(sizeof(AtomBox) * ni) + align_up(12 * ni) +
-                  2 * align_up(12 * ng) + align_up(sizeof(VolDesc) * ng) + align_up(sizeof(Counters));
-    int rc = arena_get(ctx, need, &gs->in_arena);
-    if (rc) return rc;
-    Carver cv(gs->in_arena.base);
-    gs->d_xyz = cv.take<double>(3 * ni);
-    gs->d_radii = cv.take<float>(ni);
-    gs->d_item_group = cv.take<int32_t>(ni);
-    gs->d_boxes = cv.take<AtomBox>(ni);
-    gs->d_vols = cv.take<VolDesc>(ng);       // (boxes, volumes and counters follow the inputs: a per-atom sphere batch whose bounds the host makes sends all six in one row)
-    gs->d_ctr = cv.take<Counters>(1);
-    gs->d_crs = cv.take<int32_t>(3 * ni);
-    gs->g_lo = cv.take<int32_t>(3 * ng);
-    gs->g_hi = cv.take<int32_t>(3 * ng);
-    return 0;
+    return arena_carve(ctx, "sphere / list batch", &gs->in_arena, [&](Carver &cv) {
+        cv.take(gs->d_xyz, 3 * ni);
+        cv.take(gs->d_radii, ni);
+        cv.take(gs->d_item_group, ni);
+        cv.take(gs->d_boxes, ni);
+        cv.take(gs->d_vols, ng);       // (boxes, volumes and counters follow the inputs: a per-atom sphere batch whose bounds the host makes sends all six in one row)
+        cv.take(gs->d_ctr, 1);
+        cv.take(gs->d_crs, 3 * ni);
+        cv.take(gs->g_lo, 3 * ng);
+        cv.take(gs->g_hi, 3 * ng);
+    });
 }
 
 // Every path that sizes a sphere / list batch ends here -- the device's totals after their round trip, the host's without one: the totals onto the
@@ -2474,11 +2482,9 @@ static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n
     Job job;
     memset(&job, 0, sizeof job);
     job.fix_mul = m->fix_mul;
-    size_t need = job_carve(job, nullptr, (int)n_groups, gs.total_words, gs.total_keys, max_runs, max_runs, 0, nullptr);
     Arena arena;
-    int rc = arena_get(ctx, need, &arena);
+    int rc = arena_carve(ctx, "grouped blobs", &arena, [&](Carver &cv) { job_carve(job, cv, (int)n_groups, gs.total_words, gs.total_keys, max_runs, max_runs, 0, nullptr); });
     if (rc) { arena_put(ctx, gs.in_arena); return rc; }
-    job_carve(job, arena.base, (int)n_groups, gs.total_words, gs.total_keys, max_runs, max_runs, 0, nullptr);
     hipStream_t st = ctx->stream;
     hipError_t e = hipSuccess;
     {   // volume descriptors into the job + zeroes over counters, masks, first-key bitmap and both levels of rank counters (adjacent in the arena: job_carve): one launch
@@ -2601,18 +2607,24 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
     }
     const int64_t tw = std::max<int64_t>(gs.total_words, 1);
     Arena a;
-    rc = arena_get(ctx, align_up(8 * tw) + 3 * align_up(8 * n_groups) + align_up(4 * n_groups), &a);
+    uint64_t *mask = nullptr;
+    double *d_pos = nullptr, *d_neg = nullptr;
+    unsigned long long *d_cnt = nullptr;
+    unsigned int *d_inv = nullptr;
+    size_t zero_bytes = 0;
+    rc = arena_carve(ctx, "region sums", &a, [&](Carver &cv) {
+        cv.take(mask, tw);
+        cv.take(d_pos, n_groups);
+        cv.take(d_neg, n_groups);
+        cv.take(d_cnt, n_groups);
+        cv.take(d_inv, n_groups);
+        zero_bytes = cv.off;      // (all of it)
+    });
     if (rc) { arena_put(ctx, gs.in_arena); return rc; }
-    Carver cv(a.base);
-    uint64_t *mask = cv.take<uint64_t>(tw);
-    double *d_pos = cv.take<double>(n_groups);
-    double *d_neg = cv.take<double>(n_groups);
-    unsigned long long *d_cnt = cv.take<unsigned long long>(n_groups);
-    unsigned int *d_inv = cv.take<unsigned int>(n_groups);
     hipStream_t st = ctx->stream;
     hipError_t e;
     {   // the staged inputs into the scratch (when group_setup left their copy to us) and zeroes over masks and sums: one launch
-        const size_t in16 = gs.pend_bytes / 16, zero16 = cv.off / 16;
+        const size_t in16 = gs.pend_bytes / 16, zero16 = zero_bytes / 16;
         hipLaunchKernelGGL(k_job_init, dim3((unsigned)std::min<size_t>((std::max(zero16, in16) + 255) / 256, 2048)), dim3(256), 0, st,
                            reinterpret_cast<const uint4 *>(gs.pend_src), reinterpret_cast<uint4 *>(gs.pend_dst), (unsigned long long)in16,
                            (const uint4 *)nullptr, (uint4 *)nullptr, 0ull, reinterpret_cast<uint4 *>(a.base), (unsigned long long)zero16);
@@ -2711,16 +2723,21 @@ extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t 
             k_sumsig = reinterpret_cast<double *>(pinned_take(ctx, 8 * rows, sum_sig ? sum_sig + (size_t)a0 * cells : nullptr));
             k_valid = reinterpret_cast<uint8_t *>(pinned_take(ctx, na, valid ? valid + a0 : nullptr));
         } else {
+            double *d_xyz = nullptr;
+            AtomBox *d_box = nullptr;
+            auto carve = [&](Carver &cv, size_t atoms) {      // (sized once for the largest chunk, laid out for each chunk's own count)
+                cv.take(d_xyz, 3 * atoms);
+                cv.take(d_box, atoms);
+                cv.take(k_n, atoms * cells); cv.take(k_sum, atoms * cells); cv.take(k_nsig, atoms * cells); cv.take(k_sumsig, atoms * cells);
+                cv.take(k_valid, atoms);
+            };
             if (!scratch.base) {
                 const size_t nc = (size_t)std::min<int64_t>(chunk, n_atoms);
-                const int rc = arena_get(ctx, align_up(24 * nc) + align_up(sizeof(AtomBox) * nc) + 4 * align_up(8 * nc * cells) + align_up(nc), &scratch);
+                const int rc = arena_carve(ctx, "radial profiles", &scratch, [&](Carver &cv) { carve(cv, nc); });
                 if (rc) return rc;
             }
             Carver cv(scratch.base);
-            double *d_xyz = cv.take<double>(3 * na);
-            AtomBox *d_box = cv.take<AtomBox>(na);
-            k_n = cv.take<long long>(rows); k_sum = cv.take<double>(rows); k_nsig = cv.take<long long>(rows); k_sumsig = cv.take<double>(rows);
-            k_valid = cv.take<uint8_t>(na);
+            carve(cv, na);
             k_xyz = d_xyz;
             k_box = d_box;
             const H2DItem in[2] = {{d_xyz, xyz + 3 * a0, 24 * na}, {d_box, &boxes[(size_t)a0], sizeof(AtomBox) * na}};
@@ -2762,13 +2779,16 @@ extern "C" int pdbeda_test_overlap(pdbeda_ctx *ctx, const int32_t *crs, const in
     for (int64_t p = 0; p < n_pairs; ++p)
         if (a_idx[p] < 0 || a_idx[p] >= n_sets || b_idx[p] < 0 || b_idx[p] >= n_sets) return fail(ctx, PDBEDA_ERR_ARGUMENT, "pair index out of range");
     std::vector<unsigned int> h_out(n_pairs);
-    int rc = with_scratch(ctx, align_up(12 * std::max<int64_t>(nv, 1)) + align_up(8 * (n_sets + 1)) + 3 * align_up(4 * n_pairs), [&](char *base) -> int {
-        Carver cv(base);
-        int32_t *d_crs = cv.take<int32_t>(3 * std::max<int64_t>(nv, 1));
-        int64_t *d_off = cv.take<int64_t>(n_sets + 1);
-        int32_t *d_a = cv.take<int32_t>(n_pairs);
-        int32_t *d_b = cv.take<int32_t>(n_pairs);
-        unsigned int *d_out = cv.take<unsigned int>(n_pairs);
+    int32_t *d_crs = nullptr, *d_a = nullptr, *d_b = nullptr;
+    int64_t *d_off = nullptr;
+    unsigned int *d_out = nullptr;
+    int rc = with_scratch(ctx, "test overlap", [&](Carver &cv) {
+        cv.take(d_crs, 3 * std::max<int64_t>(nv, 1));
+        cv.take(d_off, n_sets + 1);
+        cv.take(d_a, n_pairs);
+        cv.take(d_b, n_pairs);
+        cv.take(d_out, n_pairs);
+    }, [&]() -> int {
         hipStream_t st = ctx->stream;
         if (nv > 0) HIP_TRY(ctx, h2d_one(ctx, d_crs, crs, (size_t)(12 * nv)));
         {
@@ -2798,17 +2818,19 @@ extern "C" int pdbeda_symmetry_atoms(pdbeda_ctx *ctx, const double *xyz, int64_t
     std::vector<unsigned long long> h_keep((size_t)n_words);
     std::vector<int64_t> picked;
     std::vector<double> h_xyz;
-    int rc = with_scratch(ctx, align_up(24 * n_atoms) + align_up(96 * n_ops) + align_up(72) + 2 * align_up(24) + align_up(8 * n_words) + align_up(8 * total) + align_up(24 * total),
-                          [&](char *base) -> int {
-        Carver cv(base);
-        double *d_xyz = cv.take<double>(3 * n_atoms);
-        double *d_rot = cv.take<double>(12 * n_ops);
-        double *d_ortho = cv.take<double>(9);
-        double *d_lo = cv.take<double>(3);
-        double *d_hi = cv.take<double>(3);
-        unsigned long long *d_keep = cv.take<unsigned long long>(n_words);
-        int64_t *d_picked = cv.take<int64_t>(total);
-        double *d_out = cv.take<double>(3 * total);
+    double *d_xyz = nullptr, *d_rot = nullptr, *d_ortho = nullptr, *d_lo = nullptr, *d_hi = nullptr, *d_out = nullptr;
+    unsigned long long *d_keep = nullptr;
+    int64_t *d_picked = nullptr;
+    int rc = with_scratch(ctx, "symmetry atoms", [&](Carver &cv) {
+        cv.take(d_xyz, 3 * n_atoms);
+        cv.take(d_rot, 12 * n_ops);
+        cv.take(d_ortho, 9);
+        cv.take(d_lo, 3);
+        cv.take(d_hi, 3);
+        cv.take(d_keep, n_words);
+        cv.take(d_picked, total);
+        cv.take(d_out, 3 * total);
+    }, [&]() -> int {
         hipStream_t st = ctx->stream;
         {
             const H2DItem in[5] = {{d_xyz, xyz, (size_t)(24 * n_atoms)}, {d_rot, rot, (size_t)(96 * n_ops)}, {d_ortho, ortho, 72}, {d_lo, bbox_lo, 24}, {d_hi, bbox_hi, 24}};
@@ -2849,12 +2871,14 @@ extern "C" int pdbeda_nearest_atom(pdbeda_ctx *ctx, const double *centroids, int
     if (!ctx || n_centroids < 0 || n_atoms <= 0 || !atom_xyz || (n_centroids > 0 && (!centroids || !index || !distance))) return PDBEDA_ERR_ARGUMENT;
     if (n_centroids == 0) return PDBEDA_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return with_scratch(ctx, align_up(24 * n_centroids) + align_up(24 * n_atoms) + 2 * align_up(8 * n_centroids), [&](char *base) -> int {
-        Carver cv(base);
-        double *d_c = cv.take<double>(3 * n_centroids);
-        double *d_a = cv.take<double>(3 * n_atoms);
-        int64_t *d_i = cv.take<int64_t>(n_centroids);
-        double *d_d = cv.take<double>(n_centroids);
+    double *d_c = nullptr, *d_a = nullptr, *d_d = nullptr;
+    int64_t *d_i = nullptr;
+    return with_scratch(ctx, "nearest atom", [&](Carver &cv) {
+        cv.take(d_c, 3 * n_centroids);
+        cv.take(d_a, 3 * n_atoms);
+        cv.take(d_i, n_centroids);
+        cv.take(d_d, n_centroids);
+    }, [&]() -> int {
         hipStream_t st = ctx->stream;
         {
             const H2DItem in[2] = {{d_c, centroids, (size_t)(24 * n_centroids)}, {d_a, atom_xyz, (size_t)(24 * n_atoms)}};
@@ -2974,20 +2998,21 @@ extern "C" int pdbeda_coord_contacts(pdbeda_ctx *ctx, const double *q_xyz, int64
     const int64_t cells = g.n_cells;
     std::vector<unsigned> zeros((size_t)cells, 0u);
     int64_t total = 0;
-    const size_t bytes = align_up(24 * n_q) + align_up(24 * n_p) + align_up(4 * cells) + align_up(24 * n_p) + align_up(4 * (cells + 1)) + align_up(4 * cells) +
-                         3 * align_up(8 * n_q) + align_up(8);
-    int rc = with_scratch(ctx, bytes, [&](char *base) -> int {
-        Carver cv(base);
-        double *d_q = cv.take<double>(3 * n_q);
-        double *d_p = cv.take<double>(3 * n_p);
-        unsigned *d_count = cv.take<unsigned>(cells);
-        double *d_sorted = cv.take<double>(3 * n_p);
-        unsigned *d_start = cv.take<unsigned>(cells + 1);
-        unsigned *d_cursor = cv.take<unsigned>(cells);
-        double *d_dist = cv.take<double>(n_q);
-        int64_t *d_idx = cv.take<int64_t>(n_q);
-        double *d_odist = cv.take<double>(n_q);
-        int64_t *d_nout = cv.take<int64_t>(1);
+    double *d_q = nullptr, *d_p = nullptr, *d_sorted = nullptr, *d_dist = nullptr, *d_odist = nullptr;
+    unsigned *d_count = nullptr, *d_start = nullptr, *d_cursor = nullptr;
+    int64_t *d_idx = nullptr, *d_nout = nullptr;
+    int rc = with_scratch(ctx, "coord contacts", [&](Carver &cv) {
+        cv.take(d_q, 3 * n_q);
+        cv.take(d_p, 3 * n_p);
+        cv.take(d_count, cells);
+        cv.take(d_sorted, 3 * n_p);
+        cv.take(d_start, cells + 1);
+        cv.take(d_cursor, cells);
+        cv.take(d_dist, n_q);
+        cv.take(d_idx, n_q);
+        cv.take(d_odist, n_q);
+        cv.take(d_nout, 1);
+    }, [&]() -> int {
         hipStream_t st = ctx->stream;
         {
             const H2DItem in[3] = {{d_q, q_xyz, (size_t)(24 * n_q)}, {d_p, p_xyz, (size_t)(24 * n_p)}, {d_count, zeros.data(), (size_t)(4 * cells)}};
@@ -3028,31 +3053,32 @@ extern "C" int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int
     std::vector<unsigned> h_keep((size_t)n_cand);
     unsigned h_total = 0;
     int64_t rows = 0;
-    const size_t bytes_a = align_up(24 * n_poly) + align_up(24 * n_q) + align_up(96 * n_ops) + align_up(72) + align_up(16 * n_cand) + align_up(4 * cells_p) +
-                           align_up(4 * n_cand) + align_up(4 * cells_n) + align_up(24 * n_poly) + align_up(4 * (cells_p + 1)) + align_up(4 * cells_p) +
-                           align_up(4 * (cells_n + 1)) + align_up(4 * cells_n) + 3 * align_up(8 * n_q) + align_up(8);
+    double *d_poly = nullptr, *d_q = nullptr, *d_rot = nullptr, *d_ortho = nullptr, *d_sorted_p = nullptr, *d_dist = nullptr, *d_odist = nullptr;
+    int32_t *d_cand = nullptr;
+    unsigned *d_count_p = nullptr, *d_keep = nullptr, *d_count_n = nullptr, *d_start_p = nullptr, *d_cursor_p = nullptr, *d_start_n = nullptr, *d_cursor_n = nullptr;
+    int64_t *d_idx = nullptr, *d_nout = nullptr;
     Arena A, B;
-    int rc = arena_get(ctx, bytes_a, &A);
+    int rc = arena_carve(ctx, "crystal contacts", &A, [&](Carver &cv) {
+        cv.take(d_poly, 3 * n_poly);
+        cv.take(d_q, 3 * n_q);
+        cv.take(d_rot, 12 * n_ops);
+        cv.take(d_ortho, 9);
+        cv.take(d_cand, 4 * n_cand);
+        cv.take(d_count_p, cells_p);
+        cv.take(d_keep, n_cand);
+        cv.take(d_count_n, cells_n);
+        cv.take(d_sorted_p, 3 * n_poly);
+        cv.take(d_start_p, cells_p + 1);
+        cv.take(d_cursor_p, cells_p);
+        cv.take(d_start_n, cells_n + 1);
+        cv.take(d_cursor_n, cells_n);
+        cv.take(d_dist, n_q);
+        cv.take(d_idx, n_q);
+        cv.take(d_odist, n_q);
+        cv.take(d_nout, 1);
+    });
     if (rc) return rc;
     rc = [&]() -> int {
-        Carver cv(A.base);
-        double *d_poly = cv.take<double>(3 * n_poly);
-        double *d_q = cv.take<double>(3 * n_q);
-        double *d_rot = cv.take<double>(12 * n_ops);
-        double *d_ortho = cv.take<double>(9);
-        int32_t *d_cand = cv.take<int32_t>(4 * n_cand);
-        unsigned *d_count_p = cv.take<unsigned>(cells_p);
-        unsigned *d_keep = cv.take<unsigned>(n_cand);
-        unsigned *d_count_n = cv.take<unsigned>(cells_n);
-        double *d_sorted_p = cv.take<double>(3 * n_poly);
-        unsigned *d_start_p = cv.take<unsigned>(cells_p + 1);
-        unsigned *d_cursor_p = cv.take<unsigned>(cells_p);
-        unsigned *d_start_n = cv.take<unsigned>(cells_n + 1);
-        unsigned *d_cursor_n = cv.take<unsigned>(cells_n);
-        double *d_dist = cv.take<double>(n_q);
-        int64_t *d_idx = cv.take<int64_t>(n_q);
-        double *d_odist = cv.take<double>(n_q);
-        int64_t *d_nout = cv.take<int64_t>(1);
         hipStream_t st = ctx->stream;
         {   // inputs and the zeroed counters and flags in a row: ONE copy whenever the pinned block holds them (up to ~80 000 atoms), else one per item
             const H2DItem in[8] = {{d_poly, poly_xyz, (size_t)(24 * n_poly)}, {d_q, q_xyz, (size_t)(24 * n_q)}, {d_rot, rot, (size_t)(96 * n_ops)},
@@ -3110,13 +3136,15 @@ extern "C" int pdbeda_image_coords(pdbeda_ctx *ctx, const double *poly_xyz, int6
     if (n_cand * n_poly >= (1ll << 32) - 1) return fail(ctx, PDBEDA_ERR_ARGUMENT, "more than 2^32 image atoms");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t total = n_cand * n_poly;
-    return with_scratch(ctx, align_up(24 * n_poly) + align_up(96 * n_ops) + align_up(72) + align_up(16 * n_cand) + align_up(24 * total), [&](char *base) -> int {
-        Carver cv(base);
-        double *d_poly = cv.take<double>(3 * n_poly);
-        double *d_rot = cv.take<double>(12 * n_ops);
-        double *d_ortho = cv.take<double>(9);
-        int32_t *d_cand = cv.take<int32_t>(4 * n_cand);
-        double *d_out = cv.take<double>(3 * total);
+    double *d_poly = nullptr, *d_rot = nullptr, *d_ortho = nullptr, *d_out = nullptr;
+    int32_t *d_cand = nullptr;
+    return with_scratch(ctx, "image coords", [&](Carver &cv) {
+        cv.take(d_poly, 3 * n_poly);
+        cv.take(d_rot, 12 * n_ops);
+        cv.take(d_ortho, 9);
+        cv.take(d_cand, 4 * n_cand);
+        cv.take(d_out, 3 * total);
+    }, [&]() -> int {
         hipStream_t st = ctx->stream;
         {
             const H2DItem in[4] = {{d_poly, poly_xyz, (size_t)(24 * n_poly)}, {d_rot, rot, (size_t)(96 * n_ops)}, {d_ortho, ortho, 72}, {d_cand, cand, (size_t)(16 * n_cand)}};
@@ -3181,23 +3209,27 @@ extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_
     const CellGrid grid = make_cell_grid(glo, ghi, maxd, n_atoms, crop_lo, crop_hi);
     const int64_t cells = grid.n_cells;
     const size_t na = (size_t)n_atoms, tables = 6 * na + 8;
-    const size_t bytes = align_up(24 * na) + 2 * align_up(4 * cells) + align_up(4 * (cells + 1)) + align_up(24 * na) + align_up(4 * na) + align_up(8 * tables) +
-                         align_up(8 * n_tiles) + 2 * align_up(24 * na) + align_up(64) + (owner ? align_up(4 * nbox) : 0);
-    return with_scratch(ctx, bytes, [&](char *base) -> int {
-        Carver cv(base);
-        double *d_xyz = cv.take<double>(3 * na);
-        unsigned *d_count = cv.take<unsigned>(cells);
-        unsigned *d_cursor = cv.take<unsigned>(cells);
-        unsigned *d_start = cv.take<unsigned>(cells + 1);
-        double *d_sorted = cv.take<double>(3 * na);
-        int *d_sidx = cv.take<int>(na);
-        unsigned long long *d_tab = cv.take<unsigned long long>(tables);      // atom_n [3][n] | atom_sum [3][n] | unowned [6] | range [1]
-        double *d_tsq = cv.take<double>(n_tiles);
-        long long *d_on = cv.take<long long>(3 * na);
-        double *d_os = cv.take<double>(3 * na);
-        long long *d_un = cv.take<long long>(8);      // unowned_n [3] | (as doubles) unowned_sum [4]
+    double *d_xyz = nullptr, *d_sorted = nullptr, *d_tsq = nullptr, *d_os = nullptr;
+    unsigned *d_count = nullptr, *d_cursor = nullptr, *d_start = nullptr;
+    int *d_sidx = nullptr;
+    unsigned long long *d_tab = nullptr;
+    long long *d_on = nullptr, *d_un = nullptr;
+    int32_t *d_owner = nullptr;
+    return with_scratch(ctx, "map partition", [&](Carver &cv) {
+        cv.take(d_xyz, 3 * na);
+        cv.take(d_count, cells);
+        cv.take(d_cursor, cells);
+        cv.take(d_start, cells + 1);
+        cv.take(d_sorted, 3 * na);
+        cv.take(d_sidx, na);
+        cv.take(d_tab, tables);      // atom_n [3][n] | atom_sum [3][n] | unowned [6] | range [1]
+        cv.take(d_tsq, n_tiles);
+        cv.take(d_on, 3 * na);
+        cv.take(d_os, 3 * na);
+        cv.take(d_un, 8);      // unowned_n [3] | (as doubles) unowned_sum [4]
+        if (owner) cv.take(d_owner, nbox);
+    }, [&]() -> int {
         double *d_us = reinterpret_cast<double *>(d_un + 3);
-        int32_t *d_owner = owner ? cv.take<int32_t>(nbox) : nullptr;
         hipStream_t st = ctx->stream;
         HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 4 * (size_t)cells, st));
         HIP_TRY(ctx, hipMemsetAsync(d_tab, 0, 8 * tables, st));
@@ -3437,22 +3469,27 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     GroupSetup gs;
     rc = group_alloc(ctx, 2 * V, n_groups, &gs);
     if (rc) return bail(rc, clouds, nullptr);
-    Arena aux;
-    rc = arena_get(ctx, align_up(sizeof(VolDesc) * (size_t)n_groups) + 2 * align_up(4 * n_pool) + align_up(8 * (n_pool + 1)) + align_up(8 * n_pool) + align_up(8 * (n + 1)) + 3 * align_up(4 * std::max<int64_t>(n_pairs, 1)), &aux);
-    if (rc) { arena_put(ctx, gs.in_arena); return bail(rc, clouds, nullptr); }
     // what the device needs of the host's decisions, in ONE copy: pooled clouds, their groups, voxel offsets, the atoms' voxel
     // slices, the bonded pairs and the pairs' (zeroed) touch flags sit in a row in the scratch arena and in one host block
     // (six copies and a fill were seven launches on the stream, 6-8 us apart each: round 4, tools/exp/trace_cloud.sh)
-    Carver cv(aux.base);
+    Arena aux;
     const int64_t np1 = std::max<int64_t>(n_pairs, 1);
-    VolDesc *d_union_vols = cv.take<VolDesc>(n_groups);      // (the union job's volume descriptors ride in the same block: round 5)
-    int32_t *d_pool_cloud = cv.take<int32_t>(n_pool), *d_pool_group = cv.take<int32_t>(n_pool);
-    int64_t *d_pool_voff = cv.take<int64_t>(n_pool + 1);
-    int64_t *d_set_off = cv.take<int64_t>(n + 1);
-    int32_t *d_pa = cv.take<int32_t>(np1), *d_pb = cv.take<int32_t>(np1);
-    unsigned int *d_touch = cv.take<unsigned int>(np1);
-    const size_t upload_bytes = cv.off;
-    int32_t *d_comp = cv.take<int32_t>(2 * n_pool);
+    VolDesc *d_union_vols = nullptr;
+    int32_t *d_pool_cloud = nullptr, *d_pool_group = nullptr, *d_pa = nullptr, *d_pb = nullptr, *d_comp = nullptr;
+    int64_t *d_pool_voff = nullptr, *d_set_off = nullptr;
+    unsigned int *d_touch = nullptr;
+    size_t upload_bytes = 0;
+    rc = arena_carve(ctx, "aggregate cloud", &aux, [&](Carver &cv) {
+        cv.take(d_union_vols, n_groups);      // (the union job's volume descriptors ride in the same block: round 5)
+        cv.take(d_pool_cloud, n_pool); cv.take(d_pool_group, n_pool);
+        cv.take(d_pool_voff, n_pool + 1);
+        cv.take(d_set_off, n + 1);
+        cv.take(d_pa, np1); cv.take(d_pb, np1);
+        cv.take(d_touch, np1);
+        upload_bytes = cv.off;      // (the row that is uploaded ends here)
+        cv.take(d_comp, 2 * n_pool);
+    });
+    if (rc) { arena_put(ctx, gs.in_arena); return bail(rc, clouds, nullptr); }
     auto fail_dev = [&](hipError_t e, pdbeda_bloblist *u) {
         arena_put(ctx, aux);
         return bail(fail(ctx, PDBEDA_ERR_DEVICE, "aggregate cloud: %s", hipGetErrorString(e)), clouds, u);
