@@ -224,6 +224,24 @@ int pdbeda_bloblist_moments(pdbeda_bloblist *bl, int32_t *box_lo, int32_t *box_h
 /* Dense labels of a full-map list: int32 [us][ur][uc] over header.uniqueNcrs, blob index or
  * -1.  Computed on first use unless PDBEDA_FLAG_LABELS was given. */
 int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host);
+/* For every blob of list a, the nearest blob of list b in the sense of a caller-made table of voxel offsets (no reference counterpart: a
+ * reference blob knows nothing about any other blob).  The contract is purely integer.
+ * a and b are whole-map lists of the same context whose maps have the same header.uniqueNcrs: the green and the red list of one fused _pm
+ * call, two separately labelled lists of one map, or lists of two maps on one grid.  offsets (n_offsets x 3: dc, dr, ds) is an ORDERED
+ * neighbourhood table; the library gives it no geometric meaning and does not check its order.  Per blob i of a, over all pairs (p, t) with
+ * p a voxel of blob i and p + offsets[t] inside the non-repeating box header.uniqueNcrs (nothing wraps, as in the peaks) and a voxel of some
+ * blob of b: the smallest t, and among the voxels p with that t the one that comes first in c-major (c, r, s) order, c most significant
+ * (the order of first_key in pdbeda_bloblist_stats) -- a strict total order, so the answer does not depend on the order of the voxel
+ * list or of any atomic.  index[i] = t, voxel[i] = p, partner_voxel[i] = p + offsets[t], partner[i] = the index in b of the blob that
+ * holds that voxel; without a pair index and partner are -1 and the two voxels 0.  The offset (0, 0, 0) is legal (it hits where lists of
+ * two maps overlap).
+ * Any output pointer may be NULL.  Synchronous; rows in the blob order of a, the order of pdbeda_bloblist_stats.  An empty a or b, or
+ * n_offsets == 0, succeeds with rows of -1 and launches no search.  PDBEDA_ERR_ARGUMENT (nothing has been launched): a NULL or freed
+ * list; a == b; lists of different contexts; a list that is not whole-map; unequal uniqueNcrs; n_offsets > 16384 or < 0; an offset
+ * component outside [-127, 127] (the table lives in LDS as packed words).  PDBEDA_ERR_TIMEOUT on a context whose watchdog has expired.
+ * A failing call leaves the context usable. */
+int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, const int32_t *offsets, int64_t n_offsets, int32_t *index,
+                            int32_t *partner, int32_t *voxel, int32_t *partner_voxel);
 int pdbeda_bloblist_free(pdbeda_bloblist *bl);
 /* Diagnostic (no reference counterpart): counters of the labelling job behind a list,
  * out[8] = run ids, component ids, runs of the job beyond the first (1 = the typical-size arena was too small for this map and

@@ -107,6 +107,7 @@ _SIGS = {
     "pdbeda_bloblist_voxels": (C.c_int, [_p, _p, _p]),
     "pdbeda_bloblist_moments": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pdbeda_bloblist_labels": (C.c_int, [_p, _p]),
+    "pdbeda_bloblist_nearest": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p, _p]),
     "pdbeda_bloblist_free": (C.c_int, [_p]),
     "pdbeda_bloblist_counters": (C.c_int, [_p, _p]),
     "pdbeda_map_peaks": (C.c_int, [_p, C.c_float, _p, C.POINTER(_p)]),
@@ -395,6 +396,18 @@ class BlobList(object):
                "sw": np.zeros(n, np.float64), "sw1": np.zeros((n, 3), np.float64), "sw2": np.zeros((n, 6), np.float64)}
         self._ctx.check(self._ctx._lib.pdbeda_bloblist_moments(self._h, *[_ptr(out[k]) for k in ("boxLo", "boxHi", "extremeCrs", "extreme", "s1", "s2", "sw", "sw1", "sw2")]),
                         "pdbeda_bloblist_moments")
+        return out
+
+    def nearest(self, other, offsets):
+        """pdbeda_bloblist_nearest: per blob of this list, in list order, ``index`` (the first entry of the ordered ``offsets`` table, n x 3 int32,
+        that leads from a voxel of the blob into a blob of ``other``; -1 without one), ``partner`` (that blob's index in ``other``, or -1) and the two
+        voxels ``voxel`` / ``partnerVoxel`` (n x 3 int32, zeros without a partner)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, 3)
+        n = len(self)
+        out = {"index": np.zeros(n, np.int32), "partner": np.zeros(n, np.int32), "voxel": np.zeros((n, 3), np.int32), "partnerVoxel": np.zeros((n, 3), np.int32)}
+        self._ctx.check(self._ctx._lib.pdbeda_bloblist_nearest(self._h, other._h if other is not None else None, _ptr(offsets) if len(offsets) else None, len(offsets),
+                                                               _ptr(out["index"]), _ptr(out["partner"]), _ptr(out["voxel"]), _ptr(out["partnerVoxel"])),
+                        "pdbeda_bloblist_nearest")
         return out
 
     def labels(self, shape):

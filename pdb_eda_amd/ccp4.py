@@ -591,6 +591,41 @@ def blobShapeFinish(header, numVoxels, moments, wholeMap=False):
             "anisotropy": anisotropy, "equivalentRadii": np.sqrt(5.0) * lengths}
 
 
+NEAREST_MAX_OFFSETS, NEAREST_MAX_COMPONENT = 16384, 127      # what pdbeda_bloblist_nearest takes (its table lives in LDS as packed words)
+NEAREST_COLUMNS = ("index", "partner", "distance", "voxel", "partnerVoxel", "voxelXyz", "partnerVoxelXyz")
+
+
+def neighbourOffsets(header, maxDistance):
+    """The ordered neighbourhood table of ``pdbeda_bloblist_nearest`` for a map: ``(offsets int32 (n, 3), distance float64 (n,))`` with every
+    integer offset (dc, dr, ds) whose length |o . step| is <= ``maxDistance`` A -- step the linear part of ``crs2xyzCoord``, so permuted axes and
+    skewed cells are included -- in ascending order of the squared length, ties by (dc, dr, ds) ascending, dc most significant.  The offset
+    (0, 0, 0) comes first.  ValueError: more than 16384 offsets, or a component beyond +-127 (the limits of the device call).  Before it
+    enumerates anything the function also refuses a reach whose bounding box of offsets holds more than 64 x 16384 candidates.  The
+    ball fills pi / 6 of that box in an orthogonal cell and pi / 6 sin(angle) of it in a cell with one oblique angle, so a table that
+    would fit is refused there only for cells skewed to within about 2 degrees of flat: none that a map comes with."""
+    maxDistance = float(maxDistance)
+    if not (maxDistance >= 0 and np.isfinite(maxDistance)):
+        raise ValueError("maxDistance must be a finite, non-negative number of Angstrom")
+    step = header.crs2xyz_array(np.eye(3)) - header.crs2xyz_array(np.zeros((1, 3)))          # row k: the xyz step of crs axis k
+    # |o_k| <= |x| * |column k of step^-1| for x = o . step: the box that holds every offset of the ball
+    reach = np.floor(maxDistance * np.linalg.norm(np.linalg.inv(step), axis=0) * (1.0 + 1e-12)).astype(np.int64) + 1
+    if (reach - 1 > NEAREST_MAX_COMPONENT).any() or float(np.prod(2.0 * reach + 1.0)) > 64.0 * NEAREST_MAX_OFFSETS:
+        raise ValueError("maxDistance = %g A reaches beyond the %d offsets of +-%d voxels that the nearest-blob search takes" %
+                         (maxDistance, NEAREST_MAX_OFFSETS, NEAREST_MAX_COMPONENT))
+    axes = [np.arange(-int(n), int(n) + 1, dtype=np.int64) for n in reach]
+    cand = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3)
+    metric = step.dot(step.T)
+    d2 = np.einsum("ni,ij,nj->n", cand.astype(np.float64), metric, cand.astype(np.float64))
+    distance = np.sqrt(np.maximum(d2, 0.0))
+    keep = distance <= maxDistance
+    cand, d2, distance = cand[keep], d2[keep], distance[keep]
+    if len(cand) > NEAREST_MAX_OFFSETS or (len(cand) and int(np.abs(cand).max()) > NEAREST_MAX_COMPONENT):
+        raise ValueError("maxDistance = %g A gives %d offsets (the nearest-blob search takes %d of +-%d voxels)" %
+                         (maxDistance, len(cand), NEAREST_MAX_OFFSETS, NEAREST_MAX_COMPONENT))
+    order = np.lexsort((cand[:, 2], cand[:, 1], cand[:, 0], d2))
+    return np.ascontiguousarray(cand[order], dtype=np.int32), np.ascontiguousarray(distance[order])
+
+
 class _DeviceBlobSegment(object):
     """One device blob list behind a ``DeviceBlobs`` sequence: its statistics columns and, once somebody asked, its objects."""
 
@@ -687,6 +722,26 @@ class DeviceBlobs(collections.abc.Sequence):
             return {k: np.zeros(0) for k in SHAPE_COLUMNS}
         parts = [seg.shape() for seg in self._segments]
         return parts[0] if len(parts) == 1 else {k: np.concatenate([part[k] for part in parts]) for k in SHAPE_COLUMNS}
+
+    def nearestBlobs(self, other, maxDistance):
+        """For every blob of this whole-map list the nearest blob of ``other`` -- the red list of the same ``createFullBlobLists`` call, a
+        separately made list of the same map, or a list of another map on the same grid -- within ``maxDistance`` A, from ONE device call
+        (``pdbeda_bloblist_nearest`` in include/pdbeda.h has the contract; the table is ``neighbourOffsets``): no label volume and no voxel
+        list comes to the host.  A dict of arrays, one row per blob: ``partner`` (index in ``other``, -1 without one), ``distance`` (A between
+        the two closest voxel centres, NaN without a partner), ``index`` (of that offset in the table), ``voxel`` / ``partnerVoxel`` (crs) and
+        ``voxelXyz`` / ``partnerVoxelXyz``.  Among equally near pairs the table's order decides, then the c-major position of the voxel."""
+        for blobs in (self, other):
+            if not isinstance(blobs, DeviceBlobs) or len(blobs._segments) != 1 or not blobs._segments[0].wholeMap:
+                raise ValueError("nearestBlobs works between two lists that createFullBlobList / createFullBlobLists returned (not joined ones)")
+        mine, theirs = self._segments[0], other._segments[0]
+        header = mine.densityMatrix.header
+        offsets, distance = neighbourOffsets(header, maxDistance)
+        out = mine.bl.nearest(theirs.bl, offsets)
+        found = out["index"] >= 0
+        out["distance"] = np.where(found, distance[np.where(found, out["index"], 0)], np.nan) if len(distance) else np.full(len(found), np.nan)
+        out["voxelXyz"] = header.crs2xyz_array(out["voxel"]).reshape(-1, 3)
+        out["partnerVoxelXyz"] = header.crs2xyz_array(out["partnerVoxel"]).reshape(-1, 3)
+        return out
 
     def columns(self):
         """{"centroid", "totalDensity", "n", "volume"} of all blobs as arrays -- or None once any of the objects exists (they

@@ -32,6 +32,7 @@
 #include "pdbeda_profiles.h"
 #include "pdbeda_partition.h"
 #include "pdbeda_blobshape.h"
+#include "pdbeda_blobnear.h"
 
 using namespace pdbeda;
 
@@ -1916,6 +1917,108 @@ extern "C" int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host)
     if (e == hipSuccess) e = ctx_sync(ctx);
     arena_put(ctx, a);
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "labels: %s", hipGetErrorString(e));
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Nearest blob of another list (pdbeda_blobnear.h; no reference counterpart; the contract: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// The launch graph: the packed table to the device (one staged copy), one fill (the records start as "no pair"), b's signed volume by
+// launch_labels when its job kept none, k_blobnear_scan over the chunks of a's voxel lists, k_blobnear_finish, and the rows in one copy and
+// one wait.  Every refusal comes before the first launch; the scratch arena goes back to the pool in stream order whatever happens; the
+// rows are registered for delivery only behind the last launch.
+extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, const int32_t *offsets, int64_t n_offsets, int32_t *index, int32_t *partner,
+                                       int32_t *voxel, int32_t *partner_voxel) {
+    if (!a || !b || a->freed || b->freed) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = a->ctx;
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    if (a == b) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: a list against itself");
+    if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: the lists belong to different contexts");
+    if (!a->whole_map || !b->whole_map) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: both lists must be whole-map lists");
+    const Geom &g = a->map->geom, &gb = b->map->geom;
+    for (int k = 0; k < 3; ++k)
+        if (g.unique_ncrs[k] != gb.unique_ncrs[k]) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: the maps of the two lists have different uniqueNcrs");
+    if (n_offsets < 0 || n_offsets > BN_MAX_OFFSETS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: a table of %lld offsets (the limit is %d)", (long long)n_offsets, BN_MAX_OFFSETS);
+    if (n_offsets > 0 && !offsets) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: no offsets table");
+    std::vector<uint32_t> packed((size_t)n_offsets);
+    for (int64_t t = 0; t < n_offsets; ++t) {
+        const int32_t *o = offsets + 3 * t;
+        for (int k = 0; k < 3; ++k)
+            if (o[k] < -BN_MAX_COMPONENT || o[k] > BN_MAX_COMPONENT)
+                return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: offset %lld has the component %d (the limit is +-%d)", (long long)t, o[k], BN_MAX_COMPONENT);
+        packed[(size_t)t] = blobnear_pack(o[0], o[1], o[2]);
+    }
+    // the counts of both lists first: a job that overflowed its typical-size arena runs again now (both lists of a fused call move with it)
+    if (int rc = list_resolve_counts(a)) return rc;
+    if (int rc = list_resolve_counts(b)) return rc;
+    const int64_t cnt = a->rank_hi - a->rank_lo, cnt_b = b->rank_hi - b->rank_lo;
+    auto no_pairs = [&]() {
+        for (int64_t i = 0; i < cnt; ++i) {
+            if (index) index[i] = -1;
+            if (partner) partner[i] = -1;
+            for (int k = 0; k < 3; ++k) { if (voxel) voxel[3 * i + k] = 0; if (partner_voxel) partner_voxel[3 * i + k] = 0; }
+        }
+        return PDBEDA_OK;
+    };
+    if (cnt == 0 || cnt_b == 0 || n_offsets == 0) return no_pairs();
+    const int64_t nv = pdbeda_bloblist_num_voxels(a);      // (materialises a's voxel lists)
+    if (nv < 0) return (int)nv;
+    if (nv == 0) return no_pairs();
+    if (cnt >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: a list of 2^31 blobs or more");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    pdbeda_bloblist *ow = owner_of(a);
+    const int64_t nvox = (int64_t)g.unique_ncrs[0] * g.unique_ncrs[1] * g.unique_ncrs[2];
+    const bool have = b->labels_dev && b->labels_done;
+    const size_t nb = (size_t)cnt;
+    BlobNearArgs args;
+    uint32_t *d_table = nullptr;
+    int32_t *d_rows = nullptr, *tmp = nullptr;
+    Arena arena;
+    const int rc_arena = arena_carve(ctx, "nearest blobs", &arena, [&](Carver &cv) {
+        cv.take(args.best, nb);
+        cv.take(d_table, (size_t)n_offsets);
+        cv.take(d_rows, 8 * nb);
+        if (!have) cv.take(tmp, (size_t)nvox);
+    });
+    if (rc_arena) return rc_arena;
+    std::vector<int32_t> rows(8 * nb);
+    auto run = [&]() -> int {
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, h2d_one(ctx, d_table, packed.data(), sizeof(uint32_t) * (size_t)n_offsets));
+        HIP_TRY(ctx, hipMemsetAsync(args.best, 0xFF, sizeof(unsigned long long) * nb, st));
+        const int32_t *signed_vol = b->labels_dev;
+        if (!have) {
+            launch_labels<false>(ctx, b->job, b->td, tmp, b->map->geom_dev);
+            signed_vol = tmp;
+        }
+        args.crs = ow->crs_dev; args.off = ow->offsets_dev + a->rank_lo; args.cnt = cnt;
+        args.labels = signed_vol; args.sign = b->sign;
+        args.uc = g.unique_ncrs[0]; args.ur = g.unique_ncrs[1]; args.us = g.unique_ncrs[2];
+        args.table = d_table; args.n_off = (int32_t)n_offsets;
+        // positions per thread: one while that gives fewer than BN_MIN_GROUPS workgroups (a walk is a chain of read latencies: a short list
+        // wants its walks side by side, not eight in a row in one thread), then the power of two that keeps about that many
+        args.per_thread = 1;
+        while (args.per_thread < BN_PER_THREAD && nv > (int64_t)256 * args.per_thread * BN_MIN_GROUPS) args.per_thread *= 2;
+        const int64_t chunk = (int64_t)256 * args.per_thread;
+        const unsigned chunks = (unsigned)((nv + chunk - 1) / chunk);
+        { PROF(ctx, "k_blobnear_scan"); hipLaunchKernelGGL(k_blobnear_scan, dim3(chunks), dim3(256), 0, st, args); }
+        { PROF(ctx, "k_blobnear_finish"); hipLaunchKernelGGL(k_blobnear_finish, dim3(grid_for(cnt, 256)), dim3(256), 0, st, args, d_rows); }
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, d2h(ctx, rows.data(), d_rows, sizeof(int32_t) * 8 * nb));
+        HIP_TRY(ctx, ctx_sync(ctx));
+        return PDBEDA_OK;
+    };
+    const int rc = run();
+    if (rc != PDBEDA_OK) (void)ctx_sync(ctx);      // (`packed` is freed on return and the table's copy may be a hipMemcpyAsync out of it: nothing of a failed call may still read it)
+    arena_put(ctx, arena);      // (stream order: whatever is still queued on a failed call runs before the arena's next user)
+    if (rc != PDBEDA_OK) return rc;
+    for (size_t i = 0; i < nb; ++i) {
+        const int32_t *r = rows.data() + 8 * i;
+        if (index) index[i] = r[0];
+        if (partner) partner[i] = r[1];
+        if (voxel) memcpy(voxel + 3 * i, r + 2, 12);
+        if (partner_voxel) memcpy(partner_voxel + 3 * i, r + 5, 12);
+    }
     return PDBEDA_OK;
 }
 

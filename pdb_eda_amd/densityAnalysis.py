@@ -345,6 +345,38 @@ def _crs_keys(crs):
     return (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]
 
 
+def blobDipoleColumns(near, back, greenTotal, redTotal, greenCentroid, redCentroid, ratio):
+    """The columns of the dipole table that need no atom, from canned inputs: ``near`` / ``back`` are the ``nearestBlobs`` columns of the green
+    list against the red one and of the red list against the green one (``partner``, ``distance``, ``voxelXyz``, ``partnerVoxelXyz``), the
+    totals and centroids the two lists' statistics columns.  One row per green blob that has a red partner, in green order: ``green`` / ``red``
+    (indices), ``gap`` (A between the two closest voxels), ``mutual`` (the red blob's nearest green blob is this one), ``greenElectrons`` /
+    ``redElectrons`` (|total / ratio|), ``balance`` (min / max of the two), ``centroidDistance``, ``midpoint`` (of the two closest voxels) and
+    ``shift`` (red centroid -> green centroid: the way the density says the atom should move)."""
+    partner = np.asarray(near["partner"], dtype=np.int64)
+    green = np.nonzero(partner >= 0)[0].astype(np.int64)
+    red = partner[green]
+    backPartner = np.asarray(back["partner"], dtype=np.int64)
+    greenCentroid, redCentroid = np.asarray(greenCentroid, dtype=np.float64).reshape(-1, 3), np.asarray(redCentroid, dtype=np.float64).reshape(-1, 3)
+    greenElectrons = np.abs(np.asarray(greenTotal, dtype=np.float64)[green] / ratio)
+    redElectrons = np.abs(np.asarray(redTotal, dtype=np.float64)[red] / ratio)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        balance = np.minimum(greenElectrons, redElectrons) / np.maximum(greenElectrons, redElectrons)
+    shift = greenCentroid[green] - redCentroid[red]
+    return {"green": green, "red": red, "gap": np.asarray(near["distance"], dtype=np.float64)[green], "mutual": backPartner[red] == green,
+            "greenElectrons": greenElectrons, "redElectrons": redElectrons, "balance": balance, "centroidDistance": np.sqrt((shift ** 2).sum(axis=1)),
+            "midpoint": 0.5 * (np.asarray(near["voxelXyz"], dtype=np.float64).reshape(-1, 3)[green] +
+                               np.asarray(near["partnerVoxelXyz"], dtype=np.float64).reshape(-1, 3)[green]),
+            "shift": shift}
+
+
+def collinearity(atomXyz, greenCentroid, redCentroid):
+    """The cosine at the atom between the directions to the two centroids: -1 = the atom sits between them (NaN when it sits ON one)."""
+    u = np.asarray(greenCentroid, dtype=np.float64).reshape(-1, 3) - np.asarray(atomXyz, dtype=np.float64).reshape(-1, 3)
+    v = np.asarray(redCentroid, dtype=np.float64).reshape(-1, 3) - np.asarray(atomXyz, dtype=np.float64).reshape(-1, 3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (u * v).sum(axis=1) / np.sqrt((u ** 2).sum(axis=1) * (v ** 2).sum(axis=1))
+
+
 class DensityAnalysis(object):
     """ref densityAnalysis.py:278-1240 (the accelerated subset)."""
 
@@ -357,6 +389,8 @@ class DensityAnalysis(object):
     blobShapeHeader = ['blob_index', 'num_voxels', 'volume', 'sign', 'electrons_of_discrepancy', 'extreme_in_sigma', 'extreme_in_electrons_per_A3', 'extreme_xyz',
                        'principal_length_1', 'principal_length_2', 'principal_length_3', 'anisotropy', 'box_extent', 'on_border', 'distance_to_atom', 'chain',
                        'residue_number', 'residue_name', 'atom_name', 'atom_symmetry', 'atom_xyz']
+    blobDipoleHeader = ['green_index', 'red_index', 'gap_distance', 'mutual', 'green_electrons', 'red_electrons', 'balance', 'centroid_distance', 'midpoint_xyz',
+                        'shift_xyz', 'distance_to_atom', 'chain', 'residue_number', 'residue_name', 'atom_name', 'atom_symmetry', 'atom_xyz', 'collinearity']
     regionDensityHeader = ["actual_significant_regional_density", "num_electrons_actual_significant_regional_density"]
     atomRegionDensityHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy"] + regionDensityHeader
     symmetryAtomRegionDensityHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "symmetry", "atom_xyz", "fully_within_density_map"] + regionDensityHeader
@@ -913,6 +947,43 @@ class DensityAnalysis(object):
                           np.asarray(shape["onBorder"], dtype=np.bool_), list(dist),
                           (chain, rows), (number, rows), (resname, rows), (cols.name if isinstance(cols.name, (list, tuple)) else list(cols.name), rows),
                           symmetry, coords)
+
+    # ---- green / red dipoles (no reference counterpart; built like the tables above) ------------
+    def calculateBlobDipoles(self, greenBlobs, redBlobs, maxDistance=2.5):
+        """One row (``blobDipoleHeader``) per green blob that has a red blob within ``maxDistance`` A of one of its voxels, in green order: the two
+        indices, the gap between the two closest voxels, ``mutual`` (the red blob's nearest green blob is this one: a second device call with the
+        lists swapped), the electrons of each blob and their balance min / max, the distance of the centroids, the midpoint of the two closest
+        voxels, the shift vector from the red centroid to the green one, the symmetry atom nearest to that midpoint and ``collinearity``: the cosine
+        at that atom between the directions to the two centroids (-1: the atom sits between them -- it is in the wrong place by about the shift).
+        The default of 2.5 A is a choice (about one atom diameter), not a measured optimum.  Totals and centroids are the device lists' own
+        columns (as in the shape table): blob objects of these lists that somebody has changed since (``merge``) are not looked at."""
+        symmetryAtoms = self.symmetryAtoms
+        symmetryAtomCoords = self.symmetryAtomCoords
+        if not self.densityElectronRatio:
+            raise RuntimeError("Failed to calculate densityElectronRatio, probably due to total aggregated electrons less than the minimum.")
+        ratio = self.densityElectronRatio
+        if not isinstance(greenBlobs, ccp4.DeviceBlobs) or not isinstance(redBlobs, ccp4.DeviceBlobs):
+            raise ValueError("greenBlobs and redBlobs must be what createFullBlobLists / createFullBlobList returned")
+        near = greenBlobs.nearestBlobs(redBlobs, maxDistance)                # (ValueError for joined or non-whole-map lists)
+        if not (near["partner"] >= 0).any():
+            return []
+        if len(symmetryAtomCoords) == 0:
+            raise ValueError("XB must be a 2-dimensional array.")       # (the blob table's failure for a file without operators)
+        back = redBlobs.nearestBlobs(greenBlobs, maxDistance)
+        greenStats, redStats = greenBlobs._segments[0].stats, redBlobs._segments[0].stats
+        d = blobDipoleColumns(near, back, greenStats["totalDensity"], redStats["totalDensity"], greenStats["centroid"], redStats["centroid"], ratio)
+        midpoint = np.ascontiguousarray(d["midpoint"], dtype=np.float64)
+        idx, dist = self.densityObj._ctx.nearest_atom(midpoint, np.asarray(symmetryAtomCoords, dtype=np.float64))
+        rows, symmetry, coords = symmetryAtoms.columns(idx)
+        cols = _structure.columns(self.biopdbObj)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        chain, number, resname = (cols.atom_lists(which) for which in ("chain", "number", "resname"))
+        atom_xyz = np.asarray(symmetryAtomCoords, dtype=np.float64)[np.asarray(idx, dtype=np.int64)]
+        cosine = collinearity(atom_xyz, np.asarray(greenStats["centroid"])[d["green"]], np.asarray(redStats["centroid"])[d["red"]])
+        return self._rows(d["green"], d["red"], np.ascontiguousarray(d["gap"]), np.ascontiguousarray(d["mutual"], dtype=np.bool_), d["greenElectrons"], d["redElectrons"],
+                          d["balance"], d["centroidDistance"], midpoint, np.ascontiguousarray(d["shift"], dtype=np.float64), list(dist),
+                          (chain, rows), (number, rows), (resname, rows), (cols.name if isinstance(cols.name, (list, tuple)) else list(cols.name), rows),
+                          symmetry, coords, np.ascontiguousarray(cosine))
 
     # ---- Fo / Fc maps, RSCC / RSR (ref densityAnalysis.py:426-446, 783-882) -------------------
     @property

@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole")
 
 
 def numpyConverter(obj):
@@ -82,6 +82,15 @@ def _shapeTable(analyzer, o):
     return _plainColumns(table, listColumns=(19,), floatColumns=(7, 12, 20))
 
 
+def _dipoleTable(analyzer, o):
+    """dipole sub-mode (no reference counterpart): the green Fo-Fc blobs that have a red one beside them -- the fused lists of the blob sub-mode at
+    ``numSD`` -- each with its red partner, the gap, the shift vector and the symmetry atom between them; ``radius`` is the largest gap when given."""
+    diffObj, numSD = analyzer.diffDensityObj, o["numSD"]
+    green, red = diffObj.createFullBlobLists(diffObj.meanDensity + numSD * diffObj.stdDensity)
+    table = analyzer.calculateBlobDipoles(green, red, o["radius"]) if o["radiusGiven"] else analyzer.calculateBlobDipoles(green, red)
+    return _plainColumns(table, listColumns=(15,), floatColumns=(8, 9, 16))
+
+
 def _partitionBlobTable(analyzer, o):
     """partition / blob: who owns the voxels of the green and / or red Fo-Fc blobs (green when neither is asked for)."""
     diffObj, numSD = analyzer.diffDensityObj, o["numSD"]
@@ -136,6 +145,7 @@ TABLES = {
     ("blob", None): (lambda an: _DA.blobStatisticsHeader, _blobTable),
     ("peak", None): (lambda an: _DA.peakStatisticsHeader, _peakTable),
     ("shape", None): (lambda an: _DA.blobShapeHeader, _shapeTable),
+    ("dipole", None): (lambda an: _DA.blobDipoleHeader, _dipoleTable),
     # (no reference counterpart; the shell columns are lists, carried as the peak table's list columns are)
     ("profile", "atom"): (lambda an: _DA.atomRadialProfileHeader, lambda an, o: an.calculateAtomRadialProfiles(o["radius"], o["shells"], o["numSD"], o["type"])),
     ("profile", "atom-type"): (lambda an: _DA.atomTypeRadialProfileHeader, lambda an, o: an.atomTypeRadialProfiles(o["radius"], o["shells"], o["numSD"])),
@@ -149,21 +159,23 @@ TABLES = {
 }
 
 
-def rows(analyzer, mode, level="atom", radius=3.5, numSD=None, type="", atomMask=None, optimizedRadii=False, green=False, red=False,
+def rows(analyzer, mode, level="atom", radius=None, numSD=None, type="", atomMask=None, optimizedRadii=False, green=False, red=False,
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape;  level: atom | residue | domain | symmetry-atom
-    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak and shape) | atom-type (profile) | summary | blob
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole;  level: atom | residue | domain | symmetry-atom
+    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak, shape and dipole) | atom-type (profile) | summary | blob
     (partition);  green / red: blob / peak / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
     (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
-    maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default)."""
+    maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default);  dipole: always the fused green
+    and red lists (numSD default 3.0), ``radius`` is the largest gap between the two blobs when given (else 2.5 A);  radius default 3.5 elsewhere."""
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % (MODES,))
-    key = (mode, None if mode in ("blob", "peak", "shape") else level)
+    key = (mode, None if mode in ("blob", "peak", "shape", "dipole") else level)
     if key not in TABLES:
         raise ValueError("%s mode has the levels %s" % (mode, ", ".join(lv for md, lv in TABLES if md == mode and lv)))
-    options = {"radius": float(radius), "numSD": float(numSD if numSD is not None else (3.0 if green or red or mode in ("difference", "partition") else 1.5)),
+    options = {"radius": float(radius if radius is not None else 3.5), "radiusGiven": radius is not None,
+               "numSD": float(numSD if numSD is not None else (3.0 if green or red or mode in ("difference", "partition", "dipole") else 1.5)),
                "type": type, "atomMask": atomMask, "optimizedRadii": optimizedRadii, "green": green, "red": red, "shells": int(shells)}
     if mode == "cloud":
         analyzer.aggregateCloud()
