@@ -110,6 +110,15 @@ __device__ __forceinline__ void wave_lds_sync() {
 // (s_waitcnt vmcnt(0)), which is what a kernel that has fire-and-forget stores in flight must NOT do.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// A 32-bit word of global memory that no workgroup of the running kernel writes (an earlier kernel of the job did), read
+// through the SCALAR cache: the address is block-uniform, the load rides on lgkmcnt beside the kernel arguments -- not on
+// vmcnt, where loads, stores and atomics return IN ORDER and a wait for one load is a wait for every store and atomic issued
+// before it -- and the value lands in a scalar register, which a tight vector budget cannot push to scratch behind a full
+// wait.  (The scalar cache is invalidated at kernel start, like the vector L1: a kernel boundary publishes the word.)
+__device__ __forceinline__ uint32_t load_uniform_word(const uint32_t *p) {
+    return *(const uint32_t __attribute__((address_space(4))) *)p;
+}
+
 // Tile t owns component ids [t * CCAP, (t+1) * CCAP) and run ids [t * runs_per_tile, ...): no
 // allocation atomics on the fast path.  Unused component ids are marked empty (r_n = 0).
 template <typename JobRef>
@@ -831,10 +840,10 @@ __global__ void __launch_bounds__(NTH, 8) k_face_merge(Job job_arg, const float 
     kernarg_prefetch();
     PDBEDA_LATE_JOB(lj);
     /*@F0*/
-    const bool any_unit = *lj.unit_flag == lj.epoch;   // block-uniform: some tile of this job is a unit tile (rare)
     static_assert(FACE_K == 7, "a word's component record is one 64-bit load: seven runs and the run at the last bit");
     __shared__ unsigned long long s_set[PAIR_SLOTS], s_pairs[PAIR_SLOTS];
     __shared__ uint32_t s_wsum[NTH / 64];
+    __shared__ uint32_t s_unit_word;
     // what kpar[] holds for the components of this tile and of the four tiles it meets across its r / s faces, fetched with
     // everything else: a union starts from two VALUES (an ancestor-or-self of either component, named by its first key), and
     // these are such values whatever the other workgroups have united meanwhile -- no trip for them in front of the first hook
@@ -868,14 +877,6 @@ __global__ void __launch_bounds__(NTH, 8) k_face_merge(Job job_arg, const float 
     if (r >= ur || s >= us || r2 < 0 || r2 >= ur || s2 < 0) task = false;
     const uint32_t tile_b = task ? (uint32_t)(((s2 >> 3) * td.rtiles + (r2 >> 3)) * td.ctiles + ct) : 0u;   // the r / s faces join tiles of one c column
     const int64_t wA = task ? word_at(fq, r, s, w0 + fwl) : 0, wB = task ? word_at(fq, r2, s2, w0 + fwl) : 0;
-    uint64_t mA = 0ull, mB = 0ull;
-    unsigned long long cA = 0ull, cB = 0ull;
-    uint32_t modes = 0u;
-    if (task) {
-        mA = lj.mask[wA]; mB = lj.mask[wB];
-        cA = comps64[comps_at((uint32_t)tile, fq, r, s, fwl)]; cB = comps64[comps_at(tile_b, fq, r2, s2, fwl)];
-        modes = (uint32_t)lj.tile_mode[tile] | (uint32_t)lj.tile_mode[tile_b];
-    }
     // the five tables: this tile, (rt - 1, st), (rt - 1, st - 1), (rt, st - 1), (rt + 1, st - 1)
     uint32_t tiles5[5];
     {
@@ -894,6 +895,17 @@ __global__ void __launch_bounds__(NTH, 8) k_face_merge(Job job_arg, const float 
         const uint32_t t5 = j == 0 ? tiles5[0] : (j == 1 ? tiles5[1] : (j == 2 ? tiles5[2] : (j == 3 ? tiles5[3] : tiles5[4])));
         kp_pre[k] = (e < 5 * KPH && t5 != 0xffffffffu) ? kuf_load(lj.kpar, t5 * (uint32_t)CCAP + (uint32_t)(e % KPH)) : KP_UNUSED;
     }
+    // (the packed parents FIRST: the compiler folds the two tile modes into a lane mask inside the block of the face loads --
+    //  behind a wait for them, and loads return in order.  With the parents' loads behind that block the wait was a whole cold
+    //  trip before they were issued; now everything of the trip is in flight when it comes.)
+    uint64_t mA = 0ull, mB = 0ull;
+    unsigned long long cA = 0ull, cB = 0ull;
+    uint32_t modes = 0u;
+    if (task) {
+        mA = lj.mask[wA]; mB = lj.mask[wB];
+        cA = comps64[comps_at((uint32_t)tile, fq, r, s, fwl)]; cB = comps64[comps_at(tile_b, fq, r2, s2, fwl)];
+        modes = (uint32_t)lj.tile_mode[tile] | (uint32_t)lj.tile_mode[tile_b];
+    }
     {   // every tile clears its slice of the first-key bitmap and of the rank counters (saves a memset launch; painted by the next
         // kernel) and its inbox counter -- HERE, under the first trip: fire-and-forget stores, and the barriers of this kernel's hot
         // path wait for LDS only (lds_barrier), so nothing ever waits for them (r03 had them behind the last barrier: 0.9 us at
@@ -910,6 +922,11 @@ __global__ void __launch_bounds__(NTH, 8) k_face_merge(Job job_arg, const float 
         if (tid == 0) lj.inbox_count[(size_t)tile * INBOX_STRIDE] = 0u;
     }
     for (int i = tid; i < pair_slots; i += NTH) s_set[i] = 0ull;   // 0 = empty: a pair (lo << 32 | hi) has hi > lo >= 0
+    // the job's unit flag (used by the cold tail only) rides with the trip: a scalar load, issued HERE -- behind the vector loads,
+    // in front of the first wait for them.  As the kernel's first statement it was a vector load, a full wait and a spill in
+    // front of everything: a cold round trip for four bytes before "the one trip" had been issued (emitted code, r12).
+    // (Parked in LDS across the hot path: the tail's one ds_read costs less than a scalar register held through the kernel.)
+    if (tid == 0) s_unit_word = load_uniform_word(lj.unit_flag);
 #pragma unroll
     for (int k = 0; k < KPL; ++k) {
         const int e = tid + k * NTH;
@@ -1033,6 +1050,7 @@ __global__ void __launch_bounds__(NTH, 8) k_face_merge(Job job_arg, const float 
     }
     /*@F4*/
     /*@F5*/
+    const bool any_unit = s_unit_word == lj.epoch;   // block-uniform: some tile of this job is a wide or a unit tile (rare)
     if (any_unit) {
         // Some tile left the fast path in k_tile_label.  A WIDE tile (more than CCAP components) is complete -- united in LDS, its
         // components under global ids: the pairs it has across its faces are united here, word by word (by the workgroup of the
@@ -1176,13 +1194,25 @@ __global__ void __launch_bounds__(256) k_resolve_tiles(Job job, int n_tiles) {
     const bool is_root = used && kp_id(p0) == i;
     const bool member = used && !is_root;   // non-root component with voxels
     int root = (int)i;
+    kp_t rp = p0;
     /*@R1*/
     if (member) {
-        const kp_t rp = kuf_find_from(job.kpar, p0);
+        rp = kuf_find_from(job.kpar, p0);
         root = (int)kp_id(rp);
-        job.kpar[i] = rp;
     }
     /*@R2*/
+    // The chain is  loads -> find -> LDS table -> barrier -> returning inbox atomic -> entry stores.  Loads, stores and atomics
+    // share ONE in-order counter (vmcnt): a wait for a load is a wait for every store and atomic the wave issued before it, and
+    // behind the divergent find the compiler cannot count, so such a wait is a full one.  Hence the order below: the record is
+    // waited for HERE (first key included; `root` ties the wait behind the find, whose first step needs p0 alone), the table
+    // takes the member while nothing but loads has ever been issued, and only then go the fire-and-forget stores and the
+    // paints -- between find and table, where they stood, the wait for the record in front of the table's first LDS operation
+    // was a wait for three device-scope atomics (emitted code; stamps r12: find -> behind the barrier 3.4 us, 0.4 with the table first).
+    // They are not moved to the kernel's end either: a thousand tiles painting at once as their last act made the kernel's
+    // tail as long as the chain had become short (measured).  Here they have the barrier and the inbox's round trip to land.
+    asm volatile("" :: "v"(v_key), "v"(root));
+    if (member) { table_add(root, n_i, v_sum, v_c, v_r, v_s); s_any = 1; }
+    if (member) job.kpar[i] = rp;
     job.parent[i] = root;   // (every id of the tile: the accessors and the label writer go through parent[])
     {   // the tile's roots as four ballots: k_emit_tiles maps its threads onto the set bits instead of scanning every component id
         const unsigned long long rbits = __ballot(is_root);
@@ -1190,7 +1220,6 @@ __global__ void __launch_bounds__(256) k_resolve_tiles(Job job, int n_tiles) {
     }
     if (is_root) paint(v_key);
     /*@R3*/
-    if (member) { table_add(root, n_i, v_sum, v_c, v_r, v_s); s_any = 1; }
     lds_barrier();
     /*@R4*/
     if (s_any == 0) return;   // nothing to fold in this tile
