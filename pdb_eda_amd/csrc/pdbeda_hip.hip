@@ -179,48 +179,54 @@ struct pdbeda_map {
     bool fix_refused = false;         // the range pass found a NaN / infinity: labelling calls refuse the map (map_fix_mul)
 };
 
+// A blob list is a VIEW of a labelling job: the whole job, or one plane of a fused whole-map job (the handle is &job->view[p])
+struct LabelJob;
 struct pdbeda_bloblist {
-    std::vector<AtomBox> host_boxes;   // a per-atom sphere batch whose boxes the host made: box of atom a (else empty)
-    pdbeda_ctx *ctx = nullptr;
-    pdbeda_map *map = nullptr;
-    Arena arena;
-    Job job;
+    LabelJob *job = nullptr;
     int vol_lo = 0, vol_hi = 0;      // volumes of the job that belong to this list
-    bool owns_arena = true;          // the "red" list of a fused call shares the green list's arena
-    pdbeda_bloblist *sibling = nullptr;
-    bool freed = false;
-    // resolved lazily
-    bool have_counts = false;
-    int64_t rank_lo = 0, rank_hi = 0;  // blob rank range of this list inside the job's table
-    int64_t job_blobs = -1;            // blobs of the whole job (known once the counters have been read)
-    int64_t n_voxels = -1;
-    int32_t *labels_dev = nullptr;     // inside arena when requested
-    bool labels_done = false;
-    int64_t *offsets_dev = nullptr;
-    int32_t *crs_dev = nullptr;
-    unsigned int *cursor_dev = nullptr;
-    bool voxels_done = false;
-    Arena vox_arena;
-    bool whole_map = false;
-    TileDims td;
     int sign = 1;
-    // whole-map jobs: what it takes to run the job again (a typical-size arena that turned out too small: see whole_map_enqueue)
-    float cut_pos = 0.0f, cut_neg = 0.0f;
-    bool want_pos = false, want_neg = false;
-    uint32_t flags = 0;
-    int tier = 0, unit_form = 0, reruns = 0;
-    size_t job_bytes = 0;              // bytes the job carved out of its arena (a recycled arena may be larger)
-    // whole-map jobs, on the list that owns the arena: the first rows of the job's blob table, fetched WITH the counters (round 5: the count and the table of
-    // each of the two lists of a fused call were four waits; now one serves both)
-    int64_t spec_rows = 0;
-    std::vector<int64_t> spec_n, spec_key;
-    std::vector<double> spec_total, spec_centroid, spec_center, spec_volume;
-    std::vector<int32_t> spec_group;
+    bool freed = false;
+    int64_t n_voxels = -1;
     // pdbeda_bloblist_moments: the rows of THIS list, made by the first call and kept until the list is freed
     bool shape_done = false;
     std::vector<int32_t> shape_i;      // [blobs][10]: box_lo, box_hi, extreme crs, bits of the extreme value
     std::vector<int64_t> shape_l;      // [blobs][9]: sum d, sum d d'
     std::vector<double> shape_d;       // [blobs][10]: sum w, sum w d, sum w d d'
+};
+
+// One record per labelling job, deleted (its arenas back to the pool) when the last of its views is freed
+struct LabelJob {
+    pdbeda_ctx *ctx = nullptr;
+    pdbeda_map *map = nullptr;
+    Arena arena;
+    Job job;
+    TileDims td;
+    bool whole_map = false;
+    int32_t *labels_dev = nullptr;     // the signed label volume: inside arena when requested
+    bool labels_done = false;
+    Arena vox_arena;                   // the voxel lists of the job's blobs, made on demand
+    int64_t *offsets_dev = nullptr;
+    int32_t *crs_dev = nullptr;
+    unsigned int *cursor_dev = nullptr;
+    bool voxels_done = false;
+    std::vector<AtomBox> host_boxes;   // a per-atom sphere batch whose boxes the host made: box of atom a (else empty)
+    // whole-map jobs: what it takes to run the job again (a typical-size arena that turned out too small: see whole_map_enqueue)
+    float cut_pos = 0.0f, cut_neg = 0.0f;
+    bool want_pos = false, want_neg = false;
+    uint32_t flags = 0;
+    int tier = 0, unit_form = 0, reruns = 0;
+    size_t bytes = 0;                  // bytes the job carved out of its arena (a recycled arena may be larger)
+    // what the counters said, once read
+    bool have_counts = false;
+    int64_t n_blobs = 0, n_blobs_vol0 = 0;
+    // whole-map jobs: the first rows of the job's blob table, fetched WITH the counters (round 5: the count and the table of
+    // each of the two lists of a fused call were four waits; now one serves both)
+    int64_t spec_rows = 0;
+    std::vector<int64_t> spec_n, spec_key;
+    std::vector<double> spec_total, spec_centroid, spec_center, spec_volume;
+    std::vector<int32_t> spec_group;
+    int live = 0;                      // views not yet freed
+    pdbeda_bloblist view[2];
 };
 
 static const int N_PARTIAL = 2048;
@@ -1347,11 +1353,22 @@ static int engine_enqueue(pdbeda_ctx *ctx, pdbeda_map *m, Job &job, int64_t max_
     return 0;
 }
 
-static pdbeda_bloblist *new_list(pdbeda_ctx *ctx, pdbeda_map *m) {
-    pdbeda_bloblist *bl = new pdbeda_bloblist();
-    bl->ctx = ctx;
-    bl->map = m;
-    ctx->live_handles++;
+static LabelJob *new_label_job(pdbeda_ctx *ctx, pdbeda_map *m) {
+    LabelJob *lj = new LabelJob();
+    lj->ctx = ctx;
+    lj->map = m;
+    return lj;
+}
+
+// Hand out view p of an enqueued job: the volumes [vol_lo, vol_hi)
+static pdbeda_bloblist *job_view(LabelJob *lj, int p, int vol_lo, int vol_hi, int sign) {
+    pdbeda_bloblist *bl = &lj->view[p];
+    bl->job = lj;
+    bl->vol_lo = vol_lo;
+    bl->vol_hi = vol_hi;
+    bl->sign = sign;
+    lj->live++;
+    lj->ctx->live_handles++;
     return bl;
 }
 
@@ -1387,15 +1404,8 @@ static void launch_labels(pdbeda_ctx *ctx, const Job &job, const TileDims &td, i
 // voxel a run of a unit tile, a blob per 2x2x2 cell: 2.9 GB at 256^3, of which a job touches a few hundred MB).  A map that
 // needs more raises Counters::overflow on the device, stays inside its arena, and is run again at tier 1 (the worst case)
 // by the first accessor that reads the counters (list_resolve_counts): correct always, slower only where it was slow already.
-struct WholeMapJob {
-    Job job;
-    Arena arena;
-    TileDims td;
-    int32_t *labels_dev = nullptr;
-    bool labels = false;
-    size_t bytes = 0;
-};
-static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool want_pos, bool want_neg, uint32_t flags, int tier, int unit_form, WholeMapJob *out) {
+// On success the job, its arena and the recipe of this run are written into *out (the record of a job's first run, or of the run it replaces).
+static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool want_pos, bool want_neg, uint32_t flags, int tier, int unit_form, LabelJob *out) {
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const Geom &g = m->geom;
@@ -1496,33 +1506,21 @@ static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool w
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { arena_put(ctx, arena); return fail(ctx, PDBEDA_ERR_DEVICE, "whole-map labelling launch: %s", hipGetErrorString(e)); }
-    out->job = job; out->arena = arena; out->td = td; out->labels_dev = labels_dev; out->labels = labels; out->bytes = need;
+    out->job = job; out->arena = arena; out->td = td; out->labels_dev = labels_dev; out->labels_done = labels; out->bytes = need;
+    out->cut_pos = cut_pos; out->cut_neg = cut_neg; out->want_pos = want_pos; out->want_neg = want_neg; out->flags = flags; out->tier = tier; out->unit_form = unit_form;
     return PDBEDA_OK;
 }
 
 static int full_blobs_impl(pdbeda_map *m, float cut_pos, float cut_neg, bool want_pos, bool want_neg, uint32_t flags,
                            pdbeda_bloblist **out_pos, pdbeda_bloblist **out_neg) {
     pdbeda_ctx *ctx = m->ctx;
-    WholeMapJob wj;
+    LabelJob *lj = new_label_job(ctx, m);
+    lj->whole_map = true;
     const int tier = ctx->debug_worst_case_arena ? 1 : 0, form = tier;   // (the debug hook: the second run's shape at once)
-    int rc = whole_map_enqueue(m, cut_pos, cut_neg, want_pos, want_neg, flags, tier, form, &wj);
-    if (rc) return rc;
-    const int n_planes = (want_pos ? 1 : 0) + (want_neg ? 1 : 0);
-    pdbeda_bloblist *first = nullptr;
-    for (int p = 0; p < n_planes; ++p) {
-        pdbeda_bloblist *bl = new_list(ctx, m);
-        bl->job = wj.job;
-        bl->td = wj.td;
-        bl->vol_lo = p;
-        bl->vol_hi = p + 1;
-        bl->whole_map = true;
-        bl->sign = wj.td.sign[p];
-        if (p == 0) { bl->arena = wj.arena; bl->owns_arena = true; first = bl; }
-        else { bl->owns_arena = false; bl->sibling = first; first->sibling = bl; }
-        bl->labels_dev = wj.labels_dev;
-        bl->labels_done = wj.labels;
-        bl->cut_pos = cut_pos; bl->cut_neg = cut_neg; bl->want_pos = want_pos; bl->want_neg = want_neg; bl->flags = flags; bl->tier = tier; bl->unit_form = form;
-        bl->job_bytes = wj.bytes;
+    int rc = whole_map_enqueue(m, cut_pos, cut_neg, want_pos, want_neg, flags, tier, form, lj);
+    if (rc) { delete lj; return rc; }
+    for (int p = 0; p < lj->td.n_planes; ++p) {
+        pdbeda_bloblist *bl = job_view(lj, p, p, p + 1, lj->td.sign[p]);
         if (bl->sign > 0) *out_pos = bl; else *out_neg = bl;
     }
     return PDBEDA_OK;
@@ -1546,35 +1544,48 @@ extern "C" int pdbeda_full_blobs_pm(pdbeda_map *m, float cutoff_pos, float cutof
 }
 
 // ---- accessors ------------------------------------------------------------------------
-static pdbeda_bloblist *owner_of(pdbeda_bloblist *bl) { return bl->owns_arena ? bl : bl->sibling; }
 static const int64_t SPEC_ROWS = 2048;      // rows of a whole-map job's blob table fetched with its counters (84 B each: 172 KB; the analysis entry's 128^3 map has ~1 400 blobs)
+
+// What the counters of a job said: recorded once, for every view of the job
+static void job_record_counts(LabelJob *lj, const Counters &ctr) {
+    lj->n_blobs = ctr.n_blobs;
+    lj->n_blobs_vol0 = ctr.n_blobs_vol0;
+    lj->have_counts = true;
+}
+
+// Rank range of a list inside its job's blob table (the counters have been read): a list is the whole job, or one plane of a
+// fused whole-map job (k_emit published the split)
+struct RankRange { int64_t lo, hi; };
+static RankRange list_ranks(const pdbeda_bloblist *bl) {
+    const LabelJob *lj = bl->job;
+    if (bl->vol_lo == 0 && bl->vol_hi == lj->job.n_vols) return {0, lj->n_blobs};
+    return bl->vol_lo == 0 ? RankRange{0, lj->n_blobs_vol0} : RankRange{lj->n_blobs_vol0, lj->n_blobs};
+}
+
 static int list_resolve_counts(pdbeda_bloblist *bl) {
-    if (bl->have_counts) return 0;
-    pdbeda_ctx *ctx = bl->ctx;
+    LabelJob *lj = bl->job;
+    if (lj->have_counts) return 0;
+    pdbeda_ctx *ctx = lj->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // rank range of this list inside the job's blob table: a list is the whole job, or one plane of a fused whole-map job
-    // (k_emit published the split)
     Counters ctr;
-    // a whole-map job: the first rows of its blob table ride along with the counters, kept on the list that owns the job for both lists of a fused call
-    // (rows beyond the blob count are stale bytes: never served)
+    // a whole-map job: the first rows of its blob table ride along with the counters (rows beyond the blob count are stale bytes: never served)
     auto fetch = [&]() -> int {
-        pdbeda_bloblist *ow = bl->whole_map ? owner_of(bl) : nullptr;
-        const int64_t g = ow ? std::min<int64_t>((int64_t)bl->job.blob_cap, SPEC_ROWS) : 0;
+        const Job &job = lj->job;
+        const int64_t g = lj->whole_map ? std::min<int64_t>((int64_t)job.blob_cap, SPEC_ROWS) : 0;
         if (g > 0) {
-            const Job &job = bl->job;
-            ow->spec_rows = 0;
-            ow->spec_n.resize((size_t)g); ow->spec_key.resize((size_t)g); ow->spec_total.resize((size_t)g); ow->spec_centroid.resize(3 * (size_t)g);
-            ow->spec_center.resize(3 * (size_t)g); ow->spec_volume.resize((size_t)g); ow->spec_group.resize((size_t)g);
-            const D2HItem parts[8] = {{&ctr, job.ctr, sizeof ctr}, {ow->spec_n.data(), job.b_n, (size_t)(8 * g)}, {ow->spec_total.data(), job.b_total, (size_t)(8 * g)},
-                                      {ow->spec_centroid.data(), job.b_centroid, (size_t)(24 * g)}, {ow->spec_center.data(), job.b_center, (size_t)(24 * g)},
-                                      {ow->spec_volume.data(), job.b_volume, (size_t)(8 * g)}, {ow->spec_key.data(), job.b_key, (size_t)(8 * g)},
-                                      {ow->spec_group.data(), job.b_group, (size_t)(4 * g)}};
+            lj->spec_rows = 0;
+            lj->spec_n.resize((size_t)g); lj->spec_key.resize((size_t)g); lj->spec_total.resize((size_t)g); lj->spec_centroid.resize(3 * (size_t)g);
+            lj->spec_center.resize(3 * (size_t)g); lj->spec_volume.resize((size_t)g); lj->spec_group.resize((size_t)g);
+            const D2HItem parts[8] = {{&ctr, job.ctr, sizeof ctr}, {lj->spec_n.data(), job.b_n, (size_t)(8 * g)}, {lj->spec_total.data(), job.b_total, (size_t)(8 * g)},
+                                      {lj->spec_centroid.data(), job.b_centroid, (size_t)(24 * g)}, {lj->spec_center.data(), job.b_center, (size_t)(24 * g)},
+                                      {lj->spec_volume.data(), job.b_volume, (size_t)(8 * g)}, {lj->spec_key.data(), job.b_key, (size_t)(8 * g)},
+                                      {lj->spec_group.data(), job.b_group, (size_t)(4 * g)}};
             HIP_TRY(ctx, d2h_many(ctx, parts, 8));
             HIP_TRY(ctx, ctx_sync(ctx));
-            ow->spec_rows = g;
+            lj->spec_rows = g;
             return 0;
         }
-        HIP_TRY(ctx, d2h(ctx, &ctr, bl->job.ctr, sizeof ctr));
+        HIP_TRY(ctx, d2h(ctx, &ctr, job.ctr, sizeof ctr));
         HIP_TRY(ctx, ctx_sync(ctx));
         return 0;
     };
@@ -1582,50 +1593,23 @@ static int list_resolve_counts(pdbeda_bloblist *bl) {
         const int rc_fetch = fetch();
         if (rc_fetch) return rc_fetch;
     }
-    while (bl->whole_map && ctr.overflow != 0u) {
-        // The job is run again, ONCE (both lists of a fused call move to the new job), when the typical-size arena was too small
+    while (lj->whole_map && ctr.overflow != 0u) {
+        // The job is run again, ONCE (every list of the job reads the new run), when the typical-size arena was too small
         // for this map (bits 0 / 1), or when the map has unit tiles and the job was enqueued without their two launches (bit 2,
         // Job::unit_form).  The second run has both: the worst-case arena and the unit launches -- a first run without the unit
         // launches does not know how many ids its unit tiles would have asked for.
-        pdbeda_bloblist *ow = owner_of(bl);
-        if (!ow) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling: a list without its job");
         const int tier = 1, form = 1;
-        if (tier == ow->tier && form == ow->unit_form) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling overflowed its worst-case arena");
-        if (ow->voxels_done || bl->voxels_done) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling: overflow noticed after the voxel lists were made");
-        WholeMapJob wj;
-        arena_put(ctx, ow->arena);                         // (stream order: the first run's kernels are done -- ctx_sync above)
-        int rc = whole_map_enqueue(ow->map, ow->cut_pos, ow->cut_neg, ow->want_pos, ow->want_neg, ow->flags, tier, form, &wj);
-        if (rc) { ow->arena.base = nullptr; ow->arena.cap = 0; return rc; }
-        ow->arena = wj.arena;
-        pdbeda_bloblist *both[2] = {ow, ow->sibling};
-        for (pdbeda_bloblist *l : both) {
-            if (!l) continue;
-            l->job = wj.job; l->td = wj.td; l->labels_dev = wj.labels_dev; l->labels_done = wj.labels;
-            l->tier = tier; l->unit_form = form; l->reruns += 1; l->have_counts = false; l->job_bytes = wj.bytes; l->spec_rows = 0;
-        }
+        if (tier == lj->tier && form == lj->unit_form) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling overflowed its worst-case arena");
+        if (lj->voxels_done) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling: overflow noticed after the voxel lists were made");
+        arena_put(ctx, lj->arena);                         // (stream order: the first run's kernels are done -- ctx_sync above)
+        int rc = whole_map_enqueue(lj->map, lj->cut_pos, lj->cut_neg, lj->want_pos, lj->want_neg, lj->flags, tier, form, lj);
+        if (rc) { lj->arena.base = nullptr; lj->arena.cap = 0; return rc; }
+        lj->reruns += 1;
         const int rc_fetch = fetch();
         if (rc_fetch) return rc_fetch;
     }
-    if (!bl->whole_map && ctr.unit_wait_failed) return fail(ctx, PDBEDA_ERR_DEVICE, "sphere batch: the device's volumes outgrew what the host sized the job for");
-    if (bl->vol_lo == 0 && bl->vol_hi == bl->job.n_vols) { bl->rank_lo = 0; bl->rank_hi = ctr.n_blobs; }
-    else if (bl->whole_map && bl->job.n_vols == 2 && bl->vol_hi == bl->vol_lo + 1) {
-        bl->rank_lo = bl->vol_lo == 0 ? 0 : ctr.n_blobs_vol0;
-        bl->rank_hi = bl->vol_lo == 0 ? ctr.n_blobs_vol0 : ctr.n_blobs;
-    } else return fail(ctx, PDBEDA_ERR_STATE, "blob list covers an unexpected volume range");
-    bl->job_blobs = ctr.n_blobs;
-    bl->have_counts = true;
-    // the other list of a fused call reads the same counters: its range is known now too
-    if (bl->whole_map && bl->job.n_vols == 2) {
-        pdbeda_bloblist *ow = owner_of(bl);
-        pdbeda_bloblist *both[2] = {ow, ow ? ow->sibling : nullptr};
-        for (pdbeda_bloblist *l : both) {
-            if (!l || l == bl || l->freed || l->have_counts || l->job.ctr != bl->job.ctr || l->vol_hi != l->vol_lo + 1) continue;
-            l->rank_lo = l->vol_lo == 0 ? 0 : ctr.n_blobs_vol0;
-            l->rank_hi = l->vol_lo == 0 ? ctr.n_blobs_vol0 : ctr.n_blobs;
-            l->job_blobs = ctr.n_blobs;
-            l->have_counts = true;
-        }
-    }
+    if (!lj->whole_map && ctr.unit_wait_failed) return fail(ctx, PDBEDA_ERR_DEVICE, "sphere batch: the device's volumes outgrew what the host sized the job for");
+    job_record_counts(lj, ctr);
     return 0;
 }
 
@@ -1634,18 +1618,19 @@ static int list_resolve_counts(pdbeda_bloblist *bl) {
 // unit tiles by cause (run slots, -, component table), bytes of the job's arena.
 extern "C" int pdbeda_bloblist_counters(pdbeda_bloblist *bl, int64_t *out) {
     if (!bl || bl->freed || !out) return PDBEDA_ERR_ARGUMENT;
-    pdbeda_ctx *ctx = bl->ctx;
+    const LabelJob *lj = bl->job;
+    pdbeda_ctx *ctx = lj->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Counters c;
-    HIP_TRY(ctx, d2h(ctx, &c, bl->job.ctr, sizeof c));
+    HIP_TRY(ctx, d2h(ctx, &c, lj->job.ctr, sizeof c));
     HIP_TRY(ctx, ctx_sync(ctx));
-    out[0] = c.n_runs; out[1] = c.n_comps; out[2] = bl->reruns; out[3] = c.n_blobs;
+    out[0] = c.n_runs; out[1] = c.n_comps; out[2] = lj->reruns; out[3] = c.n_blobs;
     out[4] = out[5] = out[6] = 0;
-    out[7] = (int64_t)(bl->job_bytes ? bl->job_bytes : owner_of(bl)->arena.cap);   // bytes of device memory the job needs (its arena, if recycled, may be up to twice that)
-    if (bl->whole_map && bl->job.tile_mode) {   // tiles off the fast path by kind: tile_mode 1 = unit tile (run slots / values), 2 = wide tile (more than CCAP components, united in LDS all the same), 3 = unit tile (no ids left for a wide tile's components)
-        const int64_t n_tiles = (int64_t)bl->td.ctiles * bl->td.rtiles * bl->td.stiles;
+    out[7] = (int64_t)(lj->bytes ? lj->bytes : lj->arena.cap);   // bytes of device memory the job needs (its arena, if recycled, may be up to twice that)
+    if (lj->whole_map && lj->job.tile_mode) {   // tiles off the fast path by kind: tile_mode 1 = unit tile (run slots / values), 2 = wide tile (more than CCAP components, united in LDS all the same), 3 = unit tile (no ids left for a wide tile's components)
+        const int64_t n_tiles = (int64_t)lj->td.ctiles * lj->td.rtiles * lj->td.stiles;
         std::vector<uint8_t> mode(n_tiles);
-        HIP_TRY(ctx, d2h(ctx, mode.data(), bl->job.tile_mode, n_tiles));
+        HIP_TRY(ctx, d2h(ctx, mode.data(), lj->job.tile_mode, n_tiles));
         HIP_TRY(ctx, ctx_sync(ctx));
         for (uint8_t v : mode) { if (v == 1) ++out[4]; else if (v == 2) ++out[5]; else if (v == 3) ++out[6]; }
     }
@@ -1657,7 +1642,8 @@ extern "C" int64_t pdbeda_bloblist_count(pdbeda_bloblist *bl) {
     if (!bl || bl->freed) return PDBEDA_ERR_ARGUMENT;
     int rc = list_resolve_counts(bl);
     if (rc) return rc;
-    return bl->rank_hi - bl->rank_lo;
+    const RankRange r = list_ranks(bl);
+    return r.hi - r.lo;
 }
 
 extern "C" int pdbeda_bloblist_stats(pdbeda_bloblist *bl, int64_t *n, double *total_density, double *centroid, double *coord_center,
@@ -1665,22 +1651,20 @@ extern "C" int pdbeda_bloblist_stats(pdbeda_bloblist *bl, int64_t *n, double *to
     if (!bl || bl->freed) return PDBEDA_ERR_ARGUMENT;
     int rc = list_resolve_counts(bl);
     if (rc) return rc;
-    pdbeda_ctx *ctx = bl->ctx;
-    const Job &job = bl->job;
-    const int64_t lo = bl->rank_lo, cnt = bl->rank_hi - bl->rank_lo;
+    const LabelJob *lj = bl->job;
+    pdbeda_ctx *ctx = lj->ctx;
+    const Job &job = lj->job;
+    const int64_t lo = list_ranks(bl).lo, cnt = list_ranks(bl).hi - lo;
     if (cnt == 0) return PDBEDA_OK;
-    if (bl->whole_map) {      // the rows that came with the counters
-        const pdbeda_bloblist *ow = owner_of(bl);
-        if (ow && ow->spec_rows >= lo + cnt && ow->job.ctr == job.ctr) {
-            if (n) memcpy(n, ow->spec_n.data() + lo, (size_t)(8 * cnt));
-            if (total_density) memcpy(total_density, ow->spec_total.data() + lo, (size_t)(8 * cnt));
-            if (centroid) memcpy(centroid, ow->spec_centroid.data() + 3 * lo, (size_t)(24 * cnt));
-            if (coord_center) memcpy(coord_center, ow->spec_center.data() + 3 * lo, (size_t)(24 * cnt));
-            if (volume) memcpy(volume, ow->spec_volume.data() + lo, (size_t)(8 * cnt));
-            if (first_key) memcpy(first_key, ow->spec_key.data() + lo, (size_t)(8 * cnt));
-            if (group) memcpy(group, ow->spec_group.data() + lo, (size_t)(4 * cnt));
-            return PDBEDA_OK;
-        }
+    if (lj->whole_map && lj->spec_rows >= lo + cnt) {      // the rows that came with the counters
+        if (n) memcpy(n, lj->spec_n.data() + lo, (size_t)(8 * cnt));
+        if (total_density) memcpy(total_density, lj->spec_total.data() + lo, (size_t)(8 * cnt));
+        if (centroid) memcpy(centroid, lj->spec_centroid.data() + 3 * lo, (size_t)(24 * cnt));
+        if (coord_center) memcpy(coord_center, lj->spec_center.data() + 3 * lo, (size_t)(24 * cnt));
+        if (volume) memcpy(volume, lj->spec_volume.data() + lo, (size_t)(8 * cnt));
+        if (first_key) memcpy(first_key, lj->spec_key.data() + lo, (size_t)(8 * cnt));
+        if (group) memcpy(group, lj->spec_group.data() + lo, (size_t)(4 * cnt));
+        return PDBEDA_OK;
     }
     const D2HItem columns[7] = {{n, job.b_n + lo, (size_t)(8 * cnt)}, {total_density, job.b_total + lo, (size_t)(8 * cnt)},
                                 {centroid, job.b_centroid + 3 * lo, (size_t)(24 * cnt)}, {coord_center, job.b_center + 3 * lo, (size_t)(24 * cnt)},
@@ -1697,12 +1681,13 @@ extern "C" int pdbeda_bloblist_stats(pdbeda_bloblist *bl, int64_t *n, double *to
 // too small (or the list is not a whole batch job).
 static int list_stats_one_trip(pdbeda_bloblist *bl, int64_t guess, std::vector<int64_t> &n, std::vector<double> &tot, std::vector<double> &cen,
                                std::vector<int32_t> &grp, const D2HItem *extra = nullptr) {      // (extra: one more result of the caller's, in the same pack and wait)
-    pdbeda_ctx *ctx = bl->ctx;
-    const Job &job = bl->job;
+    LabelJob *lj = bl->job;
+    pdbeda_ctx *ctx = lj->ctx;
+    const Job &job = lj->job;
     guess = std::min<int64_t>(guess, (int64_t)job.blob_cap);
-    const bool whole_job = !bl->whole_map && bl->vol_lo == 0 && bl->vol_hi == job.n_vols;
+    const bool whole_job = !lj->whole_map && bl->vol_lo == 0 && bl->vol_hi == job.n_vols;
     const int64_t extra_bytes = extra ? (int64_t)extra->bytes + 64 : 0;
-    if (!bl->have_counts && whole_job && guess > 0 && 44 * guess + 4096 + extra_bytes < (int64_t)pinned_room(ctx)) {
+    if (!lj->have_counts && whole_job && guess > 0 && 44 * guess + 4096 + extra_bytes < (int64_t)pinned_room(ctx)) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         n.resize((size_t)guess); tot.resize((size_t)guess); cen.resize(3 * (size_t)guess); grp.resize((size_t)guess);
         Counters ctr;
@@ -1712,7 +1697,7 @@ static int list_stats_one_trip(pdbeda_bloblist *bl, int64_t guess, std::vector<i
         HIP_TRY(ctx, d2h_many(ctx, parts, 6));
         HIP_TRY(ctx, ctx_sync(ctx));
         if (ctr.unit_wait_failed) return fail(ctx, PDBEDA_ERR_DEVICE, "sphere batch: the device's volumes outgrew what the host sized the job for");
-        bl->rank_lo = 0; bl->rank_hi = ctr.n_blobs; bl->job_blobs = ctr.n_blobs; bl->have_counts = true;
+        job_record_counts(lj, ctr);
         if ((int64_t)ctr.n_blobs <= guess) {
             const size_t nb = ctr.n_blobs;
             n.resize(nb); tot.resize(nb); cen.resize(3 * nb); grp.resize(nb);
@@ -1727,37 +1712,34 @@ static int list_stats_one_trip(pdbeda_bloblist *bl, int64_t guess, std::vector<i
     return pdbeda_bloblist_stats(bl, n.data(), tot.data(), cen.data(), nullptr, nullptr, nullptr, grp.data());
 }
 
-// Voxel lists are materialised once per JOB (shared by the lists of a fused call through
-// the owning list).
-
+// Voxel lists are materialised once per JOB (every list of a fused call reads its part of them).
 static int list_materialise_voxels(pdbeda_bloblist *bl) {
-    pdbeda_bloblist *ow = owner_of(bl);
-    if (ow->voxels_done) return 0;
-    pdbeda_ctx *ctx = bl->ctx;
+    LabelJob *lj = bl->job;
+    if (lj->voxels_done) return 0;
+    pdbeda_ctx *ctx = lj->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    {   // the job's blob count: one read of the counters per list, not one more here (every caller has resolved its counts;
+    {   // the job's blob count: one read of the counters per job, not one more here (every caller has resolved its counts;
         // a whole-map job that overflowed its typical-size arena has been run again by then)
         const int rc_counts = list_resolve_counts(bl);
         if (rc_counts) return rc_counts;
-        ow = owner_of(bl);
     }
-    Job &job = ow->job;
-    const int64_t nb = bl->job_blobs;
+    const Job &job = lj->job;
+    const int64_t nb = lj->n_blobs;
     // total voxels unknown until the offsets scan; bound by key bits
     const int64_t max_vox = job.key_words * 64;
-    int rc = arena_carve(ctx, "voxel lists", &ow->vox_arena, [&](Carver &cv) {
-        cv.take(ow->offsets_dev, nb + 1);
-        cv.take(ow->cursor_dev, std::max<int64_t>(nb, 1));
-        cv.take(ow->crs_dev, 3 * std::max<int64_t>(max_vox, 1));
+    int rc = arena_carve(ctx, "voxel lists", &lj->vox_arena, [&](Carver &cv) {
+        cv.take(lj->offsets_dev, nb + 1);
+        cv.take(lj->cursor_dev, std::max<int64_t>(nb, 1));
+        cv.take(lj->crs_dev, 3 * std::max<int64_t>(max_vox, 1));
     });
     if (rc) return rc;
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_blob_offsets, dim3(1), dim3(1024), 0, st, job, ow->offsets_dev, ow->cursor_dev);
+    hipLaunchKernelGGL(k_blob_offsets, dim3(1), dim3(1024), 0, st, job, lj->offsets_dev, lj->cursor_dev);
     if (job.total_words > 0)
-        hipLaunchKernelGGL(k_voxel_lists, dim3(grid_for(job.total_words * 64, 256, 8192)), dim3(256), 0, st, job, ow->offsets_dev,
-                           ow->cursor_dev, ow->crs_dev);
+        hipLaunchKernelGGL(k_voxel_lists, dim3(grid_for(job.total_words * 64, 256, 8192)), dim3(256), 0, st, job, lj->offsets_dev,
+                           lj->cursor_dev, lj->crs_dev);
     HIP_TRY(ctx, hipGetLastError());
-    ow->voxels_done = true;      // (enqueued: whatever reads the lists is ordered behind them on the stream, and waits there)
+    lj->voxels_done = true;      // (enqueued: whatever reads the lists is ordered behind them on the stream, and waits there)
     return 0;
 }
 
@@ -1768,11 +1750,12 @@ extern "C" int64_t pdbeda_bloblist_num_voxels(pdbeda_bloblist *bl) {
     if (bl->n_voxels >= 0) return bl->n_voxels;
     rc = list_materialise_voxels(bl);
     if (rc) return rc;
-    pdbeda_ctx *ctx = bl->ctx;
-    pdbeda_bloblist *ow = owner_of(bl);
+    const LabelJob *lj = bl->job;
+    pdbeda_ctx *ctx = lj->ctx;
+    const RankRange r = list_ranks(bl);
     int64_t off[2] = {0, 0};
-    HIP_TRY(ctx, d2h(ctx, &off[0], ow->offsets_dev + bl->rank_lo, 8));
-    HIP_TRY(ctx, d2h(ctx, &off[1], ow->offsets_dev + bl->rank_hi, 8));
+    HIP_TRY(ctx, d2h(ctx, &off[0], lj->offsets_dev + r.lo, 8));
+    HIP_TRY(ctx, d2h(ctx, &off[1], lj->offsets_dev + r.hi, 8));
     HIP_TRY(ctx, ctx_sync(ctx));
     bl->n_voxels = off[1] - off[0];
     return bl->n_voxels;
@@ -1782,15 +1765,16 @@ extern "C" int pdbeda_bloblist_voxels(pdbeda_bloblist *bl, int32_t *crs, int64_t
     if (!bl || bl->freed) return PDBEDA_ERR_ARGUMENT;
     int64_t nv = pdbeda_bloblist_num_voxels(bl);
     if (nv < 0) return (int)nv;
-    pdbeda_ctx *ctx = bl->ctx;
-    pdbeda_bloblist *ow = owner_of(bl);
-    const int64_t cnt = bl->rank_hi - bl->rank_lo;
+    const LabelJob *lj = bl->job;
+    pdbeda_ctx *ctx = lj->ctx;
+    const RankRange r = list_ranks(bl);
+    const int64_t cnt = r.hi - r.lo;
     std::vector<int64_t> off(cnt + 1);
-    HIP_TRY(ctx, d2h(ctx, off.data(), ow->offsets_dev + bl->rank_lo, 8 * (cnt + 1))); HIP_TRY(ctx, ctx_sync(ctx));
+    HIP_TRY(ctx, d2h(ctx, off.data(), lj->offsets_dev + r.lo, 8 * (cnt + 1))); HIP_TRY(ctx, ctx_sync(ctx));
     const int64_t base = off[0];
     if (blob_offsets)
         for (int64_t i = 0; i <= cnt; ++i) blob_offsets[i] = off[i] - base;
-    if (crs && nv > 0) HIP_TRY(ctx, d2h(ctx, crs, ow->crs_dev + 3 * base, 12 * nv)); HIP_TRY(ctx, ctx_sync(ctx));
+    if (crs && nv > 0) HIP_TRY(ctx, d2h(ctx, crs, lj->crs_dev + 3 * base, 12 * nv)); HIP_TRY(ctx, ctx_sync(ctx));
     return PDBEDA_OK;
 }
 
@@ -1804,8 +1788,10 @@ extern "C" int pdbeda_bloblist_voxels(pdbeda_bloblist *bl, int32_t *crs, int64_t
 static int list_moments_compute(pdbeda_bloblist *bl) {
     const int64_t nv = pdbeda_bloblist_num_voxels(bl);      // (resolves the counts and materialises the voxel lists)
     if (nv < 0) return (int)nv;
-    pdbeda_ctx *ctx = bl->ctx;
-    const int64_t cnt = bl->rank_hi - bl->rank_lo;
+    const LabelJob *lj = bl->job;
+    pdbeda_ctx *ctx = lj->ctx;
+    const RankRange ranks = list_ranks(bl);
+    const int64_t cnt = ranks.hi - ranks.lo;
     if (cnt == 0 || nv == 0) { bl->shape_done = true; return PDBEDA_OK; }
     // What the accumulators hold: F = fix_of(|rho|) < 2^39 (map_fix_mul keeps 2^22 max |rho| inside 61 bits).  The low limbs of the two-limb sums are
     // below 2^32 per voxel and are read as signed 64-bit: fewer than 2^31 voxels in the list.  sum F is ONE 64-bit word, and the high limb of F d d' is
@@ -1813,11 +1799,10 @@ static int list_moments_compute(pdbeda_bloblist *bl) {
     // bounds sum F and 2^61 * 2^30 / 2^32 the high limbs; a sphere / list batch may meet a stored voxel again through the periodic wrap, so only its
     // voxel count bounds it: below 2^24 voxels sum F < 2^63 and the high limbs < 2^61.
     if (cnt >= (1ll << 31) || nv >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a list of 2^31 blobs or voxels, or more");
-    if (!bl->whole_map && nv >= (1ll << 24)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a sphere / list batch of 2^24 voxels or more");
-    pdbeda_map *m = bl->map;
+    if (!lj->whole_map && nv >= (1ll << 24)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a sphere / list batch of 2^24 voxels or more");
+    pdbeda_map *m = lj->map;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc = map_fix_mul(m)) return rc;      // (known since the labelling call, unless the map was invalidated meanwhile)
-    pdbeda_bloblist *ow = owner_of(bl);
     const size_t nb = (size_t)cnt;
     BlobShapeArgs a;
     unsigned long long *d_widest = nullptr;
@@ -1836,7 +1821,7 @@ static int list_moments_compute(pdbeda_bloblist *bl) {
     if (rc_arena) return rc_arena;
     auto run = [&]() -> int {
         a.geom = m->geom_dev; a.dens = m->dens;
-        a.crs = ow->crs_dev; a.off = ow->offsets_dev + bl->rank_lo; a.cnt = cnt;
+        a.crs = lj->crs_dev; a.off = lj->offsets_dev + ranks.lo; a.cnt = cnt;
         a.fix_mul = m->fix_mul;
         hipStream_t st = ctx->stream;
         const unsigned chunks = (unsigned)((nv + BS_CHUNK - 1) / BS_CHUNK);
@@ -1868,7 +1853,7 @@ static int list_moments_compute(pdbeda_bloblist *bl) {
 extern "C" int pdbeda_bloblist_moments(pdbeda_bloblist *bl, int32_t *box_lo, int32_t *box_hi, int32_t *extreme_crs, float *extreme, int64_t *s1, int64_t *s2,
                                        double *sw, double *sw1, double *sw2) {
     if (!bl || bl->freed) return PDBEDA_ERR_ARGUMENT;
-    if (bl->ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    if (bl->job->ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     if (!bl->shape_done)
         if (int rc = list_moments_compute(bl)) return rc;
     const size_t cnt = bl->shape_l.size() / 9;
@@ -1891,25 +1876,26 @@ extern "C" int pdbeda_bloblist_moments(pdbeda_bloblist *bl, int32_t *box_lo, int
 
 extern "C" int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host) {
     if (!bl || bl->freed || !labels_host) return PDBEDA_ERR_ARGUMENT;
-    if (!bl->whole_map) return fail(bl->ctx, PDBEDA_ERR_STATE, "dense labels exist only for whole-map blob lists");
-    pdbeda_ctx *ctx = bl->ctx;
+    const LabelJob *lj = bl->job;
+    pdbeda_ctx *ctx = lj->ctx;
+    if (!lj->whole_map) return fail(ctx, PDBEDA_ERR_STATE, "dense labels exist only for whole-map blob lists");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     {   // a job whose unit tiles waited in vain (k_face_merge) has no valid labels either: the same check the blob table makes
         const int rc_counts = list_resolve_counts(bl);
         if (rc_counts) return rc_counts;
     }
-    const Geom &g = bl->map->geom;
+    const Geom &g = lj->map->geom;
     const int uc = g.unique_ncrs[0], ur = g.unique_ncrs[1], us = g.unique_ncrs[2];
     const int64_t nvox = (int64_t)uc * ur * us;
     // scratch: [signed volume if it was not requested at labelling time] + decoded volume
-    const bool have = bl->labels_dev && bl->labels_done;
+    const bool have = lj->labels_dev && lj->labels_done;
     Arena a;
     int32_t *decoded = nullptr, *tmp = nullptr;
     int rc = arena_carve(ctx, "labels", &a, [&](Carver &cv) { cv.take(decoded, nvox); if (!have) cv.take(tmp, nvox); });
     if (rc) return rc;
-    const int32_t *signed_vol = bl->labels_dev;
+    const int32_t *signed_vol = lj->labels_dev;
     if (!have) {
-        launch_labels<false>(ctx, bl->job, bl->td, tmp, bl->map->geom_dev);
+        launch_labels<false>(ctx, lj->job, lj->td, tmp, lj->map->geom_dev);
         signed_vol = tmp;
     }
     hipLaunchKernelGGL(k_labels_decode, dim3(grid_for(nvox, 256, 4096)), dim3(256), 0, ctx->stream, signed_vol, nvox, bl->sign, decoded);
@@ -1930,12 +1916,13 @@ extern "C" int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host)
 extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, const int32_t *offsets, int64_t n_offsets, int32_t *index, int32_t *partner,
                                        int32_t *voxel, int32_t *partner_voxel) {
     if (!a || !b || a->freed || b->freed) return PDBEDA_ERR_ARGUMENT;
-    pdbeda_ctx *ctx = a->ctx;
+    const LabelJob *ja = a->job, *jb = b->job;
+    pdbeda_ctx *ctx = ja->ctx;
     if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     if (a == b) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: a list against itself");
-    if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: the lists belong to different contexts");
-    if (!a->whole_map || !b->whole_map) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: both lists must be whole-map lists");
-    const Geom &g = a->map->geom, &gb = b->map->geom;
+    if (jb->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: the lists belong to different contexts");
+    if (!ja->whole_map || !jb->whole_map) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: both lists must be whole-map lists");
+    const Geom &g = ja->map->geom, &gb = jb->map->geom;
     for (int k = 0; k < 3; ++k)
         if (g.unique_ncrs[k] != gb.unique_ncrs[k]) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: the maps of the two lists have different uniqueNcrs");
     if (n_offsets < 0 || n_offsets > BN_MAX_OFFSETS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: a table of %lld offsets (the limit is %d)", (long long)n_offsets, BN_MAX_OFFSETS);
@@ -1948,10 +1935,11 @@ extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, c
                 return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: offset %lld has the component %d (the limit is +-%d)", (long long)t, o[k], BN_MAX_COMPONENT);
         packed[(size_t)t] = blobnear_pack(o[0], o[1], o[2]);
     }
-    // the counts of both lists first: a job that overflowed its typical-size arena runs again now (both lists of a fused call move with it)
+    // the counts of both lists first: a job that overflowed its typical-size arena runs again now
     if (int rc = list_resolve_counts(a)) return rc;
     if (int rc = list_resolve_counts(b)) return rc;
-    const int64_t cnt = a->rank_hi - a->rank_lo, cnt_b = b->rank_hi - b->rank_lo;
+    const RankRange ra = list_ranks(a), rb = list_ranks(b);
+    const int64_t cnt = ra.hi - ra.lo, cnt_b = rb.hi - rb.lo;
     auto no_pairs = [&]() {
         for (int64_t i = 0; i < cnt; ++i) {
             if (index) index[i] = -1;
@@ -1966,9 +1954,8 @@ extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, c
     if (nv == 0) return no_pairs();
     if (cnt >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: a list of 2^31 blobs or more");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pdbeda_bloblist *ow = owner_of(a);
     const int64_t nvox = (int64_t)g.unique_ncrs[0] * g.unique_ncrs[1] * g.unique_ncrs[2];
-    const bool have = b->labels_dev && b->labels_done;
+    const bool have = jb->labels_dev && jb->labels_done;
     const size_t nb = (size_t)cnt;
     BlobNearArgs args;
     uint32_t *d_table = nullptr;
@@ -1986,12 +1973,12 @@ extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, c
         hipStream_t st = ctx->stream;
         HIP_TRY(ctx, h2d_one(ctx, d_table, packed.data(), sizeof(uint32_t) * (size_t)n_offsets));
         HIP_TRY(ctx, hipMemsetAsync(args.best, 0xFF, sizeof(unsigned long long) * nb, st));
-        const int32_t *signed_vol = b->labels_dev;
+        const int32_t *signed_vol = jb->labels_dev;
         if (!have) {
-            launch_labels<false>(ctx, b->job, b->td, tmp, b->map->geom_dev);
+            launch_labels<false>(ctx, jb->job, jb->td, tmp, jb->map->geom_dev);
             signed_vol = tmp;
         }
-        args.crs = ow->crs_dev; args.off = ow->offsets_dev + a->rank_lo; args.cnt = cnt;
+        args.crs = ja->crs_dev; args.off = ja->offsets_dev + ra.lo; args.cnt = cnt;
         args.labels = signed_vol; args.sign = b->sign;
         args.uc = g.unique_ncrs[0]; args.ur = g.unique_ncrs[1]; args.us = g.unique_ncrs[2];
         args.table = d_table; args.n_off = (int32_t)n_offsets;
@@ -2025,21 +2012,18 @@ extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, c
 extern "C" int pdbeda_bloblist_free(pdbeda_bloblist *bl) {
     if (!bl) return PDBEDA_ERR_ARGUMENT;
     if (bl->freed) return PDBEDA_ERR_STATE;
-    pdbeda_ctx *ctx = bl->ctx;
+    LabelJob *lj = bl->job;
+    pdbeda_ctx *ctx = lj->ctx;
     bl->freed = true;
     ctx->live_handles--;
-    bl->shape_done = false;      // (the rows go with the list, also while the other list of a fused call keeps the struct alive)
+    bl->shape_done = false;      // (the rows go with the list, also while another list keeps the job alive)
     std::vector<int32_t>().swap(bl->shape_i); std::vector<int64_t>().swap(bl->shape_l); std::vector<double>().swap(bl->shape_d);
-    pdbeda_bloblist *ow = owner_of(bl);
-    pdbeda_bloblist *other = bl->sibling;
-    const bool other_alive = other && !other->freed;
-    if (!other_alive) {
+    if (--lj->live == 0) {
         // last list of the job.  Arenas are recycled only inside this context, i.e. by work that
         // is enqueued later on the SAME stream, so stream order protects them: no host sync.
-        arena_put(ctx, ow->arena);
-        arena_put(ctx, ow->vox_arena);
-        if (other) delete other;
-        delete bl;
+        arena_put(ctx, lj->arena);
+        arena_put(ctx, lj->vox_arena);
+        delete lj;
     }
     return PDBEDA_OK;
 }
@@ -2081,11 +2065,11 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
     for (int p = 0; p < a.n_planes; ++p) {
         pdbeda_bloblist *bl = pj->blobs[p];
         if (!bl) continue;
-        if (bl->labels_dev && bl->labels_done) have[p] = bl->labels_dev;
+        if (bl->job->labels_dev && bl->job->labels_done) have[p] = bl->job->labels_dev;
         else need_own[p] = true;
     }
     // (the two lists of ONE fused labelling job: one signed volume serves both planes)
-    const bool shared = need_own[0] && need_own[1] && pj->blobs[0]->job.ctr == pj->blobs[1]->job.ctr;
+    const bool shared = need_own[0] && need_own[1] && pj->blobs[0]->job == pj->blobs[1]->job;
     if (shared) need_own[1] = false;
     const int rc = arena_carve(ctx, "peak search", &pj->arena, [&](Carver &cv) {
         a.ctr = cv.take<PeakCounters>(1);
@@ -2115,7 +2099,7 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
     hipError_t e = hipSuccess;
     {   // (nothing to clear: the stencil stores every tile's counts, the scan every counter)
         for (int p = 0; p < a.n_planes; ++p)
-            if (need_own[p]) launch_labels<false>(ctx, pj->blobs[p]->job, pj->blobs[p]->td, const_cast<int32_t *>(a.plane[p].labels), m->geom_dev);
+            if (need_own[p]) launch_labels<false>(ctx, pj->blobs[p]->job->job, pj->blobs[p]->job->td, const_cast<int32_t *>(a.plane[p].labels), m->geom_dev);
         const dim3 grid((unsigned)((a.uc + PK_C - 1) / PK_C), (unsigned)((a.ur + PK_R - 1) / PK_R), (unsigned)((a.us + PK_S - 1) / PK_S));
         { PROF(ctx, "k_peak_stencil"); hipLaunchKernelGGL(k_peak_stencil, grid, dim3(PK_THREADS), 0, ctx->stream, a, m->dens); }
         { PROF(ctx, "k_peak_scan"); hipLaunchKernelGGL(k_peak_scan, dim3(1), dim3(PK_SCAN_THREADS), 0, ctx->stream, a); }
@@ -2132,9 +2116,10 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
 static int peaks_check_blobs(pdbeda_map *m, pdbeda_bloblist *bl, int sign, float cutoff) {
     if (!bl) return PDBEDA_OK;
     pdbeda_ctx *ctx = m->ctx;
-    if (bl->freed || !bl->whole_map || bl->map != m || bl->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "peaks: the blob list is not a whole-map list of this map");
-    if (bl->sign != sign || (sign > 0 ? bl->cut_pos : bl->cut_neg) != cutoff)
-        return fail(ctx, PDBEDA_ERR_ARGUMENT, "peaks: the blob list was made with another cutoff (%g, asked for %g)", (double)(bl->sign > 0 ? bl->cut_pos : bl->cut_neg), (double)cutoff);
+    const LabelJob *lj = bl->job;
+    if (bl->freed || !lj->whole_map || lj->map != m || lj->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "peaks: the blob list is not a whole-map list of this map");
+    if (bl->sign != sign || (sign > 0 ? lj->cut_pos : lj->cut_neg) != cutoff)
+        return fail(ctx, PDBEDA_ERR_ARGUMENT, "peaks: the blob list was made with another cutoff (%g, asked for %g)", (double)(bl->sign > 0 ? lj->cut_pos : lj->cut_neg), (double)cutoff);
     return list_resolve_counts(bl);
 }
 
@@ -2632,13 +2617,11 @@ static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n
         arena_put(ctx, arena);
         return rc ? rc : fail(ctx, PDBEDA_ERR_DEVICE, "grouped blobs: %s", hipGetErrorString(e));
     }
-    pdbeda_bloblist *bl = new_list(ctx, m);
-    bl->job = job;
-    bl->arena = arena;
-    bl->vol_lo = 0;
-    bl->vol_hi = (int)n_groups;
-    bl->host_boxes.swap(gs.host_boxes);
-    *out = bl;
+    LabelJob *lj = new_label_job(ctx, m);
+    lj->job = job;
+    lj->arena = arena;
+    lj->host_boxes.swap(gs.host_boxes);
+    *out = job_view(lj, 0, 0, (int)n_groups, 1);      // (one list over all the volumes)
     return PDBEDA_OK;
 }
 
@@ -3536,7 +3519,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     t_marks[2] = now_s();
 
     // ---- 3. device: pooled voxels -> union job (a group per residue + the domain group) ----
-    pdbeda_bloblist *cow = owner_of(clouds);
+    const LabelJob *cj = clouds->job;
     std::vector<int32_t> pool_group((size_t)n_pool), group_res;     // compact residue groups in increasing order
     for (int64_t p = 0; p < n_pool; ++p) {
         const int32_t r = at->residue[pool_atom[(size_t)p]];
@@ -3606,7 +3589,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     std::vector<VolDesc> union_vols((size_t)n_groups);
     {
         std::vector<int64_t> lo(3 * (size_t)n_groups, INT64_MAX), hi(3 * (size_t)n_groups, INT64_MIN);
-        const bool have_boxes = (int64_t)cow->host_boxes.size() == n;      // (the sphere job's own boxes, made by the host with the same statements: two xyz2crs per pooled cloud were 0.06 ms here)
+        const bool have_boxes = (int64_t)cj->host_boxes.size() == n;      // (the sphere job's own boxes, made by the host with the same statements: two xyz2crs per pooled cloud were 0.06 ms here)
         int64_t last_a = -1;
         bool cur_empty = false;
         AtomBox bx = {{0, 0, 0}, {-1, -1, -1}};
@@ -3614,7 +3597,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
             const int64_t a = at->alias[pool_atom[(size_t)p]];          // (the clouds are those of the coordinate's last atom: its coordinate, its radius)
             if (a != last_a) {
                 if (have_boxes) {
-                    bx = cow->host_boxes[(size_t)a];
+                    bx = cj->host_boxes[(size_t)a];
                 } else {
                     int32_t C[3], R[3];
                     xyz2crs(m->geom, at->xyz + 3 * a, C);
@@ -3668,7 +3651,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     if (e != hipSuccess) { arena_put(ctx, gs.in_arena); return fail_dev(e, nullptr); }
     PoolPaint paint;
     memset(&paint, 0, sizeof paint);
-    paint.src_crs = cow->crs_dev; paint.src_off = cow->offsets_dev;
+    paint.src_crs = cj->crs_dev; paint.src_off = cj->offsets_dev;
     paint.pool_cloud = d_pool_cloud; paint.pool_voff = d_pool_voff; paint.pool_group = d_pool_group;
     paint.n_pool = (int)n_pool; paint.domain_group = n_rg; paint.V = V;
     paint.set_off = d_set_off; paint.pair_a = d_pa; paint.pair_b = d_pb; paint.touch = d_touch; paint.n_pairs = (int)n_pairs;
@@ -3677,9 +3660,9 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     if (!fused_paint) {
         e = flush_pending(ctx, &gs);      // (these two read the aux block)
         if (e != hipSuccess) { arena_put(ctx, gs.in_arena); return fail_dev(e, nullptr); }
-        { PROF(ctx, "k_pool_gather"); hipLaunchKernelGGL(k_pool_gather, dim3(grid_for(2 * V, 256)), dim3(256), 0, st, cow->crs_dev, cow->offsets_dev, d_pool_cloud, d_pool_voff,
+        { PROF(ctx, "k_pool_gather"); hipLaunchKernelGGL(k_pool_gather, dim3(grid_for(2 * V, 256)), dim3(256), 0, st, cj->crs_dev, cj->offsets_dev, d_pool_cloud, d_pool_voff,
                                                          d_pool_group, (int)n_pool, V, n_rg, gs.d_crs, gs.d_item_group); }
-        if (n_pairs > 0) { PROF(ctx, "k_test_overlap"); hipLaunchKernelGGL(k_test_overlap, dim3((unsigned)n_pairs), dim3(256), 0, st, cow->crs_dev, d_set_off, d_pa, d_pb, d_touch); }
+        if (n_pairs > 0) { PROF(ctx, "k_test_overlap"); hipLaunchKernelGGL(k_test_overlap, dim3((unsigned)n_pairs), dim3(256), 0, st, cj->crs_dev, d_set_off, d_pa, d_pb, d_touch); }
     }
     if (host_sized) {
         gs.d_vols = d_union_vols;          // (in the aux block, which outlives the job's enqueue)
@@ -3712,7 +3695,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         memset(&u_ctr, 0, sizeof u_ctr);
         UnionFinish fin;
         memset(&fin, 0, sizeof fin);
-        fin.src_crs = cow->crs_dev; fin.src_off = cow->offsets_dev; fin.pool_cloud = d_pool_cloud; fin.pool_group = d_pool_group;
+        fin.src_crs = cj->crs_dev; fin.src_off = cj->offsets_dev; fin.pool_cloud = d_pool_cloud; fin.pool_group = d_pool_group;
         fin.n_pool = (int)n_pool; fin.domain_group = n_rg; fin.touch = d_touch; fin.n_pairs = (int)n_pairs; fin.cap = (unsigned int)u_cap;
         // (the takes fin_bytes made room for; as before a failed launch below keeps them until the next wait and, through fail(), delivers nothing)
         fin.out_ctr = reinterpret_cast<Counters *>(pinned_take(ctx, sizeof u_ctr, &u_ctr));
@@ -3722,8 +3705,8 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         fin.out_group = reinterpret_cast<int32_t *>(pinned_take(ctx, 4 * (size_t)u_cap, u_grp.data()));
         fin.out_touch = reinterpret_cast<unsigned int *>(pinned_take(ctx, 4 * (size_t)np1, n_pairs ? touch.data() : nullptr));      // (no pair: a line of its own all the same, nothing delivered)
         fin.out_comp = reinterpret_cast<int32_t *>(pinned_take(ctx, 8 * (size_t)n_pool, comp.data()));
-        const int64_t fin_threads = std::max<int64_t>(std::max<int64_t>(uni->job.run_cap, 2 * n_pool), n_pairs);
-        { PROF(ctx, "k_union_finish"); hipLaunchKernelGGL(k_union_finish, dim3(grid_for(fin_threads, 256, 1024)), dim3(256), 0, st, uni->job, m->geom_dev, fin); }
+        const int64_t fin_threads = std::max<int64_t>(std::max<int64_t>(uni->job->job.run_cap, 2 * n_pool), n_pairs);
+        { PROF(ctx, "k_union_finish"); hipLaunchKernelGGL(k_union_finish, dim3(grid_for(fin_threads, 256, 1024)), dim3(256), 0, st, uni->job->job, m->geom_dev, fin); }
         e = hipGetLastError();
         if (e != hipSuccess) return fail_dev(e, uni);
         e = ctx_sync(ctx);      // (the one wait of the union job: everything above lands in the host's arrays)
@@ -3734,7 +3717,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         const size_t nb_u = u_ctr.n_blobs;
         u_n.resize(nb_u); u_tot.resize(nb_u); u_cen.resize(3 * nb_u); u_grp.resize(nb_u);
     } else {
-        { PROF(ctx, "k_pool_component"); hipLaunchKernelGGL(k_pool_component, dim3(grid_for(2 * n_pool, 256)), dim3(256), 0, st, uni->job, cow->crs_dev, cow->offsets_dev, d_pool_cloud,
+        { PROF(ctx, "k_pool_component"); hipLaunchKernelGGL(k_pool_component, dim3(grid_for(2 * n_pool, 256)), dim3(256), 0, st, uni->job->job, cj->crs_dev, cj->offsets_dev, d_pool_cloud,
                                                             d_pool_group, (int)n_pool, n_rg, d_comp); }
         e = hipGetLastError();
         if (e != hipSuccess) return fail_dev(e, uni);

@@ -133,3 +133,107 @@ def test_unit_tile_beside_ordinary_tiles(gpu_ctx):
         c = run["counters"]
         assert c["unit_tiles_runs"] + c["unit_tiles_comps"] > 0, c      # the fallback path really ran
         assert c["reruns"] == 1, c                                      # ... as the second run of its job
+
+
+# ---- the lifetime of a fused job's two lists ----------------------------------------------------------------------------
+# One list of a fused green / red call is freed while the other is still read.  What the survivor reads -- its part of the
+# job's blob table, the job's voxel lists, the label volume written on demand, its moment rows -- is compared with a
+# separate single-sign job on the same map: the same columns to the byte (`group`, the list's plane inside its job, is 1
+# for the red list of a fused job and 0 for a job of its own: not compared), the same labels, the same voxels per blob.
+MOMENT_KEYS = ("boxLo", "boxHi", "extremeCrs", "extreme", "s1", "s2", "sw", "sw1", "sw2")
+_lifetime_refs = {}
+
+
+def _lifetime_case(name, gpu_ctx):
+    """-> (map, cut, {sign: what a separate full_blobs(sign * cut) reads}); made once per grid and left unchanged"""
+    if name not in _lifetime_refs:
+        from pdb_eda_amd import synthetic
+        if name == "rerun":          # the grid of test_unit_tile_beside_ordinary_tiles
+            g = synthetic.smooth_noise((16, 16, 128), 53, 1.5)
+            cut = _noise_cut(g)
+            amp = np.float32(2.0 * cut)
+            g[:8, :8, 0::2] = amp
+            g[:8, :8, 1::2] = -amp
+        else:                        # the grid of test_one_tile_column
+            g = synthetic.smooth_noise((24, 24, 64), 51, 1.5)
+            cut = _noise_cut(g)
+        dm = _dm(g, gpu_ctx)
+        refs = {}
+        for sign in (1, -1):
+            bl = dm._map.full_blobs(sign * cut)
+            refs[sign] = _read_all(bl, dm)
+            bl.free()
+        _lifetime_refs[name] = (dm, cut, refs)
+    return _lifetime_refs[name]
+
+
+def _read_all(bl, dm, what=("len", "stats", "voxels", "labels", "moments", "counters")):
+    out = {}
+    if "len" in what:
+        out["len"] = len(bl)
+    if "stats" in what:
+        st = bl.stats()
+        out["stats"] = {k: np.array(st[k]) for k in STAT_KEYS}
+    if "voxels" in what:
+        crs, off = bl.voxels()
+        out["crs"], out["off"] = np.array(crs), np.array(off)
+    if "labels" in what:
+        out["labels"] = np.array(bl.labels(dm._map.unique_shape))
+    if "moments" in what:
+        mo = bl.moments()
+        out["moments"] = {k: np.array(mo[k]) for k in MOMENT_KEYS}
+    if "counters" in what:
+        out["counters"] = bl.counters()
+    return out
+
+
+def _assert_same_list(got, want):
+    if "len" in got:
+        assert got["len"] == want["len"] and got["len"] > 0
+    if "stats" in got:
+        for k in STAT_KEYS:
+            assert got["stats"][k].tobytes() == want["stats"][k].tobytes(), k
+    if "moments" in got:
+        for k in MOMENT_KEYS:
+            assert got["moments"][k].tobytes() == want["moments"][k].tobytes(), k
+    if "labels" in got:
+        assert np.array_equal(got["labels"], want["labels"])
+    if "crs" in got:
+        assert np.array_equal(got["off"], want["off"])
+        assert np.array_equal(_sorted_lists(got), _sorted_lists(want))
+
+
+@pytest.mark.parametrize("name,reruns", [("rerun", 1), ("plain", 0)])
+def test_green_freed_before_any_accessor(gpu_ctx, name, reruns):
+    """A fused job without a label volume; the green list is freed before anything was read, then the red list is read in
+    full: on the map whose job runs again (the survivor alone moves to the second run) and on one whose job does not."""
+    dm, cut, refs = _lifetime_case(name, gpu_ctx)
+    green, red = dm._map.full_blobs_pm(cut, -cut)
+    green.free()
+    got = _read_all(red, dm)
+    red.free()
+    assert got["counters"]["reruns"] == reruns, got["counters"]
+    _assert_same_list(got, refs[-1])
+
+
+def test_red_freed_before_any_accessor(gpu_ctx):
+    """The mirror image on the map whose job runs again: the red list goes first, the green list is read."""
+    dm, cut, refs = _lifetime_case("rerun", gpu_ctx)
+    green, red = dm._map.full_blobs_pm(cut, -cut)
+    red.free()
+    got = _read_all(green, dm)
+    green.free()
+    assert got["counters"]["reruns"] == 1, got["counters"]
+    _assert_same_list(got, refs[1])
+
+
+def test_list_freed_between_the_rerun_and_the_voxel_lists(gpu_ctx):
+    """len(green) runs the job again; green is freed; the voxel lists and the moment rows are then made for red alone."""
+    dm, cut, refs = _lifetime_case("rerun", gpu_ctx)
+    green, red = dm._map.full_blobs_pm(cut, -cut)
+    assert len(green) == refs[1]["len"]
+    green.free()
+    got = _read_all(red, dm, what=("voxels", "moments", "counters"))
+    red.free()
+    assert got["counters"]["reruns"] == 1, got["counters"]
+    _assert_same_list(got, refs[-1])
