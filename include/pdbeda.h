@@ -366,6 +366,16 @@ int pdbeda_map_partition(pdbeda_map *map, const double *xyz, int64_t n_atoms, fl
  * pooled clouds under testOverlap, merged (644-650, 661-690), the domain clouds = the same over everything pooled
  * (692-712) and the totals behind densityElectronRatio (714-731).  Voxel lists never leave the device.
  *
+ * What tests/test_gpu_cloud.py pins beyond that: an atom whose alias is another atom gets that atom's clouds -- the sphere around
+ * the shared coordinate with the ALIAS's radius -- measured from its own coordinate; when two pooled atoms of one residue share
+ * a coordinate their clouds carry the later atom's electrons only, atoms of different residues each count.  A sphere may leave
+ * the stored box: a voxel with a raw index below 0 or >= ncrs has the density of the voxel it wraps to by the cell's interval,
+ * and density 0 (so it is in no cloud) where the cell is not stored there; centroids are those of the raw, unwrapped positions.  Among
+ * equally distant clouds the first in list order is the best one; a residue without a pooled cloud has no row and leaves no gap
+ * in the others' ordinals, which are the caller's.  n == 0, or no pooled cloud at all, succeeds with empty tables, zero totals,
+ * every owner in state 0 and a NaN cut-off when no atom has a cloud.  PDBEDA_ERR_ARGUMENT for an alias, key, owner key or bonded
+ * key out of range and for decreasing residue ordinals; a failing call leaves the context usable.
+ *
  * The caller flattens what the reference reads from the structure, in the reference's iteration order
  * (residues with id[0] == ' ', their child atoms whose residue_atom name has an atom type and whose occupancy != 0): */
 typedef struct pdbeda_cloud_atoms {

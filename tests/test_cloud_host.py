@@ -1,0 +1,243 @@
+"""CPU: the inputs and the yardsticks of tests/test_gpu_cloud.py (pdbeda_aggregate_cloud at large entries, at atoms that leave the
+stored box and at its decision rules), checked before a GPU sees them.
+
+tests/cloud_checker.py -- aggregateCloud restated with sets and dicts -- must equal the oracle composite (oracle/pdbeda_oracle.c
+ora_cloud_*, pinned on the reference's goldens by tests/test_oracle_cloud.py) on every small case of tests/cloud_cases.py and on the
+flattened inputs of the `orth` and `alias` analysis goldens; every crafted case must tell the rule it was built for from that rule's
+mutation; the worlds and the large entry must have the properties the GPU tests rely on; and every prefix of the large entry must
+lie on its side of the three sizes at which pdbeda_aggregate_cloud changes path, by at least 10 %."""
+import numpy as np
+import pytest
+
+from conftest import load_analysis_case
+import batch_limit_cases
+import cloud_cases as cases
+import cloud_checker as checker
+import spheres_checker
+
+
+def oracle_of(header, grid):
+    from oracle import oracle as ora
+    return ora.Oracle(header, grid)
+
+
+def checked(header, grid, oracle, e, mutate=None):
+    clouds = checker.atom_clouds(oracle, e["xyz"], e["radius"], e["cutoff"])
+    return clouds, checker.aggregate_cloud(header, grid, clouds, *[e[k] for k in cases.ARGS if k != "radius"], e["min_electrons"], mutate=mutate)
+
+
+def differs(a, b):
+    try:
+        checker.assert_same_tables(a, b, exact=True)
+    except AssertionError:
+        return True
+    return False
+
+
+# ---- crafted decision cases ------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def crafted():
+    spec, header, grid, entries = cases.crafted()
+    return header, grid, entries, oracle_of(header, grid)
+
+
+MUTATION_OF = {"equidistant": "last_min", "cutoff": "no_cut", "threshold": "gt", "corner": "six", "chain": "six", "ordinals": "first_key",
+               "aliases": "both_alias"}
+
+
+@pytest.mark.parametrize("name", ["equidistant", "cutoff", "threshold", "corner", "chain", "ordinals", "aliases", "no_pairs", "nothing", "empty"])
+def test_checker_equals_oracle_on_crafted_case(crafted, name):
+    """Dyadic densities on voxel centres: every sum is exact, so the tables agree with == (centroids at 1e-12); and the checker with the
+    case's rule mutated gives other tables."""
+    header, grid, entries, oracle = crafted
+    e = entries[name]
+    want = cases.call(oracle, e)
+    _, mine = checked(header, grid, oracle, e)
+    checker.assert_same_tables(mine, want, exact=True, what=name)
+    if name in MUTATION_OF:
+        _, mutated = checked(header, grid, oracle, e, MUTATION_OF[name])
+        assert differs(mutated, want), "%s cannot tell its rule from %s" % (name, MUTATION_OF[name])
+    assert float(grid.max()) <= 8.0 and np.all(grid * 64 == np.rint(grid * 64))
+
+
+def test_crafted_cases_show_what_they_were_built_for(crafted):
+    header, grid, entries, oracle = crafted
+    got = {k: cases.call(oracle, e) for k, e in entries.items()}
+    # equidistant: the two distances tie to the bit, the row carries the first cloud in list order (density 2.0, not 3.0)
+    e = entries["equidistant"]
+    clouds = checker.atom_clouds(oracle, e["xyz"][:1], e["radius"][:1], e["cutoff"])[0]
+    assert len(clouds) == 2 and [c[1] for c in clouds] == [2.0, 3.0]
+    d = [float(np.linalg.norm(e["xyz"][0] - c[2])) for c in clouds]
+    assert d[0] == d[1] == 1.0
+    assert got["equidistant"]["atom_total"][0] == 2.0 and got["equidistant"]["atom_distance"][0] == 1.0
+    # cut-off: 2.777 voxels; X (row 6: two clouds, the nearest 2 voxels away) is kept, Y (3 voxels away) is dropped: margins 0.777 and 0.223 voxels
+    g = got["cutoff"]
+    cut_voxels = g["centroidDistanceCutoff"] / 0.5
+    assert 2.0 < cut_voxels < 3.0 and abs(cut_voxels - 2.7776) < 1e-3
+    assert list(g["atom"]) == [0, 1, 2, 3, 4, 5, 6] and g["atom_distance"][6] == 1.0 and list(g["owner_state"]) == [1] * 7 + [0]
+    # threshold: 25.0 passes, 25 - 2^-40 does not; the totals count the filtered rows
+    g = got["threshold"]
+    assert list(g["res"]["electrons"]) == [25.0] and list(g["dom"]["electrons"]) == [25.0] and list(g["res"]["residue"]) == [0]
+    assert g["totalElectrons"] == 25.0 + (25.0 - 2.0 ** -40) and g["numVoxels"] == 6 and g["totalDensity"] == sum(1.0 + k / 8.0 for k in range(6))
+    # corner contact: offset (1, 1, 1) touches, offset (2, 2, 2) does not
+    g = got["corner"]
+    assert list(g["owner_state"]) == [1, 1, 2, 2] and list(g["res"]["residue"]) == [0, 1, 1] and list(g["res"]["n"]) == [2, 1, 1]
+    # chain: A - B - C in one residue cloud with all three atoms' electrons; A and C do not touch (their owners are incomplete)
+    g = got["chain"]
+    assert list(g["res"]["electrons"]) == [30.0] and list(g["res"]["n"]) == [4] and list(g["owner_state"]) == [2, 1, 2]
+    # ordinals: as given, with the residue without a cloud (5) skipped; the last atom of key 0 decides its owners' state
+    g = got["ordinals"]
+    assert list(g["res"]["residue"]) == [3, 3, 7, 12] and list(g["atom"]) == [0, 1, 2, 4, 5, 6] and list(g["owner_state"]) == [2, 2, 2, 0, 1, 1, 1]
+    # aliases: same residue -> the later atom's electrons only (7 + 8, not 6 + 7 + 8); different residues -> both (6.5 + 7.5); the alias's own (larger) sphere
+    g = got["aliases"]
+    assert list(g["res"]["electrons"]) == [15.0, 6.5, 7.5, 5.5, 8.5] and list(g["dom"]["electrons"]) == [15.0, 14.0, 14.0]
+    assert list(g["atom_n"]) == [1, 1, 1, 1, 1, 2, 2] and g["totalElectrons"] == 43.0
+    # nothing pooled / no atoms: empty tables, zero totals, a NaN cut-off, owners in state 0
+    for name in ("nothing", "empty"):
+        g = got[name]
+        assert len(g["atom"]) == len(g["res"]["n"]) == len(g["dom"]["n"]) == 0 and not g["owner_state"].any() and np.isnan(g["centroidDistanceCutoff"])
+        assert (g["numVoxels"], g["totalElectrons"], g["totalDensity"]) == (0, 0.0, 0.0)
+    assert len(got["nothing"]["owner_state"]) == 3 and len(got["no_pairs"]["owner_state"]) == 0 and len(got["no_pairs"]["res"]["n"]) == 2
+
+
+def test_refused_entries_differ_in_one_argument(crafted):
+    header, grid, entries, oracle = crafted
+    bad = cases.refusals(entries["chain"])
+    assert sorted(bad) == ["alias out of range", "bonded key out of range", "decreasing residues", "key out of range", "owner key out of range"]
+    for what, e in bad.items():
+        assert sum(not np.array_equal(e[k], entries["chain"][k]) for k in cases.ARGS) == 1, what
+    # the bonded key is found after the first job only if its owner is pooled
+    assert 0 in cases.call(oracle, entries["chain"])["atom"] and entries["chain"]["bonded_off"][1] > 0
+
+
+# ---- atoms that leave the stored box; many clouds an atom ------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["smooth", "noise"])
+@pytest.mark.parametrize("name", batch_limit_cases.WORLDS)
+def test_checker_equals_oracle_on_worlds(name, kind):
+    spec, header, grid, e = cases.world_entry(name, kind)
+    oracle = oracle_of(header, grid)
+    want = cases.call(oracle, e)
+    clouds, mine = checked(header, grid, oracle, e)
+    checker.assert_same_tables(mine, want, what="%s %s" % (name, kind))
+    n, ncrs = len(e["xyz"]), np.array(header.ncrs)
+    assert n == cases.WORLD_ATOMS and len(want["atom"]) >= 200 and len(want["res"]["n"]) >= 20 and len(want["dom"]["n"]) >= 20
+    assert all(np.count_nonzero(want["owner_state"] == s) >= 3 for s in (0, 1, 2))
+    pooled = [(a, c[0]) for a in want["atom"] for c in clouds[e["alias"][a]]]
+    outside = [v for _, v in pooled if any(x[k] < 0 or x[k] >= ncrs[k] for x in v for k in range(3))]
+    assert len(outside) >= 20          # pooled clouds with a raw crs component below 0 or at / above ncrs
+    # a residue group (and with it the domain group) whose volume starts below 0: the volume holds the group's voxels
+    assert len({int(e["residue"][a]) for a, v in pooled if min(min(x) for x in v) < 0}) >= 1
+    if kind == "noise":
+        assert sum(len(c) for c in clouds) > 4 * n + 64 and max(len(c) for c in clouds) >= 15          # more clouds than the one-trip guess
+    elif name == "skew":          # atoms whose whole sphere is not stored: zero density, no cloud
+        sp = spheres_checker.atom_spheres(header, grid, e["xyz"], e["radius"])
+        off = sp["offsets"]
+        lost = [a for a in range(n) if not sp["ok"][off[a]:off[a + 1]].any()]
+        assert len(lost) >= 5 and not any(clouds[a] for a in lost)
+        partly = [a for a in range(n) if sp["ok"][off[a]:off[a + 1]].any() and not sp["ok"][off[a]:off[a + 1]].all()]
+        assert len(partly) >= 5 and any(clouds[a] for a in partly)          # and spheres cut by the edge of what is stored, some with a cloud
+
+
+# ---- the analysis goldens' flattened inputs -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["orth", "alias"])
+def test_checker_equals_oracle_on_golden_inputs(name):
+    from pdb_eda_amd import ccp4, synthetic, densityAnalysis
+    from oracle import cpu_entry
+    z, spec, st, pdb, params = load_analysis_case(name)
+    header = ccp4.DensityHeader.fromFileHeader(synthetic.ccp4_header_bytes(spec))
+    densityAnalysis.setGlobals(params)
+    host = cpu_entry.HostDensity(header, z["dens"])
+    inp = densityAnalysis.DensityAnalysis(name, host, None, st, None)._cloudInputs()
+    e = {k: inp[k] for k in cases.ARGS if k != "weight"}
+    e.update(weight=inp["electrons"] * inp["occupancy"], cutoff=host.densityCutoff, min_electrons=25.0)
+    want = cases.call(host._map, e)
+    _, mine = checked(header, host._map.density, host._map, e)
+    assert len(want["atom"]) >= 20 and len(want["res"]["n"]) >= 1
+    assert name != "alias" or np.any(e["alias"] != np.arange(len(e["alias"])))
+    checker.assert_same_tables(mine, want, what=name)
+
+
+# ---- the large entry ---------------------------------------------------------------------------------------------------------------
+PINNED = 4 << 20          # the context's pinned block (pdbeda_hip.hip: pinned_cap)
+STAGED = 1 << 20          # the staged row of the aux block (pdbeda_hip.hip:3642)
+
+
+def _span(b, a):
+    return (b + a - 1) // a * a
+
+
+def switch_points(n, n_pool, n_pairs, n_groups):
+    """What pdbeda_aggregate_cloud compares at its three switch points for an entry of n atoms, n_pool pooled clouds, n_pairs bonded
+    pairs between pooled names and n_groups union groups (residues with a pooled cloud + 1), on an idle pinned block:
+    T1 (pdbeda_hip.hip:3466 -> list_stats_one_trip, 1690)   the clouds' table comes in one trip while 44 * (4 n + 64) + 4096 < PINNED;
+    T2 (3568-3577, 3642)   the uploaded part of the aux block is staged while it is <= STAGED: the carve's items in 256-byte steps --
+                           48-byte volume descriptors, 2 x 4 n_pool, 8 (n_pool + 1), 8 (n + 1), 3 x 4 max(n_pairs, 1);
+    T3 (3680-3689)         k_union_finish delivers while fin_bytes <= PINNED: 64-byte lines of the counters (64 bytes), 8 + 8 + 24 + 4
+                           bytes a row of u_cap = 2 n_pool + 64 rows, 4 max(n_pairs, 1) and 8 n_pool.
+    Small staged inputs (h2d_row: at most 256 KiB) may share the block at those moments: the 10 % that every size keeps from its limit
+    is more than that.  Returns {name: (bytes compared, limit)}; the path below the switch runs while bytes <= limit (T1: <)."""
+    np1 = max(n_pairs, 1)
+    t1 = 44 * (4 * n + 64) + 4096
+    t2 = _span(48 * n_groups, 256) + 2 * _span(4 * n_pool, 256) + _span(8 * (n_pool + 1), 256) + _span(8 * (n + 1), 256) + 3 * _span(4 * np1, 256)
+    u_cap = 2 * n_pool + 64
+    t3 = 64 + 2 * _span(8 * u_cap, 64) + _span(24 * u_cap, 64) + _span(4 * u_cap, 64) + _span(4 * np1, 64) + _span(8 * n_pool, 64)
+    return {"T1": (t1, PINNED), "T2": (t2, STAGED), "T3": (t3, PINNED)}
+
+
+@pytest.fixture(scope="module")
+def big():
+    spec, header, grid, e = cases.big_entry()
+    oracle = oracle_of(header, grid)
+    n_clouds = np.array([len(oracle.find_aberrant_blobs([p], [r], e["cutoff"])) for p, r in zip(e["xyz"], e["radius"])])
+    return e, oracle, n_clouds
+
+
+def test_big_entry_is_what_the_issue_asks_for():
+    spec, header, grid, e = cases.big_entry()
+    n = len(e["xyz"])
+    assert n == 48000 and grid.shape == (224, 224, 224) and tuple(header.crsInterval) == (224, 224, 224)          # the whole cell is stored
+    assert np.array_equal(e["xyz"], e["xyz"].astype(np.float32).astype(np.float64))
+    sizes = np.bincount(e["residue"])
+    assert sizes[:-1].min() >= 6 and sizes.max() <= 10 and np.all(np.diff(e["residue"]) >= 0)
+    assert np.array_equal(e["key"], np.arange(n)) and np.array_equal(e["owner_key"], np.arange(n)) and np.array_equal(e["alias"], np.arange(n))
+    assert set(np.unique(e["radius"])) == {np.float32(0.74), np.float32(0.8), np.float32(0.9)} and len(np.unique(e["weight"])) > n // 2
+    src = np.repeat(np.arange(n), np.diff(e["bonded_off"]))
+    assert np.all(e["residue"][src] == e["residue"][e["bonded"]]) and np.all(np.abs(src - e["bonded"]) <= 2) and np.all(src != e["bonded"])
+
+
+def test_big_sizes_lie_on_their_sides_of_the_switch_points(big):
+    """T1-T3 as switch_points() states them (with the source lines): 11 000 atoms below all three, 19 000 between T2 and T1, 29 000
+    between T1 and T3, 48 000 above all; every compared figure at least 10 % from its limit."""
+    e, oracle, n_clouds = big
+    sides = {}
+    for n in cases.BIG_SIZES:
+        p = cases.prefix(e, n)
+        want = cases.call(oracle, p)
+        pooled = np.zeros(n, dtype=bool)
+        pooled[want["atom"]] = True
+        src = np.repeat(np.arange(n), np.diff(p["bonded_off"]))
+        n_pool, n_pairs = int(n_clouds[:n][pooled].sum()), int(np.count_nonzero(pooled[src] & pooled[p["bonded"]]))
+        points = switch_points(n, n_pool, n_pairs, len(np.unique(p["residue"][pooled])) + 1)
+        ratio = {k: v[0] / v[1] for k, v in points.items()}
+        print(n, "atoms:", n_pool, "pooled clouds,", n_pairs, "pairs:", {k: round(r, 3) for k, r in ratio.items()})
+        assert all(r <= 0.9 or r >= 1.1 for r in ratio.values()), (n, ratio)
+        sides[n] = "".join("a" if ratio[k] > 1 else "b" for k in ("T2", "T1", "T3"))
+    assert [sides[n] for n in cases.BIG_SIZES] == ["bbb", "abb", "aab", "aaa"]
+
+
+def test_big_entry_exercises_every_table(big):
+    e, oracle, n_clouds = big
+    want = cases.call(oracle, e)
+    states = np.bincount(want["owner_state"], minlength=3)
+    assert states[1] >= 1000 and states[2] >= 1000 and states[0] >= 10, states
+    assert len(want["res"]["n"]) >= 1000 and len(want["dom"]["n"]) >= 20
+    pooled = np.zeros(len(n_clouds), dtype=bool)
+    pooled[want["atom"]] = True
+    assert np.count_nonzero(n_clouds > 1) >= 500 and np.count_nonzero((n_clouds > 1) & ~pooled) >= 1 and np.count_nonzero((n_clouds > 1) & pooled) >= 100
+    assert np.count_nonzero(n_clouds == 0) >= 1
+    for tag in ("res", "dom"):          # the key that aligns device and oracle rows is unique, by far more than the tolerance of the densities
+        t = want[tag]
+        k = checker.row_order(t, tag)
+        same = (t["n"][k][1:] == t["n"][k][:-1]) & ((t["residue"][k][1:] == t["residue"][k][:-1]) | (tag == "dom"))
+        gap = np.abs(np.diff(t["total"][k]))[same] / np.abs(t["total"][k][1:][same])
+        assert same.sum() > 0 and gap.min() > 1e-6, (tag, gap.min())
