@@ -285,6 +285,45 @@ int pdbeda_peaklist_rows(pdbeda_peaklist *pl, int32_t *crs, float *height, doubl
  * the box that pass the cutoff), peaks, runs of the job beyond the first (1 = the typical-size arena overflowed), bytes of
  * device memory the job holds. */
 int pdbeda_peaklist_counters(pdbeda_peaklist *pl, int64_t *out);
+/* Peak basins (no reference counterpart): the significant voxels divided among the peaks of the list by steepest ascent, with
+ * per-basin sums and the highest pass to an adjacent basin.  pl: a list of pdbeda_map_peaks or either list of
+ * pdbeda_map_peaks_pm; its map, sign and float32 cutoff are the job's.  The MAP MUST STILL BE ALIVE AND UNCHANGED since the peak
+ * call (the list keeps a pointer to it, not a copy).  Rows come in the list's order.
+ * Domain: the significant voxels of the non-repeating box header.uniqueNcrs, D >= cutoff (D <= cutoff for a negative cutoff;
+ * inclusive, a NaN fails): exactly the candidates of the peak search.  Neighbours are the 26 neighbours inside the box; nothing wraps.
+ * The PARENT of a significant voxel v is the voxel, among v and its significant neighbours, that BEATS all the others in the
+ * sense of pdbeda_map_peaks (greater |D|; on equal |D| the one that comes first in c-major (c, r, s) order).  A voxel that is its
+ * own parent is a ROOT; the root of v is reached by following parents (the order is strict: the walk ends and is unique); the
+ * BASIN of peak i is every significant voxel whose root is peak i's voxel.  On a map without NaN the roots are the peaks.  A root
+ * that is not in the list can only sit beside a NaN voxel (which the peak rule lets nothing beat): its voxels are ORPHANS, enter
+ * no row, carry -1 in `basin` and are counted in `counters`.
+ * Per peak i:
+ *   n          voxels of the basin (>= 1: the peak itself);
+ *   sum        their density: each voxel rounded once to the map's fixed-point quantum (the quantum of the blob sums, as in
+ *              pdbeda_map_partition), folded as integers and converted once -- bit-identical from run to run, within quantum / 2
+ *              per voxel of the exact sum.  A non-finite voxel is counted in n and s1 and enters neither sum nor sw1;
+ *   s1[3]      exact integer sums of d = crs - crs(peak i);
+ *   sw1[3]     sum of w d with w = |density| rounded to the same quantum; the products are exact and folded as integers.  (The
+ *              sum of w is |sum|: all voxels of a basin have the cutoff's sign.)  A one-voxel basin has exact zeros in s1 and sw1;
+ *   saddle, neighbour   over all pairs (p in basin i; q significant, in another basin of the list, a 26-neighbour of p inside
+ *              the box) the PASS of a pair is whichever of D[p], D[q] has the smaller |D|; saddle is the pass with the greatest
+ *              |D| (a signed float32 map value) and neighbour the smallest list index among the basins of the q's of the pairs
+ *              that attain it.  Both are functions of the values alone.  Without such a pair -- exactly when the basin is its
+ *              whole blob -- neighbour = -1 and saddle = 0.  Pairs with orphan voxels do not count.
+ * basin: the box's voxels, [s][r][c] of the box, c fastest (uniqueNcrs[2] x uniqueNcrs[1] x uniqueNcrs[0]): the list index of the
+ * voxel's basin, or -1 for insignificant and orphan voxels.
+ * counters[4]: significant voxels, orphan voxels, pointer-doubling rounds run, bytes of device memory the job held.
+ * An empty list succeeds: rows are untouched and basin, if given, is all -1.  PDBEDA_ERR_ARGUMENT before any launch: a NULL or
+ * freed list.  PDBEDA_ERR_TIMEOUT on a context whose watchdog has expired.  The ascent is resolved by at most 31 doubling rounds
+ * (enough for any path in a box of fewer than 2^31 voxels), enqueued in small batches with one wait per batch.  The rows are kept
+ * with the list: a second call copies them without a launch (a call that asks for `basin` runs the job again: the volume is not
+ * kept).  The result for either list of a fused job equals the single call's to the bit.  Synchronous; any output pointer may be
+ * NULL; a failing call leaves the context usable. */
+int pdbeda_peaklist_basins(pdbeda_peaklist *pl,
+                           int64_t *n, double *sum, int64_t *s1 /* n_peaks x 3 */, double *sw1 /* n_peaks x 3 */,
+                           float *saddle, int32_t *neighbour,
+                           int32_t *basin   /* box voxels [us][ur][uc], c fastest; may be NULL */,
+                           int64_t counters[4]);
 /* Release a list (no reference counterpart; does not wait: the arena is recycled in stream order).  The handle is gone afterwards. */
 int pdbeda_peaklist_free(pdbeda_peaklist *pl);
 

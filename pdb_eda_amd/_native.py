@@ -115,6 +115,7 @@ _SIGS = {
     "pdbeda_peaklist_count": (_i64, [_p]),
     "pdbeda_peaklist_rows": (C.c_int, [_p, _p, _p, _p, _p, _p, _p]),
     "pdbeda_peaklist_counters": (C.c_int, [_p, _p]),
+    "pdbeda_peaklist_basins": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pdbeda_peaklist_free": (C.c_int, [_p]),
     "pdbeda_region_sums": (C.c_int, [_p, _p, _p, _i64, _p, _i64, C.c_float, _p, _p, _p, _p]),
     "pdbeda_radial_profiles": (C.c_int, [_p, _p, _i64, C.c_float, C.c_int32, C.c_float, _p, _p, _p, _p, _p]),
@@ -464,6 +465,24 @@ class PeakList(object):
         out = np.zeros(4, dtype=np.int64)
         self._ctx.check(self._ctx._lib.pdbeda_peaklist_counters(self._h, _ptr(out)), "pdbeda_peaklist_counters")
         return {"tested": int(out[0]), "peaks": int(out[1]), "reruns": int(out[2]), "arena_bytes": int(out[3])}
+
+    def basins(self, volume=False):
+        """pdbeda_peaklist_basins: per peak, in list order, ``n`` (int64), ``sum``, ``s1`` (n x 3 int64), ``sw1`` (n x 3), ``saddle`` (float32),
+        ``neighbour`` (int32); ``counters`` {"significant", "orphans", "rounds", "arena_bytes"}; with ``volume`` also ``basin``, the int32
+        volume over the box's voxels ([s][r][c] of the box, c fastest)."""
+        n = len(self)
+        out = {"n": np.zeros(n, np.int64), "sum": np.zeros(n, np.float64), "s1": np.zeros((n, 3), np.int64), "sw1": np.zeros((n, 3), np.float64),
+               "saddle": np.zeros(n, np.float32), "neighbour": np.zeros(n, np.int32)}
+        vol = None
+        if volume:
+            vol = np.zeros(self._keep[0].unique_shape, np.int32)
+        ctr = np.zeros(4, np.int64)
+        self._ctx.check(self._ctx._lib.pdbeda_peaklist_basins(self._h, *([_ptr(out[k]) for k in ("n", "sum", "s1", "sw1", "saddle", "neighbour")] + [_ptr(vol), _ptr(ctr)])),
+                        "pdbeda_peaklist_basins")
+        out["counters"] = {"significant": int(ctr[0]), "orphans": int(ctr[1]), "rounds": int(ctr[2]), "arena_bytes": int(ctr[3])}
+        if volume:
+            out["basin"] = vol
+        return out
 
     def free(self):
         if self._h is not None and self._ctx._h:

@@ -455,21 +455,22 @@ class DensityMatrix(object):
         as ``createFullBlobList``.  blobList: ``createFullBlobList(cutoff)`` of this map -- every peak then knows its blob."""
         if np.float32(cutoff) == 0:
             return None
-        return DevicePeaks(self._map.peaks(cutoff, self._deviceListOf(blobList)), self)
+        return DevicePeaks(self._map.peaks(cutoff, self._deviceListOf(blobList)), self, cutoff, blobList)
 
     def findPeakLists(self, cutoff, blobLists=None):
         """Fused (positive, negative) peak lists at +-|cutoff| from ONE pass over the grid; blobLists: the pair
         ``createFullBlobLists(cutoff)`` returned, or None."""
         green, red = blobLists if blobLists is not None else (None, None)
         pos, neg = self._map.peaks_pm(abs(cutoff), -abs(cutoff), self._deviceListOf(green), self._deviceListOf(red))
-        return DevicePeaks(pos, self), DevicePeaks(neg, self)
+        return DevicePeaks(pos, self, abs(cutoff), green), DevicePeaks(neg, self, -abs(cutoff), red)
 
 
 class DensityPeak(object):
     """One local extremum of a map: ``crs`` (raw voxel), ``height`` (the voxel's value), ``xyz`` / ``refinedHeight`` (vertex of
     one parabola per axis), ``blobIndex`` (in the blob list the search was given, else -1), ``onBorder`` (a voxel on the edge of
-    the stored box: the extremum may be the edge's)."""
-    __slots__ = ("crs", "height", "xyz", "refinedHeight", "blobIndex", "onBorder", "densityMatrix")
+    the stored box: the extremum may be the edge's).  A peak of a device list also has the ``BASIN_COLUMNS`` of its basin as read-only
+    attributes, made for the whole list on first use (``basinFinish``)."""
+    __slots__ = ("crs", "height", "xyz", "refinedHeight", "blobIndex", "onBorder", "densityMatrix", "_peaks", "_index")
 
     def __init__(self, crs, height, xyz, refinedHeight, blobIndex, onBorder, densityMatrix=None):
         self.crs, self.height, self.xyz, self.refinedHeight = crs, height, xyz, refinedHeight
@@ -478,14 +479,23 @@ class DensityPeak(object):
     def __repr__(self):
         return "DensityPeak(crs=%r, height=%r)" % (self.crs, self.height)
 
+    def _basinValue(self, name):
+        peaks = getattr(self, "_peaks", None)
+        if peaks is None:
+            raise AttributeError("%s is known only for a peak that comes from a device list (findPeaks, findPeakLists)" % name)
+        value = peaks.basinColumns()[name][self._index]
+        return value.tolist() if isinstance(value, np.ndarray) else value.item()
+
 
 class DevicePeaks(collections.abc.Sequence):
     """What ``findPeaks`` returns: a read-only sequence of ``DensityPeak`` in list order, lazy like ``DeviceBlobs`` -- the
     columns come from the device on first use, the objects are made when somebody reads one."""
 
-    def __init__(self, pl, densityMatrix):
+    def __init__(self, pl, densityMatrix, cutoff=None, blobList=None):
         self._pl, self.densityMatrix = pl, densityMatrix
+        self.cutoff, self.blobList = cutoff, blobList      # the float32 of ``cutoff`` is the job's; blobList: what the search was given, or None
         self._items = None
+        self._basins = None
 
     def __len__(self):
         return len(self._pl)
@@ -499,12 +509,27 @@ class DevicePeaks(collections.abc.Sequence):
     def counters(self):
         return self._pl.counters()
 
+    def basinColumns(self):
+        """``basinFinish`` of the list's basins (``pdbeda_peaklist_basins``): one row per peak, plus ``counters``.  Made on first use."""
+        if self._basins is None:
+            raw = self._pl.basins()
+            cutoff = float(np.float32(self.cutoff)) if self.cutoff is not None else 0.0
+            self._basins = basinFinish(self.densityMatrix.header, self.columns(), raw, cutoff)
+            self._basins["counters"] = raw["counters"]
+        return self._basins
+
+    def basinVolume(self):
+        """int32 [s][r][c] over the non-repeating box: the list index of every significant voxel's basin, -1 elsewhere (and for orphans)."""
+        return self._pl.basins(volume=True)["basin"]
+
     def _all(self):
         if self._items is None:
             st = self.columns()
             self._items = [DensityPeak(*row, densityMatrix=self.densityMatrix)
                            for row in zip(st["crs"].tolist(), st["height"].tolist(), st["xyz"].tolist(), st["refinedHeight"].tolist(),
                                           st["blobIndex"].tolist(), st["onBorder"].tolist())]
+            for index, peak in enumerate(self._items):
+                peak._peaks, peak._index = self, index
         return self._items
 
     def __getitem__(self, i):
@@ -515,6 +540,75 @@ class DevicePeaks(collections.abc.Sequence):
 
     def __repr__(self):
         return "DevicePeaks(%d peaks)" % len(self)
+
+
+BASIN_COLUMNS = ("numVoxels", "totalDensity", "volume", "coordCenter", "centroid", "saddle", "prominence", "neighbour")
+
+
+def basinFinish(header, peakColumns, raw, cutoff):
+    """The basin columns of a peak list from the integer / fixed-point sums of ``pdbeda_peaklist_basins`` (``PeakList.basins()``) and the
+    peaks' own columns -- a few vectorised fp64 operations per row, no voxel is touched.  A dict of arrays, one row per peak:
+
+    ``numVoxels``, ``totalDensity``, ``volume`` (unitVolume x voxels), ``coordCenter`` (xyz of peak crs + s1 / n), ``centroid`` (xyz of
+    peak crs + sw1 / |sum|: the density-weighted centre, sum rho xyz / sum rho, because ``crs2xyz`` is affine; the peak's own position
+    where |sum| is 0), ``saddle`` (the highest pass to an adjacent basin, a map value; ``cutoff`` for a basin that is its whole blob),
+    ``prominence`` (|height| - |saddle| in fp64 from the float32 values) and ``neighbour`` (the basin beyond the pass, -1 without one)."""
+    n = np.asarray(raw["n"], dtype=np.int64)
+    count = len(n)
+    crs = np.asarray(peakColumns["crs"], dtype=np.float64).reshape(count, 3)
+    total = np.asarray(raw["sum"], dtype=np.float64)
+    s1 = np.asarray(raw["s1"], dtype=np.float64).reshape(count, 3)
+    sw1 = np.asarray(raw["sw1"], dtype=np.float64).reshape(count, 3)
+    weight = np.abs(total)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(weight[:, None] > 0, sw1 / weight[:, None], 0.0)
+    neighbour = np.asarray(raw["neighbour"], dtype=np.int32)
+    saddle = np.where(neighbour < 0, np.float32(cutoff), np.asarray(raw["saddle"], dtype=np.float32)).astype(np.float32)
+    height = np.asarray(peakColumns["height"], dtype=np.float32)
+    xyz = lambda at: header.crs2xyz_array(at).reshape(count, 3) if count else np.zeros((0, 3))
+    return {"numVoxels": n, "totalDensity": total, "volume": header.unitVolume * n, "coordCenter": xyz(crs + s1 / np.maximum(n, 1)[:, None]),
+            "centroid": xyz(crs + mean), "saddle": saddle, "prominence": np.abs(height.astype(np.float64)) - np.abs(saddle.astype(np.float64)),
+            "neighbour": neighbour}
+
+
+def groupBasins(columns, minProminence):
+    """Shoulders joined to the peaks they lean on, in ONE pass -- not a persistence hierarchy: every peak with ``prominence <
+    minProminence`` and a neighbour is joined to that neighbour (union-find over the edges i -> neighbour[i]); a group's representative
+    is its smallest list index, i.e. its highest peak.  A low peak without a neighbour stays alone.  columns: ``basinFinish``'s.
+    Returns ``{"representative" (per peak), "groups" (the representatives, ascending), "numVoxels", "totalDensity", "volume",
+    "coordCenter", "centroid"}`` with one row per group for the last five: the sums of the members, the centres re-based from the
+    members' absolute sums (n x coordCenter, |sum| x centroid)."""
+    n = np.asarray(columns["numVoxels"], dtype=np.int64)
+    count = len(n)
+    neighbour, prominence = np.asarray(columns["neighbour"], dtype=np.int64), np.asarray(columns["prominence"], dtype=np.float64)
+    parent = list(range(count))
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    for i in np.nonzero((prominence < minProminence) & (neighbour >= 0))[0].tolist():
+        a, b = find(i), find(int(neighbour[i]))
+        if a != b:
+            parent[max(a, b)] = min(a, b)          # (the smaller index stays the root: the representative is the group's minimum)
+    representative = np.array([find(i) for i in range(count)], dtype=np.int64)
+    groups, slot = np.unique(representative, return_inverse=True)
+    total = np.asarray(columns["totalDensity"], dtype=np.float64)
+    weight = np.abs(total)
+
+    def fold(values):
+        out = np.zeros((len(groups),) + np.shape(values)[1:], dtype=np.float64)
+        np.add.at(out, slot, values)
+        return out
+
+    group_n, group_weight = fold(n.astype(np.float64)), fold(weight)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        center = fold(np.asarray(columns["coordCenter"], dtype=np.float64) * n[:, None]) / group_n[:, None]
+        centroid = np.where(group_weight[:, None] > 0, fold(np.asarray(columns["centroid"], dtype=np.float64) * weight[:, None]) / group_weight[:, None], center)
+    return {"representative": representative, "groups": groups, "numVoxels": group_n.astype(np.int64), "totalDensity": fold(total),
+            "volume": fold(np.asarray(columns["volume"], dtype=np.float64)), "coordCenter": center, "centroid": centroid}
 
 
 SHAPE_COLUMNS = ("boxLo", "boxHi", "boxExtent", "onBorder", "extremeCrs", "extremeXyz", "extremeDensity", "weightedCentroid", "secondMomentCrs",
@@ -867,4 +961,12 @@ def _shapeAttribute(name):
 
 for _name in SHAPE_COLUMNS:
     setattr(DensityBlob, _name, _shapeAttribute(_name))
+
+
+def _basinAttribute(name):
+    return property(lambda self: self._basinValue(name), doc="``%s`` of ``basinFinish`` for this peak (read-only; made on first use for the whole list)." % name)
+
+
+for _name in BASIN_COLUMNS:
+    setattr(DensityPeak, _name, _basinAttribute(_name))
 del _name

@@ -33,6 +33,7 @@
 #include "pdbeda_partition.h"
 #include "pdbeda_blobshape.h"
 #include "pdbeda_blobnear.h"
+#include "pdbeda_basins.h"
 
 using namespace pdbeda;
 
@@ -2046,6 +2047,16 @@ struct PeakJob {
     bool resolved = false;
     int64_t n[2] = {0, 0}, tested[2] = {0, 0};
     std::vector<uint32_t> order[2];                   // list position -> arena slot
+    std::vector<uint32_t> pos[2];                     // list position -> c-major position of the peak's voxel (the low word of its key)
+    // pdbeda_peaklist_basins: the rows of each list, made by the first call and kept until the job goes
+    struct BasinRows {
+        bool done = false;
+        std::vector<int64_t> n, s1;
+        std::vector<double> sum, sw1;
+        std::vector<float> saddle;
+        std::vector<int32_t> neighbour;
+        int64_t counters[4] = {0, 0, 0, 0};
+    } basins[2];
 };
 struct pdbeda_peaklist {
     PeakJob *job = nullptr;
@@ -2230,7 +2241,8 @@ static int peaks_resolve(PeakJob *pj) {
         for (size_t i = 0; i < kv.size(); ++i) kv[i] = {keys[p][i], (uint32_t)i};
         std::sort(kv.begin(), kv.end());                                              // (keys are unique: one order)
         ord.resize(kv.size());
-        for (size_t i = 0; i < kv.size(); ++i) ord[i] = kv[i].second;
+        pj->pos[p].resize(kv.size());
+        for (size_t i = 0; i < kv.size(); ++i) { ord[i] = kv[i].second; pj->pos[p][i] = (uint32_t)(kv[i].first & 0xffffffffull); }
     }
     if (ctx->profiling) ctx->prof_host.push_back({"host_peak_sort", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sort_t0).count()});
     pj->resolved = true;
@@ -2289,6 +2301,166 @@ extern "C" int pdbeda_peaklist_counters(pdbeda_peaklist *pl, int64_t *out) {
     out[1] = pl->job->n[pl->plane];
     out[2] = pl->job->reruns;
     out[3] = (int64_t)pl->job->bytes;
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Peak basins (pdbeda_basins.h; no reference counterpart; the contract: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// The launch graph of a call that computes: (a map with NaN / infinite voxels only: k_partition_range and a wait for the quantum;) one fill
+// of the accumulators and flags, the peaks' box positions up, k_basin_parent, then batches of BN_BATCH k_basin_jump rounds with ONE wait per
+// batch for the batch's changed-flags (a bounded loop: BN_MAX_ROUNDS rounds at the most, then an error; a round behind one that changed
+// nothing reads that round's flag and returns), k_basin_mark, k_basin_resolve,
+// k_basin_sums, k_basin_decode when the volume is asked for, and one wait for the accumulators (and the volume).  The integers become the
+// rows on the host.  The scratch arena goes back to the pool in stream order whatever happens.
+static int basins_compute(pdbeda_peaklist *pl, int32_t *basin_host) {
+    PeakJob *pj = pl->job;
+    pdbeda_ctx *ctx = pj->ctx;
+    pdbeda_map *m = pj->map;
+    const int p = pl->plane;
+    const PeakJobArgs &pa = pj->args;
+    const PeakPlane &pp = pa.plane[p];
+    const int uc = pa.uc, ur = pa.ur, us = pa.us;
+    const int64_t nbox = (int64_t)uc * ur * us;      // (< 2^31: peaks_impl)
+    const size_t np = (size_t)pj->n[p];
+    PeakJob::BasinRows &br = pj->basins[p];
+    if (np == 0) {      // no peak: every significant voxel (there are some only beside NaNs) is an orphan
+        if (basin_host) std::fill(basin_host, basin_host + nbox, (int32_t)-1);
+        br.counters[0] = br.counters[1] = pj->tested[p];
+        br.counters[2] = br.counters[3] = 0;
+        br.done = true;
+        return PDBEDA_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (m->fix_mul == 0.0 && !m->fix_refused) {      // (a wait when the map's range is not known yet: before anything is staged)
+        const int rc = map_fix_mul(m);
+        if (rc && !m->fix_refused) return rc;
+    }
+    // the peaks' voxels in list order, as box positions
+    std::vector<int32_t> peak_box(np);
+    for (size_t i = 0; i < np; ++i) {
+        const uint32_t pos = pj->pos[p][i];
+        const int64_t s = pos % (uint32_t)us, cr = pos / (uint32_t)us, r = cr % ur, c = cr / ur;
+        peak_box[i] = (int32_t)((s * ur + r) * uc + c);
+    }
+    BasinArgs a;
+    memset(&a, 0, sizeof a);
+    int32_t *d_peak_box = nullptr;
+    uint32_t *d_flags = nullptr;
+    unsigned long long *d_range = nullptr;
+    size_t bytes = 0;
+    Arena arena;
+    const int rc_arena = arena_carve(ctx, "peak basins", &arena, [&](Carver &cv) {
+        cv.take(a.up, (size_t)nbox);
+        cv.take(d_peak_box, np);
+        cv.take(a.acc, BN_ACC * np);      // (the accumulators and everything behind them: ONE fill clears all)
+        cv.take(a.orphans, 1);
+        cv.take(d_flags, 32);
+        cv.take(d_range, 1);
+        bytes = cv.off;
+    });
+    if (rc_arena) return rc_arena;
+    std::vector<unsigned long long> acc(BN_ACC * np);
+    unsigned long long orphans = 0;
+    int rounds = 0;
+    double fix_mul = m->fix_mul;
+    auto run = [&]() -> int {
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, hipMemsetAsync(a.acc, 0, (size_t)((char *)(d_range + 1) - (char *)a.acc), st));
+        if (m->fix_refused) {      // NaN / infinite voxels: they enter no sum, and the quantum comes from the finite voxels of the box (as the partition's)
+            unsigned long long bits = 0;
+            { PROF(ctx, "k_partition_range"); hipLaunchKernelGGL(k_partition_range, dim3(grid_for(nbox, 256, 4096)), dim3(256), 0, st, m->dens, pa.nc, pa.nr, uc, ur, us, d_range); }
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, d2h(ctx, &bits, d_range, 8));
+            HIP_TRY(ctx, ctx_sync(ctx));
+            double top;
+            memcpy(&top, &bits, 8);
+            int S = 40, e = 0;
+            if (top > 0.0) { (void)frexp(top * (double)std::max<int64_t>(nbox, 1ll << 22), &e); S = 61 - e; }      // (|sum| <= voxels x max |rho| < 2^61)
+            fix_mul = ldexp(1.0, std::max(-900, std::min(S, 900)));
+        }
+        HIP_TRY(ctx, h2d_one(ctx, d_peak_box, peak_box.data(), 4 * np));
+        a.dens = m->dens;
+        a.uc = uc; a.ur = ur; a.us = us; a.nc = pa.nc; a.nr = pa.nr;
+        a.cut = pp.cut; a.sign = pp.sign;
+        a.peak_box = d_peak_box; a.n_peaks = (int64_t)np;
+        a.fix_mul = fix_mul;
+        const dim3 tiles((unsigned)((uc + PK_C - 1) / PK_C), (unsigned)((ur + PK_R - 1) / PK_R), (unsigned)((us + PK_S - 1) / PK_S));
+        const dim3 flat(grid_for(nbox, 256, 2048));      // (grid-stride loops: eight workgroups per CU, and a jump round that returns at once costs a small launch)
+        { PROF(ctx, "k_basin_parent"); hipLaunchKernelGGL(k_basin_parent, tiles, dim3(PK_THREADS), 0, st, a); }
+        HIP_TRY(ctx, hipGetLastError());
+        for (;;) {
+            if (rounds >= BN_MAX_ROUNDS) return fail(ctx, PDBEDA_ERR_STATE, "peak basins: the ascent did not settle in %d doubling rounds", BN_MAX_ROUNDS);
+            const int batch = std::min(BN_BATCH, BN_MAX_ROUNDS - rounds);
+            uint32_t changed[BN_BATCH];
+            for (int k = 0; k < batch; ++k) {      // (a round behind one that changed nothing returns at once: the rest of a batch costs its launches)
+                PROF(ctx, "k_basin_jump");
+                hipLaunchKernelGGL(k_basin_jump, flat, dim3(256), 0, st, a.up, nbox, rounds + k > 0 ? d_flags + rounds + k - 1 : (const uint32_t *)nullptr, d_flags + rounds + k);
+            }
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, d2h(ctx, changed, d_flags + rounds, 4 * (size_t)batch));
+            HIP_TRY(ctx, ctx_sync(ctx));
+            int settled = -1;
+            for (int k = 0; k < batch && settled < 0; ++k)
+                if (changed[k] == 0u) settled = k;
+            rounds += settled < 0 ? batch : settled + 1;      // (rounds that ran: up to and with the first that changed nothing)
+            if (settled >= 0) break;
+        }
+        { PROF(ctx, "k_basin_mark"); hipLaunchKernelGGL(k_basin_mark, dim3(grid_for((int64_t)np, 256, 1024)), dim3(256), 0, st, a.up, d_peak_box, (int64_t)np); }
+        { PROF(ctx, "k_basin_resolve"); hipLaunchKernelGGL(k_basin_resolve, flat, dim3(256), 0, st, a.up, nbox, a.orphans); }
+        { PROF(ctx, "k_basin_sums"); hipLaunchKernelGGL(k_basin_sums, tiles, dim3(PK_THREADS), 0, st, a); }
+        if (basin_host) { PROF(ctx, "k_basin_decode"); hipLaunchKernelGGL(k_basin_decode, flat, dim3(256), 0, st, a.up, nbox); }
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, d2h(ctx, acc.data(), a.acc, 8 * BN_ACC * np));
+        HIP_TRY(ctx, d2h(ctx, &orphans, a.orphans, 8));
+        if (basin_host) HIP_TRY(ctx, d2h(ctx, basin_host, a.up, 4 * (size_t)nbox));
+        HIP_TRY(ctx, ctx_sync(ctx));
+        return PDBEDA_OK;
+    };
+    const int rc = run();
+    arena_put(ctx, arena);      // (stream order: whatever is still queued on a failed call runs before the arena's next user)
+    if (rc) return rc;
+    const double fix_inv = 1.0 / fix_mul;      // (a power of two: the products below are exact)
+    br.n.resize(np); br.sum.resize(np); br.s1.resize(3 * np); br.sw1.resize(3 * np); br.saddle.resize(np); br.neighbour.resize(np);
+    for (size_t i = 0; i < np; ++i) {
+        br.n[i] = (int64_t)acc[i];
+        br.sum[i] = (double)((long long)acc[np + i] * pp.sign) * fix_inv;
+        for (int k = 0; k < 3; ++k) {
+            br.s1[3 * i + k] = (int64_t)acc[(2 + k) * np + i];
+            const __int128 v = (__int128)(long long)acc[(6 + 2 * k) * np + i] * ((__int128)1 << 32) + (__int128)(long long)acc[(5 + 2 * k) * np + i];
+            br.sw1[3 * i + k] = (double)v * fix_inv;
+        }
+        const unsigned long long key = acc[11 * np + i];
+        uint32_t bits = (uint32_t)(key >> 32);
+        if (key != 0ull && pp.sign < 0) bits |= 0x80000000u;
+        memcpy(&br.saddle[i], &bits, 4);
+        br.neighbour[i] = key != 0ull ? (int32_t)(~(uint32_t)(key & 0xffffffffull)) : -1;
+    }
+    br.counters[0] = pj->tested[p];
+    br.counters[1] = (int64_t)orphans;
+    br.counters[2] = rounds;
+    br.counters[3] = (int64_t)bytes;
+    br.done = true;
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_peaklist_basins(pdbeda_peaklist *pl, int64_t *n, double *sum, int64_t *s1, double *sw1, float *saddle, int32_t *neighbour,
+                                      int32_t *basin, int64_t counters[4]) {
+    if (!pl || pl->freed) return PDBEDA_ERR_ARGUMENT;
+    PeakJob *pj = pl->job;
+    if (pj->ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    if (int rc = peaks_resolve(pj)) return rc;
+    PeakJob::BasinRows &br = pj->basins[pl->plane];
+    if (!br.done || basin)      // (the volume is not kept: a call that asks for it runs the job, and gets the same rows)
+        if (int rc = basins_compute(pl, basin)) return rc;
+    const size_t np = br.n.size();
+    if (n && np) memcpy(n, br.n.data(), 8 * np);
+    if (sum && np) memcpy(sum, br.sum.data(), 8 * np);
+    if (s1 && np) memcpy(s1, br.s1.data(), 24 * np);
+    if (sw1 && np) memcpy(sw1, br.sw1.data(), 24 * np);
+    if (saddle && np) memcpy(saddle, br.saddle.data(), 4 * np);
+    if (neighbour && np) memcpy(neighbour, br.neighbour.data(), 4 * np);
+    if (counters) memcpy(counters, br.counters, sizeof br.counters);
     return PDBEDA_OK;
 }
 

@@ -386,6 +386,8 @@ class DensityAnalysis(object):
                             'atom_name', 'atom_symmetry', 'atom_xyz', 'centroid_xyz']
     peakStatisticsHeader = ['distance_to_atom', 'sign', 'height_in_sigma', 'height_in_electrons_per_A3', 'blob_index', 'on_border', 'chain', 'residue_number',
                             'residue_name', 'atom_name', 'symmetry', 'atom_xyz', 'peak_xyz']
+    basinStatisticsHeader = peakStatisticsHeader + ['num_voxels', 'volume', 'electrons', 'fraction_of_blob', 'saddle_in_sigma', 'prominence_in_sigma', 'neighbour_peak',
+                                                    'centroid_xyz']
     blobShapeHeader = ['blob_index', 'num_voxels', 'volume', 'sign', 'electrons_of_discrepancy', 'extreme_in_sigma', 'extreme_in_electrons_per_A3', 'extreme_xyz',
                        'principal_length_1', 'principal_length_2', 'principal_length_3', 'anisotropy', 'box_extent', 'on_border', 'distance_to_atom', 'chain',
                        'residue_number', 'residue_name', 'atom_name', 'atom_symmetry', 'atom_xyz']
@@ -911,6 +913,32 @@ class DensityAnalysis(object):
         return self._rows(list(dist), sign, height / std, height / ratio, blob, border,
                           (chain, rows), (number, rows), (resname, rows), (cols.name if isinstance(cols.name, (list, tuple)) else list(cols.name), rows),
                           symmetry, coords, peak_xyz)
+
+    # ---- basin statistics (no reference counterpart): the peak table, with what belongs to each peak ----
+    def calculateAtomSpecificBasinStatistics(self, peakList):
+        """One row per peak of a device list (``basinStatisticsHeader``): the peak table's columns, then the peak's basin -- voxels, volume,
+        electrons (|sum / densityElectronRatio|), its share of the blob's density (None when the search was given no blob list), the pass to
+        the adjacent basin and the prominence in units of the map's standard deviation, the peak beyond the pass (-1: the basin is its
+        whole blob) and the density-weighted centre."""
+        shared = self.calculateAtomSpecificPeakStatistics(peakList)          # (raises the blob table's RuntimeError without a ratio)
+        if not shared:
+            return []
+        if not isinstance(peakList, ccp4.DevicePeaks):
+            raise ValueError("basin statistics need the peak list findPeaks / findPeakLists returned")
+        ratio, std = self.densityElectronRatio, peakList.densityMatrix.stdDensity
+        basins, listed = peakList.basinColumns(), peakList.columns()
+        total = np.asarray(basins["totalDensity"], dtype=np.float64)
+        fraction = [None] * len(total)
+        if peakList.blobList is not None:
+            blobTotal = np.asarray(peakList.blobList.columns()["totalDensity"], dtype=np.float64)
+            blob = np.asarray(listed["blobIndex"], dtype=np.int64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                share = np.abs(total) / np.abs(blobTotal[np.maximum(blob, 0)])
+            fraction = [float(v) if b >= 0 else None for v, b in zip(share.tolist(), blob.tolist())]
+        extra = zip(basins["numVoxels"].tolist(), basins["volume"].tolist(), np.abs(total / ratio).tolist(), fraction,
+                    (basins["saddle"].astype(np.float64) / std).tolist(), (basins["prominence"] / std).tolist(), basins["neighbour"].tolist(),
+                    basins["centroid"].tolist())
+        return [list(row) + list(more) for row, more in zip(shared, extra)]
 
     # ---- blob shape statistics (no reference counterpart; built like the two tables above) ------
     def calculateBlobShapeStatistics(self, blobList):

@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin")
 
 
 def numpyConverter(obj):
@@ -51,9 +51,8 @@ def _blobTable(analyzer, o):
     return _plainColumns(table, listColumns=(9,), floatColumns=(10, 11))
 
 
-def _peakTable(analyzer, o):
-    """peak sub-mode (no reference counterpart): the local extrema of the green and / or red Fo-Fc map, else of the blue 2Fo-Fc
-    map, each with its blob of the blob sub-mode's list at the same cutoff and its nearest symmetry atom."""
+def _peakLists(analyzer, o):
+    """The peak lists of the peak and basin sub-modes: green and / or red Fo-Fc, else blue 2Fo-Fc, with the blob lists at the same cutoff."""
     diffObj, densObj, numSD = analyzer.diffDensityObj, analyzer.densityObj, o["numSD"]
     if o["green"] and o["red"]:          # one fused pass over the Fo-Fc grid gives both lists
         cut = diffObj.meanDensity + numSD * diffObj.stdDensity
@@ -64,8 +63,21 @@ def _peakTable(analyzer, o):
     else:
         cut = densObj.meanDensity + numSD * densObj.stdDensity
         lists = [densObj.findPeaks(cut, densObj.createFullBlobList(cut))]
-    table = [row for peaks in lists for row in analyzer.calculateAtomSpecificPeakStatistics(peaks)]
+    return lists
+
+
+def _peakTable(analyzer, o):
+    """peak sub-mode (no reference counterpart): the local extrema of the green and / or red Fo-Fc map, else of the blue 2Fo-Fc
+    map, each with its blob of the blob sub-mode's list at the same cutoff and its nearest symmetry atom."""
+    table = [row for peaks in _peakLists(analyzer, o) for row in analyzer.calculateAtomSpecificPeakStatistics(peaks)]
     return _plainColumns(table, listColumns=(10,), floatColumns=(11, 12))
+
+
+def _basinTable(analyzer, o):
+    """basin sub-mode (no reference counterpart): the peak sub-mode's rows, each with the voxels, electrons and share of its blob that belong to
+    the peak, the pass to the adjacent peak and the prominence."""
+    table = [row for peaks in _peakLists(analyzer, o) for row in analyzer.calculateAtomSpecificBasinStatistics(peaks)]
+    return _plainColumns(table, listColumns=(10,), floatColumns=(11, 12, 20))
 
 
 def _shapeTable(analyzer, o):
@@ -144,6 +156,7 @@ TABLES = {
                                       lambda an, o: _plainColumns(an.calculateSymmetryAtomRegionDiscrepancies(o["radius"], o["numSD"], o["type"]), **_SYM)),
     ("blob", None): (lambda an: _DA.blobStatisticsHeader, _blobTable),
     ("peak", None): (lambda an: _DA.peakStatisticsHeader, _peakTable),
+    ("basin", None): (lambda an: _DA.basinStatisticsHeader, _basinTable),
     ("shape", None): (lambda an: _DA.blobShapeHeader, _shapeTable),
     ("dipole", None): (lambda an: _DA.blobDipoleHeader, _dipoleTable),
     # (no reference counterpart; the shell columns are lists, carried as the peak table's list columns are)
@@ -163,15 +176,15 @@ def rows(analyzer, mode, level="atom", radius=None, numSD=None, type="", atomMas
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole;  level: atom | residue | domain | symmetry-atom
-    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak, shape and dipole) | atom-type (profile) | summary | blob
-    (partition);  green / red: blob / peak / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin;  level: atom | residue | domain | symmetry-atom
+    (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak, basin, shape and dipole) | atom-type (profile) | summary | blob
+    (partition);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
     (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
     maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default);  dipole: always the fused green
     and red lists (numSD default 3.0), ``radius`` is the largest gap between the two blobs when given (else 2.5 A);  radius default 3.5 elsewhere."""
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % (MODES,))
-    key = (mode, None if mode in ("blob", "peak", "shape", "dipole") else level)
+    key = (mode, None if mode in ("blob", "peak", "shape", "dipole", "basin") else level)
     if key not in TABLES:
         raise ValueError("%s mode has the levels %s" % (mode, ", ".join(lv for md, lv in TABLES if md == mode and lv)))
     options = {"radius": float(radius if radius is not None else 3.5), "radiusGiven": radius is not None,
