@@ -121,13 +121,18 @@ int pdbeda_map_upload_file_stats(pdbeda_ctx *ctx, const char *path, int64_t offs
                                  double *mean, double *std);
 int pdbeda_map_free(pdbeda_map *map);
 /* A new map on the geometry of `a` with density  float32( double(a) + alpha * double(b) )  per voxel -- the Fc map of
- * DensityAnalysis.fc is (2Fo-Fc) - 2 (Fo-Fc), densityAnalysis.py:426-435 (alpha = -2).  Same grid shape required. */
+ * DensityAnalysis.fc is (2Fo-Fc) - 2 (Fo-Fc), densityAnalysis.py:426-435 (alpha = -2).  Same grid shape required.
+ * The product and the sum are two fp64 roundings (no fused multiply-add) and the result is rounded to nearest float32 once:
+ * numpy's bits, float32 subnormals in and out included, and a sum beyond the float32 range becomes an infinity. */
 int pdbeda_map_combine(pdbeda_map *a, pdbeda_map *b, double alpha, pdbeda_map **out);
 /* One digit of a radix select over the voxels of the unique box with |a| < cut_a and |a + alpha b| < cut_b (b may be NULL:
  * then only the first test applies and which must be 0): the 65536-bin histogram of bits [shift, shift+16) of the key of the
  * voxels whose key agrees with `prefix` on `prefix_mask`.  key = bits of float |a| (which = 0, 32 bits) or of double
  * |a + alpha b| (which = 1, 64 bits) -- both orders are the numeric orders.  Host code walks the digits to an exact order
- * statistic: DensityAnalysis.medianAbsFoFc (densityAnalysis.py:783-801) without moving the maps.  hist: 65536 uint32. */
+ * statistic: DensityAnalysis.medianAbsFoFc (densityAnalysis.py:783-801) without moving the maps.  hist: 65536 uint32.
+ * Both tests are strict `<` on fp64 magnitudes: a voxel exactly on a cut is excluded, and so is one whose a or a + alpha b is a
+ * NaN or an infinity (cut_a = cut_b = inf keeps every voxel whose two magnitudes are finite).  +0 and -0 have one key (0);
+ * subnormal values are kept as they are, with keys of their own.  shift: 0 to 48. */
 int pdbeda_abs_select_hist(pdbeda_map *a, pdbeda_map *b, double alpha, double cut_a, double cut_b, int which, int shift,
                            unsigned long long prefix, unsigned long long prefix_mask, uint32_t *hist);
 /* Copy the float32 grid [ns][nr][nc] back to the host (inspection; DensityMatrix.density of a derived map). */
@@ -138,7 +143,9 @@ int pdbeda_map_download(pdbeda_map *map, float *density_out);
  * voxels in fp64 (ccp4.py:343-363). */
 int pdbeda_map_stats(pdbeda_map *map, double *mean, double *std);
 /* utils.sumOfAbs via getTotalAbsDensity: sum |v| for |v| > cutoff, strict (cutils.pyx:28-39,
- * ccp4.py:365-376). */
+ * ccp4.py:365-376).  The cutoff is a float32: a caller that holds a double rounds it to nearest first, and
+ * the comparison is then made on the exact values.  A NaN voxel is greater than nothing and is skipped; an infinite one makes
+ * the sum infinite.  Summed in fp64 in a fixed order: the same map and cutoff give the same bits in every run. */
 int pdbeda_sum_of_abs(pdbeda_map *map, float cutoff, double *out);
 
 /* ---- point / geometry helpers (batched) ------------------------------------------- */

@@ -496,6 +496,23 @@ class PeakList(object):
             pass
 
 
+def radix_select(digit, bits, ranks):
+    """The host side of the radix select of ``DeviceMap.abs_order_statistics``: the ``bits``-bit keys (Python ints) at the 0-based
+    ``ranks`` of the ascending order, found 16 bits a pass from the most significant digit down.  ``digit(shift, prefix, mask)`` returns
+    the 65536-bin histogram (int64) of bits [shift, shift + 16) of the keys that agree with ``prefix`` on ``mask``."""
+    out = []
+    for rank in ranks:
+        prefix, mask, remaining = 0, 0, int(rank)
+        for shift in range(bits - 16, -1, -16):
+            cs = np.cumsum(digit(shift, prefix, mask))
+            d = int(np.searchsorted(cs, remaining, side="right"))
+            remaining -= int(cs[d - 1]) if d else 0
+            prefix |= d << shift
+            mask |= 0xffff << shift
+        out.append(prefix)
+    return out
+
+
 class DeviceMap(object):
     """A density grid resident in HBM + its unit-cell basis."""
 
@@ -568,17 +585,8 @@ class DeviceMap(object):
         bits = 64 if which else 32
         if ranks is None:
             return int(digit(bits - 16, 0, 0).sum())
-        out = []
-        for rank in ranks:
-            prefix, mask, remaining = 0, 0, int(rank)
-            for shift in range(bits - 16, -1, -16):
-                cs = np.cumsum(digit(shift, prefix, mask))
-                d = int(np.searchsorted(cs, remaining, side="right"))
-                remaining -= int(cs[d - 1]) if d else 0
-                prefix |= d << shift
-                mask |= 0xffff << shift
-            out.append(np.array([prefix], dtype=np.uint64).view(np.float64)[0] if which else float(np.array([prefix], dtype=np.uint32).view(np.float32)[0]))
-        return out
+        keys = radix_select(digit, bits, ranks)
+        return [np.array([k], dtype=np.uint64).view(np.float64)[0] if which else float(np.array([k], dtype=np.uint32).view(np.float32)[0]) for k in keys]
 
     def download(self):
         """The float32 grid [ns][nr][nc] copied back to the host."""

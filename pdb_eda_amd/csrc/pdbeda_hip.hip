@@ -931,6 +931,7 @@ static int upload_file_impl(pdbeda_ctx *ctx, const char *path, int64_t offset, i
     if (e == hipSuccess && !geom_in_stats) e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
     close(fd);
     if (e == hipSuccess && !why && byteswap) {
+        PROF(ctx, "k_byteswap32");
         hipLaunchKernelGGL(k_byteswap32, dim3(grid_for(n_vox, 256, 8192)), dim3(256), 0, ctx->stream, (uint32_t *)d, n_vox);
         e = hipGetLastError();
     }
@@ -993,6 +994,7 @@ extern "C" int pdbeda_map_combine(pdbeda_map *a, pdbeda_map *b, double alpha, pd
     if (rc) { delete m; return rc; }
     hipError_t e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
     if (e == hipSuccess) {
+        PROF(ctx, "k_map_combine");
         hipLaunchKernelGGL(k_map_combine, dim3(grid_for(m->n_vox / 4 + 1, 256, 4096)), dim3(256), 0, ctx->stream, a->dens, b->dens, alpha, m->n_vox, d);
         e = hipGetLastError();
     }
@@ -1034,7 +1036,7 @@ extern "C" int pdbeda_map_free(pdbeda_map *m) {
 // ------------------------------------------------------------------------------------
 static int reduce_launch(pdbeda_map *m, int mode, const double *mean_dev, double cutoff, double scale, int take_sqrt, double *out_dev) {
     pdbeda_ctx *ctx = m->ctx;
-    hipLaunchKernelGGL(k_reduce_partials, dim3(N_PARTIAL), dim3(256), 0, ctx->stream, m->dens, m->n_vox, mode, mean_dev, cutoff, ctx->partials);
+    { PROF(ctx, "k_reduce_partials"); hipLaunchKernelGGL(k_reduce_partials, dim3(N_PARTIAL), dim3(256), 0, ctx->stream, m->dens, m->n_vox, mode, mean_dev, cutoff, ctx->partials); }
     hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, ctx->stream, ctx->partials, N_PARTIAL, scale, take_sqrt, out_dev);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
@@ -1183,8 +1185,9 @@ extern "C" int pdbeda_abs_select_hist(pdbeda_map *a, pdbeda_map *b, double alpha
     return with_scratch(ctx, 65536 * sizeof(uint32_t), [&](char *base) -> int {
         unsigned int *d_hist = reinterpret_cast<unsigned int *>(base);
         HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, 65536 * sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(k_abs_select_hist, dim3(grid_for(n, 256, 4096)), dim3(256), 0, ctx->stream, a->geom_dev, a->dens, b ? b->dens : nullptr,
-                           alpha, cut_a, cut_b, which, shift, prefix, prefix_mask, d_hist);
+        { PROF(ctx, "k_abs_select_hist");
+          hipLaunchKernelGGL(k_abs_select_hist, dim3(grid_for(n, 256, 4096)), dim3(256), 0, ctx->stream, a->geom_dev, a->dens, b ? b->dens : nullptr,
+                             alpha, cut_a, cut_b, which, shift, prefix, prefix_mask, d_hist); }
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, d2h(ctx, hist, d_hist, 65536 * sizeof(uint32_t)));
         return 0;
