@@ -803,8 +803,12 @@ import numpy as np
 from pdb_eda_amd import _native, ccp4, synthetic
 ctx = _native.Context(0)
 out = []
-for shape, seed, spacing, radii, nsd in (((40, 44, 48), 31, 0.5, (0.8, 1.6, 3.4), 0.3), ((36, 40, 52), 32, 0.35, (1.0, 2.4, 5.2), 1.0), ((30, 30, 30), 33, 0.5, (3.5,), 0.0)):
+prof = {}
+for shape, seed, spacing, radii, nsds, exact in (((40, 44, 48), 31, 0.5, (0.8, 1.6, 3.4), (0.3,), False), ((36, 40, 52), 32, 0.35, (1.0, 2.4, 5.2), (1.0,), False),
+                                                 ((30, 30, 30), 33, 0.5, (3.5,), (0.0,), False), ((48, 48, 48), 34, 0.35, (3.0, 3.5), (0.0, 1.0), True)):
     g = synthetic.smooth_noise(shape, seed, 1.0)
+    if exact:       # multiples of 2^-10 below 4: every partial sum of a row is exact in fp64, in any order
+        g = (np.round(np.clip(g, -4.0, 4.0) * 1024.0) / 1024.0).astype(np.float32)
     spec = synthetic.MapSpec(ncrs=shape[::-1], spacing=spacing)
     header = ccp4.DensityHeader.fromFileHeader(synthetic.ccp4_header_bytes(spec))
     m = _native.DeviceMap(ctx, g, header.geometry())
@@ -813,14 +817,23 @@ for shape, seed, spacing, radii, nsd in (((40, 44, 48), 31, 0.5, (0.8, 1.6, 3.4)
     lo, hi = np.array(header.crs2xyzCoord([2, 2, 2])), np.array(header.crs2xyzCoord([shape[2] - 3, shape[1] - 3, shape[0] - 3]))
     xyz = lo + rng.random((40, 3)) * (hi - lo)
     rad = np.array([radii[k %% len(radii)] for k in range(40)], dtype=np.float32)
-    bl = m.sphere_blobs(xyz, rad, np.arange(41), mean + nsd * std if nsd else 0.0)
-    st = bl.stats()
-    crs, off = bl.voxels()
-    lists = [sorted(map(tuple, crs[a:b].tolist())) for a, b in zip(off[:-1], off[1:])]
-    out.append({"n": st["n"].tolist(), "key": st["firstKey"].tolist(), "group": st["group"].tolist(), "total": [float.hex(float(x)) for x in st["totalDensity"]],
-                "centroid": [float.hex(float(x)) for x in st["centroid"].ravel()], "voxels": lists})
-    bl.free(); m.free()
+    for nsd in nsds:
+        if exact and %(prof)r:
+            ctx.profile_begin()
+        bl = m.sphere_blobs(xyz, rad, np.arange(41), mean + nsd * std if nsd else 0.0)
+        if exact and %(prof)r:
+            for k, v in ctx.profile_end().items():
+                prof[k] = prof.get(k, 0) + v[0]
+        st = bl.stats()
+        crs, off = bl.voxels()
+        lists = [sorted(map(tuple, crs[a:b].tolist())) for a, b in zip(off[:-1], off[1:])]
+        out.append({"n": st["n"].tolist(), "key": st["firstKey"].tolist(), "group": st["group"].tolist(), "total": [float.hex(float(x)) for x in st["totalDensity"]],
+                    "centroid": [float.hex(float(x)) for x in st["centroid"].ravel()], "voxels": lists})
+        bl.free()
+    m.free()
 json.dump(out, open(%(out)r, "w"))
+if %(prof)r:
+    json.dump(prof, open(%(prof)r, "w"))
 '''
 
 
@@ -829,18 +842,29 @@ def test_atom_engine_paths_agree(tmp_path):
     """Round 6: a per-atom sphere batch is labelled by one launch (k_atom_engine).  Its three ways through a volume -- the LDS tables, the
     kernel's own global-table path for a volume beyond them (forced here by shrinking the tables' use: PDBEDA_DEBUG_ATOM_CAPS), and the five
     generic kernels (boxes beyond one word a row or 512 rows, or PDBEDA_ATOM_ENGINE=0) -- give the same blobs to the last bit: counts, first
-    keys, groups, sums, centroids, voxel sets.  Radii from 0.8 to 5.2 A at 0.35 / 0.5 A spacing (rows of 6 to 32 voxels, boxes of 36 to
-    1 024 rows), cutoffs from 0 (every voxel of the sphere) to 1 sigma of noise (hundreds of runs, dozens of blobs in a box)."""
+    keys, groups, sums, centroids, voxel sets.  A batch takes the fused kernel only if EVERY box of it has one word a row and at most 512 rows:
+    (a box is 2 * rint(radius / spacing) + 2 voxels wide)
+      * 0.8 / 1.6 / 3.4 A at 0.5 A spacing, 0.3 sigma; 3.5 A at 0.5 A, cutoff 0: rows of 6, 8 and 16 voxels in boxes of 36 to 256 rows --
+        fused, every row NARROW (densities held by the thread);
+      * 1.0 / 2.4 / 5.2 A at 0.35 A, 1 sigma: rows of 8, 16 and 32 voxels, and the 5.2 A boxes have 1 024 rows -- the whole batch goes to
+        the generic kernels in every variant;
+      * 3.0 / 3.5 A at 0.35 A, cutoff 0 and 1 sigma: rows of 20 and 22 voxels in boxes of 400 and 484 rows -- fused (asserted below from the
+        kernels that ran), rows beyond NARROW_ROW: the fused kernel sums such a run sequentially where k_run_index takes a prefix
+        difference.  The density of this shape is multiples of 2^-10 below 4 (13 significant bits; v * k at most 19, a sum of 64 such
+        terms at most 25): both orders give the same fp64 number, so equality is required here too.
+    Cutoff 0 is every voxel of the sphere; 1 sigma of noise gives hundreds of runs and dozens of blobs in a box."""
     import json
     import subprocess
     import sys
     outs = []
     for k, env_extra in enumerate(({}, {"PDBEDA_DEBUG_ATOM_CAPS": "0,0"}, {"PDBEDA_DEBUG_ATOM_CAPS": "24,3"}, {"PDBEDA_ATOM_ENGINE": "0"})):
-        out, script = tmp_path / ("out%d.json" % k), tmp_path / ("worker%d.py" % k)
-        script.write_text(ATOM_ENGINE_WORKER % {"root": ROOT, "out": str(out)})
+        out, script, prof = tmp_path / ("out%d.json" % k), tmp_path / ("worker%d.py" % k), tmp_path / "kernels.json"
+        script.write_text(ATOM_ENGINE_WORKER % {"root": ROOT, "out": str(out), "prof": "" if env_extra else str(prof)})
         proc = subprocess.run([sys.executable, str(script)], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=280)
         assert proc.returncode == 0, proc.stderr[-3000:]
         outs.append(json.loads(out.read_text()))
     assert sum(len(c["n"]) for c in outs[0]) > 200 and max(max(c["n"]) for c in outs[0]) > 1000
+    kernels = json.loads(prof.read_text())      # the 18 / 22-voxel shape, default variant, both cutoffs
+    assert kernels.get("k_atom_engine") == 2 and "k_sphere_paint" not in kernels, kernels
     for k in (1, 2, 3):
         assert outs[k] == outs[0], k
