@@ -72,6 +72,9 @@ int pdbeda_device_pci_address(int device_id, char *out, int out_len);
 int pdbeda_ctx_create(int device_id, pdbeda_ctx **out);
 /* Bind to an existing hipStream_t (e.g. torch's current stream); stream == NULL -> new stream. */
 int pdbeda_ctx_create_on_stream(int device_id, void *hip_stream, pdbeda_ctx **out);
+/* Waits for the stream and releases the context's device memory; arenas that live handles of the caller still hold stay
+ * theirs.  PDBEDA_ERR_STATE (everything is released all the same): no handle of the context is alive and one of its arenas is
+ * still lent -- the library itself lost it.  With live handles the status says nothing about arenas. */
 int pdbeda_ctx_destroy(pdbeda_ctx *ctx);
 int pdbeda_ctx_synchronize(pdbeda_ctx *ctx);
 void *pdbeda_ctx_stream(pdbeda_ctx *ctx); /* the hipStream_t the kernels are launched on */

@@ -205,9 +205,13 @@ class Context(object):
         return out
 
     def close(self):
+        """The status of pdbeda_ctx_destroy: 0, or PDBEDA_ERR_STATE when no handle was alive and the library had lost an arena
+        (0 for a context that is closed already)."""
+        rc = 0
         if getattr(self, "_h", None):
-            self._lib.pdbeda_ctx_destroy(self._h)
+            rc = self._lib.pdbeda_ctx_destroy(self._h)
             self._h = None
+        return rc
 
     # -- context-level helpers -------------------------------------------------------
     def test_overlap(self, crs, set_offsets, a_idx, b_idx):

@@ -20,6 +20,7 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -40,9 +41,23 @@ using namespace pdbeda;
 // ------------------------------------------------------------------------------------
 // Handles
 // ------------------------------------------------------------------------------------
-struct Arena {
+struct pdbeda_ctx;
+struct Block {      // a piece of device memory as the pool and the lent list keep it
     char *base = nullptr;
     size_t cap = 0;
+};
+// A block lent by a context's pool, and its ONE owner: it goes back to that pool when the owner dies, is assigned over, or put() says so -- in stream
+// order, without a wait.  Whoever holds an Arena (a local, a map, a job record) releases it by going away: no path has to remember to.
+struct Arena : Block {
+    pdbeda_ctx *ctx = nullptr;
+    Arena() = default;
+    Arena(Arena &&o) noexcept : Block(o), ctx(o.ctx) { o.base = nullptr; o.cap = 0; }
+    Arena &operator=(Arena &&o) noexcept {
+        if (this != &o) { put(); base = o.base; cap = o.cap; ctx = o.ctx; o.base = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~Arena() { put(); }
+    void put();
 };
 
 struct pdbeda_ctx {
@@ -50,7 +65,7 @@ struct pdbeda_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
-    std::multimap<size_t, Arena> pool;  // free device arenas by capacity (reused: no hipMalloc in steady state)
+    std::multimap<size_t, Block> pool;  // free device arenas by capacity (reused: no hipMalloc in steady state)
     size_t pool_bytes = 0;              // bytes parked in the pool ...
     size_t pool_cap = (size_t)24 << 30; // ... trimmed (largest first) beyond this (PDBEDA_POOL_CAP_MB): streams x live lists x multi-GB
                                         // whole-map arenas must not creep up on the 288 GB until hipMalloc fails
@@ -195,17 +210,17 @@ struct pdbeda_bloblist {
     std::vector<double> shape_d;       // [blobs][10]: sum w, sum w d, sum w d d'
 };
 
-// One record per labelling job, deleted (its arenas back to the pool) when the last of its views is freed
+// One record per labelling job, deleted (its arenas go back to the pool with it) when the last of its views is freed
 struct LabelJob {
     pdbeda_ctx *ctx = nullptr;
     pdbeda_map *map = nullptr;
+    Arena vox_arena;                   // the voxel lists of the job's blobs, made on demand (declared first: it goes back to the pool after the job's arena)
     Arena arena;
     Job job;
     TileDims td;
     bool whole_map = false;
     int32_t *labels_dev = nullptr;     // the signed label volume: inside arena when requested
     bool labels_done = false;
-    Arena vox_arena;                   // the voxel lists of the job's blobs, made on demand
     int64_t *offsets_dev = nullptr;
     int32_t *crs_dev = nullptr;
     unsigned int *cursor_dev = nullptr;
@@ -350,14 +365,15 @@ static int arena_get(pdbeda_ctx *ctx, size_t bytes, Arena *out) {
     return rc;
 }
 
-static int arena_get_raw(pdbeda_ctx *ctx, size_t bytes, Arena *out) {
+static int arena_get_raw(pdbeda_ctx *ctx, size_t bytes, Arena *out) {      // (*out is empty)
     if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     bytes = align_up(std::max<size_t>(bytes, 256));
+    out->ctx = ctx;
     {
         std::lock_guard<std::mutex> g(ctx->pool_mu);
         auto it = ctx->pool.lower_bound(bytes);
         if (it != ctx->pool.end() && it->first <= bytes * 2 + (1u << 20)) {
-            *out = it->second;
+            static_cast<Block &>(*out) = it->second;
             ctx->pool_bytes -= it->second.cap;
             ctx->pool.erase(it);
             ctx->lent[out->base] = out->cap;
@@ -388,11 +404,15 @@ static int arena_get_raw(pdbeda_ctx *ctx, size_t bytes, Arena *out) {
     return 0;
 }
 
-static void arena_put(pdbeda_ctx *ctx, Arena &a) {
+// Back to the pool: recycled in stream order (whoever gets the block next is enqueued on the context's stream behind its last user), never a wait.
+void Arena::put() {
+    if (!base) return;
     std::lock_guard<std::mutex> g(ctx->pool_mu);
-    if (a.base) { ctx->lent.erase(a.base); ctx->pool.emplace(a.cap, a); ctx->pool_bytes += a.cap; }
-    a.base = nullptr;
-    a.cap = 0;
+    ctx->lent.erase(base);
+    ctx->pool.emplace(cap, Block{base, cap});
+    ctx->pool_bytes += cap;
+    base = nullptr;
+    cap = 0;
     while (ctx->pool_bytes > ctx->pool_cap && !ctx->pool.empty() && !ctx->timed_out) {   // trim: the largest parked arena goes back to the
         auto last = std::prev(ctx->pool.end());                                            // driver (hipFree waits for the device: rare by design)
         ctx->pool_bytes -= last->second.cap;
@@ -415,20 +435,20 @@ struct Carver {
     template <typename T> void take(T *&p, size_t n) { p = take<T>(n); }      // (T from the pointer it fills)
 };
 
-// An arena sized by `carve` and laid out by the same carve; the caller keeps it (and puts it back).  A second pass that does not end where the
-// first did -- the carve read something that changed in between -- leaves nothing behind: the arena is back in the pool, nothing was launched.
+// An arena sized by `carve` and laid out by the same carve, moved into *out (what *out held goes back to the pool first).  A failure -- a second pass
+// that does not end where the first did: the carve read something that changed in between -- leaves *out as it was and nothing behind.
+// The ownership rule: an Arena is released by its owner going away.  An explicit put() stands only where the TIME of the release is the point, with a
+// comment that says why.
 template <typename Carve>
 static int arena_carve(pdbeda_ctx *ctx, const char *site, Arena *out, Carve carve) {
     Carver size(nullptr);
     carve(size);
-    if (int rc = arena_get(ctx, size.off, out)) return rc;
-    Carver cv(out->base);
+    Arena a;
+    if (int rc = arena_get(ctx, size.off, &a)) return rc;
+    Carver cv(a.base);
     carve(cv);
-    if (cv.off != size.off || cv.off > out->cap) {
-        const size_t cap = out->cap;
-        arena_put(ctx, *out);
-        return fail(ctx, PDBEDA_ERR_STATE, "%s: scratch carve ends at %zu, sized %zu (arena of %zu)", site, cv.off, size.off, cap);
-    }
+    if (cv.off != size.off || cv.off > a.cap) return fail(ctx, PDBEDA_ERR_STATE, "%s: scratch carve ends at %zu, sized %zu (arena of %zu)", site, cv.off, size.off, a.cap);
+    *out = std::move(a);
     return 0;
 }
 
@@ -546,7 +566,6 @@ static int with_scratch(pdbeda_ctx *ctx, const char *site, Carve carve, Fn fn) {
     if (rc) return rc;
     rc = fn();
     hipError_t e = ctx_sync(ctx);
-    arena_put(ctx, a);
     if (rc) return rc;
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "stream sync: %s", hipGetErrorString(e));
     return 0;
@@ -633,9 +652,10 @@ extern "C" int pdbeda_ctx_destroy(pdbeda_ctx *ctx) {
         return PDBEDA_OK;
     }
     (void)ctx_sync(ctx);
+    const bool lost = ctx->live_handles == 0 && !ctx->lent.empty();   // (no handle is alive and an arena is still out: the library itself lost it)
     ctx_release_device(ctx, false);   // (arenas still lent belong to live handles of the caller)
     delete ctx;
-    return PDBEDA_OK;
+    return lost ? PDBEDA_ERR_STATE : PDBEDA_OK;
 }
 
 extern "C" int pdbeda_ctx_synchronize(pdbeda_ctx *ctx) {
@@ -720,6 +740,10 @@ static int fill_geom(pdbeda_ctx *ctx, const pdbeda_geometry *in, Geom *g) {
 }
 
 static int stats_enqueue(pdbeda_map *m, double *chunk_sums, double host[2], double range[2], bool want_range, bool with_geom = false);
+// stats_enqueue's scratch: three doubles per numpy chunk of the map
+static int stats_carve(pdbeda_map *m, Arena *out, double *&chunk_sums) {
+    return arena_carve(m->ctx, "map statistics", out, [&](Carver &cv) { cv.take(chunk_sums, 3 * (size_t)std::max<int64_t>(m->n_vox / NP_CHUNK, 1)); });
+}
 static bool stats_carries_geom(const pdbeda_map *m) { return m->n_vox / NP_CHUNK > 0; }      // (the chain's first launch exists: it brings the geometry along when asked to)
 static void range_apply(pdbeda_map *m, const double range[2]);
 
@@ -727,16 +751,16 @@ static int map_create(pdbeda_ctx *ctx, const float *host, const float *dev, cons
     if (!ctx || !geom || !out || (!host && !dev)) return PDBEDA_ERR_ARGUMENT;
     *out = nullptr;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pdbeda_map *m = new pdbeda_map();
+    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
     m->ctx = ctx;
     int rc = fill_geom(ctx, geom, &m->geom);
-    if (rc) { delete m; return rc; }
+    if (rc) return rc;
     m->n_vox = (int64_t)geom->ncrs[0] * geom->ncrs[1] * geom->ncrs[2];
-    if (m->n_vox >= (1ll << 32)) { delete m; return fail(ctx, PDBEDA_ERR_ARGUMENT, "grids of 2^32 voxels or more are not supported"); }
-    if (dev && ((uintptr_t)dev & 15u) != 0) { delete m; return fail(ctx, PDBEDA_ERR_ARGUMENT, "device density pointer must be 16-byte aligned"); }
+    if (m->n_vox >= (1ll << 32)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grids of 2^32 voxels or more are not supported");
+    if (dev && ((uintptr_t)dev & 15u) != 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "device density pointer must be 16-byte aligned");
     float *d = nullptr;
     rc = arena_carve(ctx, "map_create", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); if (host) cv.take(d, (size_t)m->n_vox); });
-    if (rc) { delete m; return rc; }
+    if (rc) return rc;
     hipError_t e = hipSuccess;
     if (host) {
         m->dens = d;
@@ -749,36 +773,26 @@ static int map_create(pdbeda_ctx *ctx, const float *host, const float *dev, cons
     }
     // (an uploaded map with its statistics from the same wait: see upload_file_impl; the geometry rides in the statistics' first launch then)
     const bool with_stats = (mean || std) && host && e == hipSuccess;
-    const bool geom_in_stats = with_stats && stats_carries_geom(m);
+    const bool geom_in_stats = with_stats && stats_carries_geom(m.get());
     if (e == hipSuccess && !geom_in_stats) e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
-    double st_host[2] = {0.0, 0.0}, range[2] = {0.0, 0.0};
+    double st_host[2] = {0.0, 0.0}, range[2] = {0.0, 0.0}, *chunk_sums = nullptr;
     Arena scratch;
-    bool have_scratch = false;
     if (with_stats) {
-        if (arena_get(ctx, 24 * (size_t)std::max<int64_t>(m->n_vox / NP_CHUNK, 1), &scratch) == 0) {
-            have_scratch = true;
-            if (stats_enqueue(m, reinterpret_cast<double *>(scratch.base), st_host, range, true, geom_in_stats) != 0) e = hipErrorUnknown;
-        } else {
-            e = hipErrorOutOfMemory;
-        }
+        if (stats_carve(m.get(), &scratch, chunk_sums) != 0) e = hipErrorOutOfMemory;
+        else if (stats_enqueue(m.get(), chunk_sums, st_host, range, true, geom_in_stats) != 0) e = hipErrorUnknown;
     }
     {
         const hipError_t e2 = ctx_sync(ctx);  // host buffers may be released on return
         if (e == hipSuccess) e = e2;
     }
-    if (have_scratch) arena_put(ctx, scratch);
-    if (e != hipSuccess) {
-        arena_put(ctx, m->arena);
-        delete m;
-        return fail(ctx, PDBEDA_ERR_DEVICE, "map upload: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "map upload: %s", hipGetErrorString(e));
     if (with_stats) {
-        range_apply(m, range);
+        range_apply(m.get(), range);
         if (mean) *mean = st_host[0];
         if (std) *std = st_host[1];
     }
     ctx->live_handles++;
-    *out = m;
+    *out = m.release();
     return PDBEDA_OK;
 }
 
@@ -916,18 +930,18 @@ static int upload_file_impl(pdbeda_ctx *ctx, const char *path, int64_t offset, i
     UploadEngine *engine = upload_engine(ctx->device);
     if (engine->n_readers < 1) { close(fd); return fail(ctx, PDBEDA_ERR_MEMORY, "no reader (pinned chunks, copy stream, thread) for the file upload"); }
     if (!ensure_reader_events(ctx, engine)) { close(fd); return fail(ctx, PDBEDA_ERR_MEMORY, "no event for the file upload"); }
-    pdbeda_map *m = new pdbeda_map();
+    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
     m->ctx = ctx;
     int rc = fill_geom(ctx, geom, &m->geom);
     float *d = nullptr;
     if (rc == 0) rc = arena_carve(ctx, "map upload from file", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)n_vox); });
-    if (rc) { close(fd); delete m; return rc; }
+    if (rc) { close(fd); return rc; }
     m->n_vox = n_vox;
     m->dens = d;
     m->own_dens = true;
     const char *why = nullptr;
     hipError_t e = engine_copy(ctx, engine, fd, offset, nullptr, (char *)d, need, &why);   // (first: the stream is idle, its query says so at once)
-    const bool geom_in_stats = (mean || std) && stats_carries_geom(m);      // (the statistics' first launch brings the geometry along: a copy launch less)
+    const bool geom_in_stats = (mean || std) && stats_carries_geom(m.get());      // (the statistics' first launch brings the geometry along: a copy launch less)
     if (e == hipSuccess && !geom_in_stats) e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
     close(fd);
     if (e == hipSuccess && !why && byteswap) {
@@ -938,34 +952,24 @@ static int upload_file_impl(pdbeda_ctx *ctx, const char *path, int64_t offset, i
     // mean / std (and the range of the blob sums' quantum) queued behind the copies: ONE wait for the map and its statistics -- every
     // caller asks for them next (cutoffs are mean + k std), and a wait of their own was one of a pool entry's host round trips
     const bool with_stats = (mean || std) && e == hipSuccess && !why;
-    double host[2] = {0.0, 0.0}, range[2] = {0.0, 0.0};
+    double host[2] = {0.0, 0.0}, range[2] = {0.0, 0.0}, *chunk_sums = nullptr;
     Arena scratch;
-    bool have_scratch = false;
     if (with_stats) {
-        if (arena_get(ctx, 24 * (size_t)std::max<int64_t>(n_vox / NP_CHUNK, 1), &scratch) == 0) {
-            have_scratch = true;
-            if (stats_enqueue(m, reinterpret_cast<double *>(scratch.base), host, range, true, geom_in_stats) != 0) e = hipErrorUnknown;
-        } else {
-            e = hipErrorOutOfMemory;
-        }
+        if (stats_carve(m.get(), &scratch, chunk_sums) != 0) e = hipErrorOutOfMemory;
+        else if (stats_enqueue(m.get(), chunk_sums, host, range, true, geom_in_stats) != 0) e = hipErrorUnknown;
     }
     const double t_s0 = now_s();
     const hipError_t e2 = ctx_sync(ctx);      // (&m->geom is free again)
     if (upload_trace()) fprintf(stderr, "upload: final wait %.3f ms\n", 1e3 * (now_s() - t_s0));
-    if (have_scratch) arena_put(ctx, scratch);
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess || why) {
-        arena_put(ctx, m->arena);
-        delete m;
-        return why ? fail(ctx, PDBEDA_ERR_ARGUMENT, "reading %s: %s", path, why) : fail(ctx, PDBEDA_ERR_DEVICE, "map upload from file: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess || why) return why ? fail(ctx, PDBEDA_ERR_ARGUMENT, "reading %s: %s", path, why) : fail(ctx, PDBEDA_ERR_DEVICE, "map upload from file: %s", hipGetErrorString(e));
     if (with_stats) {
-        range_apply(m, range);
+        range_apply(m.get(), range);
         if (mean) *mean = host[0];
         if (std) *std = host[1];
     }
     ctx->live_handles++;
-    *out = m;
+    *out = m.release();
     return PDBEDA_OK;
 }
 
@@ -985,13 +989,13 @@ extern "C" int pdbeda_map_combine(pdbeda_map *a, pdbeda_map *b, double alpha, pd
     if (a->n_vox != b->n_vox || memcmp(a->geom.ncrs, b->geom.ncrs, sizeof a->geom.ncrs) != 0)
         return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different shapes");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pdbeda_map *m = new pdbeda_map();
+    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
     m->ctx = ctx;
     m->geom = a->geom;
     m->n_vox = a->n_vox;
     float *d = nullptr;
     int rc = arena_carve(ctx, "map combine", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)m->n_vox); });
-    if (rc) { delete m; return rc; }
+    if (rc) return rc;
     hipError_t e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
     if (e == hipSuccess) {
         PROF(ctx, "k_map_combine");
@@ -999,15 +1003,11 @@ extern "C" int pdbeda_map_combine(pdbeda_map *a, pdbeda_map *b, double alpha, pd
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = ctx_sync(ctx);   // (&m->geom is read by the copy above)
-    if (e != hipSuccess) {
-        arena_put(ctx, m->arena);
-        delete m;
-        return fail(ctx, PDBEDA_ERR_DEVICE, "map combine: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "map combine: %s", hipGetErrorString(e));
     m->dens = d;
     m->own_dens = true;
     ctx->live_handles++;
-    *out = m;
+    *out = m.release();
     return PDBEDA_OK;
 }
 
@@ -1025,7 +1025,6 @@ extern "C" int pdbeda_map_free(pdbeda_map *m) {
     pdbeda_ctx *ctx = m->ctx;
     // the arena goes back to the context's pool: whoever gets it next is enqueued on this stream behind the last kernel that
     // reads the map -- no wait, no hipFree (which would synchronise the whole device under the other streams of a pool)
-    arena_put(ctx, m->arena);
     ctx->live_handles--;
     delete m;
     return PDBEDA_OK;
@@ -1509,8 +1508,8 @@ static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool w
         hipLaunchKernelGGL(k_emit_tiles, dim3(std::min<unsigned>(512u, ((unsigned)tiles_pp + 1u) / 2u)), dim3(256), 0, st, job, m->geom_dev);
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { arena_put(ctx, arena); return fail(ctx, PDBEDA_ERR_DEVICE, "whole-map labelling launch: %s", hipGetErrorString(e)); }
-    out->job = job; out->arena = arena; out->td = td; out->labels_dev = labels_dev; out->labels_done = labels; out->bytes = need;
+    if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "whole-map labelling launch: %s", hipGetErrorString(e));
+    out->job = job; out->arena = std::move(arena); out->td = td; out->labels_dev = labels_dev; out->labels_done = labels; out->bytes = need;
     out->cut_pos = cut_pos; out->cut_neg = cut_neg; out->want_pos = want_pos; out->want_neg = want_neg; out->flags = flags; out->tier = tier; out->unit_form = unit_form;
     return PDBEDA_OK;
 }
@@ -1518,15 +1517,16 @@ static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool w
 static int full_blobs_impl(pdbeda_map *m, float cut_pos, float cut_neg, bool want_pos, bool want_neg, uint32_t flags,
                            pdbeda_bloblist **out_pos, pdbeda_bloblist **out_neg) {
     pdbeda_ctx *ctx = m->ctx;
-    LabelJob *lj = new_label_job(ctx, m);
+    std::unique_ptr<LabelJob> lj(new_label_job(ctx, m));
     lj->whole_map = true;
     const int tier = ctx->debug_worst_case_arena ? 1 : 0, form = tier;   // (the debug hook: the second run's shape at once)
-    int rc = whole_map_enqueue(m, cut_pos, cut_neg, want_pos, want_neg, flags, tier, form, lj);
-    if (rc) { delete lj; return rc; }
+    int rc = whole_map_enqueue(m, cut_pos, cut_neg, want_pos, want_neg, flags, tier, form, lj.get());
+    if (rc) return rc;
     for (int p = 0; p < lj->td.n_planes; ++p) {
-        pdbeda_bloblist *bl = job_view(lj, p, p, p + 1, lj->td.sign[p]);
+        pdbeda_bloblist *bl = job_view(lj.get(), p, p, p + 1, lj->td.sign[p]);
         if (bl->sign > 0) *out_pos = bl; else *out_neg = bl;
     }
+    lj.release();      // (the views own the job now: pdbeda_bloblist_free)
     return PDBEDA_OK;
 }
 
@@ -1605,9 +1605,9 @@ static int list_resolve_counts(pdbeda_bloblist *bl) {
         const int tier = 1, form = 1;
         if (tier == lj->tier && form == lj->unit_form) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling overflowed its worst-case arena");
         if (lj->voxels_done) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling: overflow noticed after the voxel lists were made");
-        arena_put(ctx, lj->arena);                         // (stream order: the first run's kernels are done -- ctx_sync above)
+        lj->arena.put();      // the first run's arena goes back BEFORE the larger one is carved: the job's peak is the larger of the two, not their sum (stream order: the first run's kernels are done -- ctx_sync above)
         int rc = whole_map_enqueue(lj->map, lj->cut_pos, lj->cut_neg, lj->want_pos, lj->want_neg, lj->flags, tier, form, lj);
-        if (rc) { lj->arena.base = nullptr; lj->arena.cap = 0; return rc; }
+        if (rc) return rc;      // (the record holds no arena now)
         lj->reruns += 1;
         const int rc_fetch = fetch();
         if (rc_fetch) return rc_fetch;
@@ -1731,7 +1731,8 @@ static int list_materialise_voxels(pdbeda_bloblist *bl) {
     const int64_t nb = lj->n_blobs;
     // total voxels unknown until the offsets scan; bound by key bits
     const int64_t max_vox = job.key_words * 64;
-    int rc = arena_carve(ctx, "voxel lists", &lj->vox_arena, [&](Carver &cv) {
+    Arena lists;      // (the job's only once the launches are queued: a failed call leaves the record without lists, and nothing lent)
+    int rc = arena_carve(ctx, "voxel lists", &lists, [&](Carver &cv) {
         cv.take(lj->offsets_dev, nb + 1);
         cv.take(lj->cursor_dev, std::max<int64_t>(nb, 1));
         cv.take(lj->crs_dev, 3 * std::max<int64_t>(max_vox, 1));
@@ -1743,6 +1744,7 @@ static int list_materialise_voxels(pdbeda_bloblist *bl) {
         hipLaunchKernelGGL(k_voxel_lists, dim3(grid_for(job.total_words * 64, 256, 8192)), dim3(256), 0, st, job, lj->offsets_dev,
                            lj->cursor_dev, lj->crs_dev);
     HIP_TRY(ctx, hipGetLastError());
+    lj->vox_arena = std::move(lists);
     lj->voxels_done = true;      // (enqueued: whatever reads the lists is ordered behind them on the stream, and waits there)
     return 0;
 }
@@ -1814,7 +1816,7 @@ static int list_moments_compute(pdbeda_bloblist *bl) {
     long long *d_l = nullptr;
     double *d_d = nullptr;
     Arena arena;
-    const int rc_arena = arena_carve(ctx, "blob moments", &arena, [&](Carver &cv) {
+    const int rc_arena = arena_carve(ctx, "blob moments", &arena, [&](Carver &cv) {      // (back to the pool on every way out, in stream order: whatever a failed call left queued runs before the arena's next user)
         cv.take(a.park_rho, (size_t)nv); cv.take(a.park_blob, (size_t)nv);
         cv.take(a.box, BS_BOX * nb); cv.take(a.rec, BS_REC * nb);
         cv.take(d_widest, 8);      // (right behind the sums records: ONE fill clears both)
@@ -1823,35 +1825,30 @@ static int list_moments_compute(pdbeda_bloblist *bl) {
         cv.take(d_d, 10 * nb);
     });
     if (rc_arena) return rc_arena;
-    auto run = [&]() -> int {
-        a.geom = m->geom_dev; a.dens = m->dens;
-        a.crs = lj->crs_dev; a.off = lj->offsets_dev + ranks.lo; a.cnt = cnt;
-        a.fix_mul = m->fix_mul;
-        hipStream_t st = ctx->stream;
-        const unsigned chunks = (unsigned)((nv + BS_CHUNK - 1) / BS_CHUNK);
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)a.box, (int)0x80000000u, BS_BOX * nb, st));
-        HIP_TRY(ctx, hipMemsetAsync(a.rec, 0, (size_t)((char *)(d_widest + 8) - (char *)a.rec), st));      // (the sums records and the widest box behind them)
-        { PROF(ctx, "k_blobshape_box"); hipLaunchKernelGGL(k_blobshape_box, dim3(chunks), dim3(256), 0, st, a); }
-        { PROF(ctx, "k_blobshape_widths"); hipLaunchKernelGGL(k_blobshape_widths, dim3(grid_for(cnt, 256, 1024)), dim3(256), 0, st, a.box, cnt, d_widest); }
-        HIP_TRY(ctx, hipGetLastError());
-        unsigned long long widest = 0;
-        HIP_TRY(ctx, d2h(ctx, &widest, d_widest, 8));
-        HIP_TRY(ctx, ctx_sync(ctx));
-        if (widest >= (unsigned long long)BS_MAX_WIDTH)
-            return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a blob's box is %llu voxels wide (the limit is %d)", widest, BS_MAX_WIDTH - 1);
-        { PROF(ctx, "k_blobshape_sums"); hipLaunchKernelGGL(k_blobshape_sums, dim3(chunks), dim3(256), 0, st, a); }
-        { PROF(ctx, "k_blobshape_finish"); hipLaunchKernelGGL(k_blobshape_finish, dim3(grid_for(cnt, 256)), dim3(256), 0, st, a.box, a.rec, cnt, 1.0 / m->fix_mul, d_i, d_l, d_d); }
-        HIP_TRY(ctx, hipGetLastError());
-        bl->shape_i.resize(10 * nb); bl->shape_l.resize(9 * nb); bl->shape_d.resize(10 * nb);
-        const D2HItem rows[3] = {{bl->shape_i.data(), d_i, sizeof(int32_t) * 10 * nb}, {bl->shape_l.data(), d_l, sizeof(long long) * 9 * nb}, {bl->shape_d.data(), d_d, sizeof(double) * 10 * nb}};
-        HIP_TRY(ctx, d2h_many(ctx, rows, 3));
-        HIP_TRY(ctx, ctx_sync(ctx));
-        return PDBEDA_OK;
-    };
-    const int rc = run();
-    arena_put(ctx, arena);      // (stream order: whatever is still queued on a failed call runs before the arena's next user)
-    if (rc == PDBEDA_OK) bl->shape_done = true;
-    return rc;
+    a.geom = m->geom_dev; a.dens = m->dens;
+    a.crs = lj->crs_dev; a.off = lj->offsets_dev + ranks.lo; a.cnt = cnt;
+    a.fix_mul = m->fix_mul;
+    hipStream_t st = ctx->stream;
+    const unsigned chunks = (unsigned)((nv + BS_CHUNK - 1) / BS_CHUNK);
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)a.box, (int)0x80000000u, BS_BOX * nb, st));
+    HIP_TRY(ctx, hipMemsetAsync(a.rec, 0, (size_t)((char *)(d_widest + 8) - (char *)a.rec), st));      // (the sums records and the widest box behind them)
+    { PROF(ctx, "k_blobshape_box"); hipLaunchKernelGGL(k_blobshape_box, dim3(chunks), dim3(256), 0, st, a); }
+    { PROF(ctx, "k_blobshape_widths"); hipLaunchKernelGGL(k_blobshape_widths, dim3(grid_for(cnt, 256, 1024)), dim3(256), 0, st, a.box, cnt, d_widest); }
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long widest = 0;
+    HIP_TRY(ctx, d2h(ctx, &widest, d_widest, 8));
+    HIP_TRY(ctx, ctx_sync(ctx));
+    if (widest >= (unsigned long long)BS_MAX_WIDTH)
+        return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a blob's box is %llu voxels wide (the limit is %d)", widest, BS_MAX_WIDTH - 1);
+    { PROF(ctx, "k_blobshape_sums"); hipLaunchKernelGGL(k_blobshape_sums, dim3(chunks), dim3(256), 0, st, a); }
+    { PROF(ctx, "k_blobshape_finish"); hipLaunchKernelGGL(k_blobshape_finish, dim3(grid_for(cnt, 256)), dim3(256), 0, st, a.box, a.rec, cnt, 1.0 / m->fix_mul, d_i, d_l, d_d); }
+    HIP_TRY(ctx, hipGetLastError());
+    bl->shape_i.resize(10 * nb); bl->shape_l.resize(9 * nb); bl->shape_d.resize(10 * nb);
+    const D2HItem rows[3] = {{bl->shape_i.data(), d_i, sizeof(int32_t) * 10 * nb}, {bl->shape_l.data(), d_l, sizeof(long long) * 9 * nb}, {bl->shape_d.data(), d_d, sizeof(double) * 10 * nb}};
+    HIP_TRY(ctx, d2h_many(ctx, rows, 3));
+    HIP_TRY(ctx, ctx_sync(ctx));
+    bl->shape_done = true;
+    return PDBEDA_OK;
 }
 
 extern "C" int pdbeda_bloblist_moments(pdbeda_bloblist *bl, int32_t *box_lo, int32_t *box_hi, int32_t *extreme_crs, float *extreme, int64_t *s1, int64_t *s2,
@@ -1905,7 +1902,6 @@ extern "C" int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host)
     hipLaunchKernelGGL(k_labels_decode, dim3(grid_for(nvox, 256, 4096)), dim3(256), 0, ctx->stream, signed_vol, nvox, bl->sign, decoded);
     hipError_t e = d2h(ctx, labels_host, decoded, 4 * nvox);
     if (e == hipSuccess) e = ctx_sync(ctx);
-    arena_put(ctx, a);
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "labels: %s", hipGetErrorString(e));
     return PDBEDA_OK;
 }
@@ -1999,10 +1995,10 @@ extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, c
         HIP_TRY(ctx, ctx_sync(ctx));
         return PDBEDA_OK;
     };
-    const int rc = run();
-    if (rc != PDBEDA_OK) (void)ctx_sync(ctx);      // (`packed` is freed on return and the table's copy may be a hipMemcpyAsync out of it: nothing of a failed call may still read it)
-    arena_put(ctx, arena);      // (stream order: whatever is still queued on a failed call runs before the arena's next user)
-    if (rc != PDBEDA_OK) return rc;
+    if (const int rc = run()) {
+        (void)ctx_sync(ctx);      // (`packed` is freed on return and the table's copy may be a hipMemcpyAsync out of it: nothing of a failed call may still read it)
+        return rc;
+    }
     for (size_t i = 0; i < nb; ++i) {
         const int32_t *r = rows.data() + 8 * i;
         if (index) index[i] = r[0];
@@ -2025,8 +2021,6 @@ extern "C" int pdbeda_bloblist_free(pdbeda_bloblist *bl) {
     if (--lj->live == 0) {
         // last list of the job.  Arenas are recycled only inside this context, i.e. by work that
         // is enqueued later on the SAME stream, so stream order protects them: no host sync.
-        arena_put(ctx, lj->arena);
-        arena_put(ctx, lj->vox_arena);
         delete lj;
     }
     return PDBEDA_OK;
@@ -2085,7 +2079,8 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
     // (the two lists of ONE fused labelling job: one signed volume serves both planes)
     const bool shared = need_own[0] && need_own[1] && pj->blobs[0]->job == pj->blobs[1]->job;
     if (shared) need_own[1] = false;
-    const int rc = arena_carve(ctx, "peak search", &pj->arena, [&](Carver &cv) {
+    Arena arena;      // (the job's only once the launches are queued: a failed run leaves the record without an arena)
+    const int rc = arena_carve(ctx, "peak search", &arena, [&](Carver &cv) {
         a.ctr = cv.take<PeakCounters>(1);
         int32_t *own[2] = {nullptr, nullptr};
         for (int p = 0; p < a.n_planes; ++p) {
@@ -2121,7 +2116,8 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
         { PROF(ctx, "k_peak_finish"); hipLaunchKernelGGL(k_peak_finish, dim3(grid_for(most, 256, 2048)), dim3(256), 0, ctx->stream, a, m->dens, m->geom_dev); }
         e = hipGetLastError();
     }
-    if (e != hipSuccess) { arena_put(ctx, pj->arena); return fail(ctx, PDBEDA_ERR_DEVICE, "peak search launch: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "peak search launch: %s", hipGetErrorString(e));
+    pj->arena = std::move(arena);
     return PDBEDA_OK;
 }
 
@@ -2151,7 +2147,7 @@ static int peaks_impl(pdbeda_map *m, int n_planes, const float cut[2], const int
         const int rc = peaks_check_blobs(m, blobs[p], sign[p], cut[p]);
         if (rc) return rc;
     }
-    PeakJob *pj = new PeakJob();
+    std::unique_ptr<PeakJob> pj(new PeakJob());
     pj->ctx = ctx;
     pj->map = m;
     memset(&pj->args, 0, sizeof pj->args);
@@ -2169,16 +2165,17 @@ static int peaks_impl(pdbeda_map *m, int n_planes, const float cut[2], const int
         seg[p] = PK_C * PK_R * PK_S / 64;
         cap[p] = n_tiles * seg[p];
     }
-    const int rc = peaks_enqueue(pj, cap, seg);
-    if (rc) { delete pj; return rc; }
+    const int rc = peaks_enqueue(pj.get(), cap, seg);
+    if (rc) return rc;
     for (int p = 0; p < n_planes; ++p) {
         pdbeda_peaklist *pl = new pdbeda_peaklist();
-        pl->job = pj;
+        pl->job = pj.get();
         pl->plane = p;
         pj->refs++;
         ctx->live_handles++;
         *out[p] = pl;
     }
+    pj.release();      // (the lists own the job now: pdbeda_peaklist_free)
     return PDBEDA_OK;
 }
 
@@ -2224,9 +2221,9 @@ static int peaks_resolve(PeakJob *pj) {
             seg[p] = std::max<int64_t>((int64_t)pj->args.plane[p].seg, (int64_t)c.max_tile[p]);
             cap[p] = std::max<int64_t>(1, (int64_t)c.peaks[p]);
         }
-        arena_put(ctx, pj->arena);                         // (stream order: the first run is done -- ctx_sync above)
+        pj->arena.put();      // the first run's arena goes back BEFORE the one of the counters' size is carved: the peak is the larger of the two, not their sum (stream order: the first run is done -- ctx_sync above)
         const int rc = peaks_enqueue(pj, cap, seg);
-        if (rc) { pj->arena.base = nullptr; pj->arena.cap = 0; return rc; }
+        if (rc) return rc;      // (the record holds no arena now)
         pj->reruns = 1;
     }
     std::vector<unsigned long long> keys[2];
@@ -2420,9 +2417,10 @@ static int basins_compute(pdbeda_peaklist *pl, int32_t *basin_host) {
         HIP_TRY(ctx, ctx_sync(ctx));
         return PDBEDA_OK;
     };
-    const int rc = run();
-    arena_put(ctx, arena);      // (stream order: whatever is still queued on a failed call runs before the arena's next user)
-    if (rc) return rc;
+    if (const int rc = run()) {
+        (void)ctx_sync(ctx);      // (`peak_box` is freed on return and its copy may be a hipMemcpyAsync out of it: nothing of a failed call may still read it)
+        return rc;
+    }
     const double fix_inv = 1.0 / fix_mul;      // (a power of two: the products below are exact)
     br.n.resize(np); br.sum.resize(np); br.s1.resize(3 * np); br.sw1.resize(3 * np); br.saddle.resize(np); br.neighbour.resize(np);
     for (size_t i = 0; i < np; ++i) {
@@ -2473,10 +2471,7 @@ extern "C" int pdbeda_peaklist_free(pdbeda_peaklist *pl) {
     PeakJob *pj = pl->job;
     pl->freed = true;
     pj->ctx->live_handles--;
-    if (--pj->refs == 0) {   // last list of the job: the arena is recycled in stream order, as a blob list's
-        arena_put(pj->ctx, pj->arena);
-        delete pj;
-    }
+    if (--pj->refs == 0) delete pj;   // last list of the job: the arena is recycled in stream order, as a blob list's
     delete pl;
     return PDBEDA_OK;
 }
@@ -2485,7 +2480,7 @@ extern "C" int pdbeda_peaklist_free(pdbeda_peaklist *pl) {
 // Sphere / list batches
 // ------------------------------------------------------------------------------------
 struct GroupSetup {
-    Arena in_arena;          // inputs + boxes + bounds (scratch, released after painting)
+    Arena in_arena;          // inputs + boxes + bounds (scratch: grouped_job releases it behind the painting, any other way out with the setup)
     double *d_xyz = nullptr;
     float *d_radii = nullptr;
     int32_t *d_item_group = nullptr;
@@ -2738,16 +2733,16 @@ static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n
         // map_fix_mul is about to WAIT (a map whose range is not known yet), and a wait hands the pinned block out afresh: inputs staged there must be on
         // their way before it, not left to k_job_init behind it
         const hipError_t ep = flush_pending(ctx, &gs);
-        if (ep != hipSuccess) { arena_put(ctx, gs.in_arena); return fail(ctx, PDBEDA_ERR_DEVICE, "grouped blobs: %s", hipGetErrorString(ep)); }
+        if (ep != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "grouped blobs: %s", hipGetErrorString(ep));
     }
     int rc_fix = map_fix_mul(m);
-    if (rc_fix) { arena_put(ctx, gs.in_arena); return rc_fix; }
-    Job job;
+    if (rc_fix) return rc_fix;
+    std::unique_ptr<LabelJob> lj(new_label_job(ctx, m));
+    Job &job = lj->job;
     memset(&job, 0, sizeof job);
     job.fix_mul = m->fix_mul;
-    Arena arena;
-    int rc = arena_carve(ctx, "grouped blobs", &arena, [&](Carver &cv) { job_carve(job, cv, (int)n_groups, gs.total_words, gs.total_keys, max_runs, max_runs, 0, nullptr); });
-    if (rc) { arena_put(ctx, gs.in_arena); return rc; }
+    int rc = arena_carve(ctx, "grouped blobs", &lj->arena, [&](Carver &cv) { job_carve(job, cv, (int)n_groups, gs.total_words, gs.total_keys, max_runs, max_runs, 0, nullptr); });
+    if (rc) return rc;
     hipStream_t st = ctx->stream;
     hipError_t e = hipSuccess;
     {   // volume descriptors into the job + zeroes over counters, masks, first-key bitmap and both levels of rank counters (adjacent in the arena: job_carve): one launch
@@ -2786,17 +2781,12 @@ static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n
         e = hipGetLastError();
     }
     if (e == hipSuccess) rc = engine_enqueue(ctx, m, job, max_runs, fused_atoms, unordered);
-    // (the inputs are consumed by the paint kernel: whoever gets their arena next is enqueued behind it on this stream)
-    arena_put(ctx, gs.in_arena);
-    if (e != hipSuccess || rc) {
-        arena_put(ctx, arena);
-        return rc ? rc : fail(ctx, PDBEDA_ERR_DEVICE, "grouped blobs: %s", hipGetErrorString(e));
-    }
-    LabelJob *lj = new_label_job(ctx, m);
-    lj->job = job;
-    lj->arena = arena;
+    // The inputs go back NOW, not with the caller's setup: the paint kernel has consumed them (whoever gets their arena next is enqueued behind it on
+    // this stream), and the union job of the same pdbeda_aggregate_cloud call takes this very block for its own inputs
+    gs.in_arena.put();
+    if (e != hipSuccess || rc) return rc ? rc : fail(ctx, PDBEDA_ERR_DEVICE, "grouped blobs: %s", hipGetErrorString(e));
     lj->host_boxes.swap(gs.host_boxes);
-    *out = job_view(lj, 0, 0, (int)n_groups, 1);      // (one list over all the volumes)
+    *out = job_view(lj.release(), 0, 0, (int)n_groups, 1);      // (one list over all the volumes)
     return PDBEDA_OK;
 }
 
@@ -2806,7 +2796,7 @@ static int grouped_blobs(pdbeda_map *m, const double *xyz, const float *radii, c
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     GroupSetup gs;
     int rc = group_setup(m, xyz, radii, crs, n_items, group_offsets, n_groups, &gs);
-    if (rc) { arena_put(ctx, gs.in_arena); return rc; }
+    if (rc) return rc;
     return grouped_job(m, gs, n_items, n_groups, xyz != nullptr, cutoff, out);
 }
 
@@ -2832,7 +2822,7 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
     if (n_groups == 0) return PDBEDA_OK;
     GroupSetup gs;
     int rc = group_setup(m, xyz, radii, nullptr, n_atoms, group_offsets, n_groups, &gs);
-    if (rc) { arena_put(ctx, gs.in_arena); return rc; }
+    if (rc) return rc;
     std::vector<unsigned long long> h_cnt(n_groups);
     std::vector<unsigned int> h_inv(n_groups);
     auto deliver_counts = [&] {      // (both paths end here, behind their wait)
@@ -2861,7 +2851,6 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
                                                             s_vols, (int)n_groups, cutoff, o_pos, o_neg, o_cnt, o_inv); }
             hipError_t e1 = hipGetLastError();
             if (e1 == hipSuccess) e1 = ctx_sync(ctx);
-            arena_put(ctx, gs.in_arena);
             if (e1 != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: %s", hipGetErrorString(e1));
             return deliver_counts();
         }
@@ -2881,7 +2870,7 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
         cv.take(d_inv, n_groups);
         zero_bytes = cv.off;      // (all of it)
     });
-    if (rc) { arena_put(ctx, gs.in_arena); return rc; }
+    if (rc) return rc;
     hipStream_t st = ctx->stream;
     hipError_t e;
     {   // the staged inputs into the scratch (when group_setup left their copy to us) and zeroes over masks and sums: one launch
@@ -2907,8 +2896,6 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
         e = d2h_many(ctx, parts, 5);
     }
     if (e == hipSuccess) e = ctx_sync(ctx);
-    arena_put(ctx, a);
-    arena_put(ctx, gs.in_arena);
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: %s", hipGetErrorString(e));
     if (setup.overflow != 0u) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: the device's volumes outgrew what the host sized the batch for");
     return deliver_counts();
@@ -3019,12 +3006,8 @@ extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t 
                 if (parts[k].dst) e = d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes);
         }
         if (e == hipSuccess) e = ctx_sync(ctx);      // (delivers the chunk's rows and rewinds the block for the next chunk)
-        if (e != hipSuccess) {
-            arena_put(ctx, scratch);
-            return fail(ctx, PDBEDA_ERR_DEVICE, "radial profiles: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "radial profiles: %s", hipGetErrorString(e));
     }
-    arena_put(ctx, scratch);
     return PDBEDA_OK;
 }
 
@@ -3369,8 +3352,8 @@ extern "C" int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int
             for (int64_t c = 0; c < n_cand; ++c) kept_out[c] = h_keep[(size_t)c] ? 1 : 0;
         if (n_q == 0 || h_total == 0) return 0;
         if ((int64_t)h_total > lanes) return fail(ctx, PDBEDA_ERR_DEVICE, "neighbour grid holds %u points of at most %lld", h_total, (long long)lanes);
-        if (int e = arena_get(ctx, align_up(24 * (size_t)h_total), &B)) return e;
-        double *d_sorted_n = reinterpret_cast<double *>(B.base);
+        double *d_sorted_n = nullptr;
+        if (int e = arena_carve(ctx, "crystal contacts: neighbours", &B, [&](Carver &cv) { cv.take(d_sorted_n, 3 * (size_t)h_total); })) return e;
         { PROF(ctx, "k_image_scatter"); hipLaunchKernelGGL(k_image_scatter, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_keep, gn, d_cursor_n, d_sorted_n, (int64_t)h_total); }
         { PROF(ctx, "k_contact_min"); hipLaunchKernelGGL(k_contact_min, dim3(grid_for(n_q, 256)), dim3(256), 0, st, d_q, n_q, d_sorted_n, d_start_n, gn, d_dist); }
         HIP_TRY(ctx, hipGetLastError());
@@ -3378,10 +3361,10 @@ extern "C" int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int
         HIP_TRY(ctx, ctx_sync(ctx));                 // wait 2: the rows
         return 0;
     }();
-    if (rc) (void)ctx_sync(ctx);                     // (a failed call drains the stream before its arenas go back to the pool)
-    if (B.base) arena_put(ctx, B);
-    arena_put(ctx, A);
-    if (rc) return rc;
+    if (rc) {
+        (void)ctx_sync(ctx);                         // (a failed call drains the stream before its arenas go back to the pool)
+        return rc;
+    }
     *n_out = rows;
     if (rows > cap) return fail(ctx, PDBEDA_ERR_CAPACITY, "need capacity %lld", (long long)rows);
     return PDBEDA_OK;
@@ -3542,6 +3525,11 @@ struct pdbeda_cloud {
     std::vector<uint8_t> owner_state;
     double totals[4] = {0.0, 0.0, 0.0, 0.0};
 };
+// A blob list that pdbeda_aggregate_cloud makes for itself: freed when the call returns, however it returns
+struct ScopedList {
+    pdbeda_bloblist *bl = nullptr;
+    ~ScopedList() { if (bl) pdbeda_bloblist_free(bl); }
+};
 
 // numpy's add.reduce over a contiguous float64 array (see k_np_chunk_sums): blocks of 8192 accumulated in order, each a
 // pairwise sum.  mode 1: (x - shift)^2.  The centroid-distance cut-off (densityAnalysis.py:607) decides which atoms are
@@ -3614,12 +3602,11 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     for (int64_t o = 0; o < at->n_owners; ++o)
         if (at->owner_key[o] < 0 || at->owner_key[o] >= at->n_keys) return fail(ctx, PDBEDA_ERR_ARGUMENT, "owner key out of range");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    pdbeda_cloud *res = new pdbeda_cloud();
+    std::unique_ptr<pdbeda_cloud> res(new pdbeda_cloud());      // (the caller's on success: *out = res.release())
     res->ctx = ctx;
     res->owner_state.assign((size_t)at->n_owners, 0);
     res->totals[3] = NAN;
-    *out = res;
-    if (n == 0) return PDBEDA_OK;
+    if (n == 0) { *out = res.release(); return PDBEDA_OK; }
     hipStream_t st = ctx->stream;
     // PDBEDA_CLOUD_TRACE=1 (experiments): the sizes of the two jobs and the host-side phases of this call on stderr
     static const bool cloud_trace = env_set("PDBEDA_CLOUD_TRACE");
@@ -3627,25 +3614,25 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     double t_wait1 = 0.0, t_pooled = 0.0, t_marks[6] = {0, 0, 0, 0, 0, 0};
 
     // ---- 1. the clouds of every atom: one sphere batch, a group per atom (findAberrantBlobs, 603) ----
-    pdbeda_bloblist *clouds = nullptr;
+    ScopedList clouds_list, uni_list;      // (in this order: the union job's list is freed first, as it is made last)
+    pdbeda_bloblist *&clouds = clouds_list.bl, *&uni = uni_list.bl;
     {
         std::vector<int64_t> goff((size_t)n + 1);
         for (int64_t i = 0; i <= n; ++i) goff[(size_t)i] = i;
         int rc = grouped_blobs(m, at->xyz, at->radius, nullptr, n, goff.data(), n, density_cutoff, &clouds);
-        if (rc) { delete res; *out = nullptr; return rc; }
+        if (rc) return rc;
     }
-    auto bail = [&](int rc, pdbeda_bloblist *a, pdbeda_bloblist *b) { if (a) pdbeda_bloblist_free(a); if (b) pdbeda_bloblist_free(b); delete res; *out = nullptr; return rc; };
     std::vector<int64_t> c_n;
     std::vector<double> c_tot, c_cen;
     std::vector<int32_t> c_grp;
     int rc = list_stats_one_trip(clouds, 4 * n + 64, c_n, c_tot, c_cen, c_grp);   // (an atom has one to three clouds: the count and the table in one wait)
-    if (rc) return bail(rc, clouds, nullptr);
+    if (rc) return rc;
     const int64_t nb = (int64_t)c_n.size();
     t_wait1 = now_s();
     // the voxel lists of the clouds (what the pooled voxels and the overlap tests are gathered from) are made by the device
     // while the host decides what to pool
     rc = list_materialise_voxels(clouds);
-    if (rc) return bail(rc, clouds, nullptr);
+    if (rc) return rc;
 
     t_marks[0] = now_s();
     // ---- 2. host: centroid-distance cut-off, best cloud, pool (604-642) ----
@@ -3690,7 +3677,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         res->atom_dist.push_back(norm3(at->xyz + 3 * i, c_cen.data() + 3 * best));
     }
     const int64_t n_pool = (int64_t)pool_cloud.size();
-    if (n_pool == 0) { pdbeda_bloblist_free(clouds); return PDBEDA_OK; }
+    if (n_pool == 0) { *out = res.release(); return PDBEDA_OK; }
     t_marks[2] = now_s();
 
     // ---- 3. device: pooled voxels -> union job (a group per residue + the domain group) ----
@@ -3718,7 +3705,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         res->owner_state[(size_t)o] = 1;
         for (int64_t q = at->bonded_off[k]; q < at->bonded_off[k + 1]; ++q) {
             const int32_t k2 = at->bonded[q];
-            if (k2 < 0 || k2 >= at->n_keys) return bail(fail(ctx, PDBEDA_ERR_ARGUMENT, "bonded key out of range"), clouds, nullptr);
+            if (k2 < 0 || k2 >= at->n_keys) return fail(ctx, PDBEDA_ERR_ARGUMENT, "bonded key out of range");
             const int32_t ib = pooled_of_key[(size_t)k2];
             if (ib < 0) continue;
             pair_a.push_back(at->alias[ia]); pair_b.push_back(at->alias[ib]); pair_owner.push_back((int32_t)o);
@@ -3729,7 +3716,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
 
     GroupSetup gs;
     rc = group_alloc(ctx, 2 * V, n_groups, &gs);
-    if (rc) return bail(rc, clouds, nullptr);
+    if (rc) return rc;
     // what the device needs of the host's decisions, in ONE copy: pooled clouds, their groups, voxel offsets, the atoms' voxel
     // slices, the bonded pairs and the pairs' (zeroed) touch flags sit in a row in the scratch arena and in one host block
     // (six copies and a fill were seven launches on the stream, 6-8 us apart each: round 4, tools/exp/trace_cloud.sh)
@@ -3750,11 +3737,8 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         upload_bytes = cv.off;      // (the row that is uploaded ends here)
         cv.take(d_comp, 2 * n_pool);
     });
-    if (rc) { arena_put(ctx, gs.in_arena); return bail(rc, clouds, nullptr); }
-    auto fail_dev = [&](hipError_t e, pdbeda_bloblist *u) {
-        arena_put(ctx, aux);
-        return bail(fail(ctx, PDBEDA_ERR_DEVICE, "aggregate cloud: %s", hipGetErrorString(e)), clouds, u);
-    };
+    if (rc) return rc;
+    auto fail_dev = [&](hipError_t e) { return fail(ctx, PDBEDA_ERR_DEVICE, "aggregate cloud: %s", hipGetErrorString(e)); };
     // The union job's volumes are made by the HOST (round 5; three launches -- k_init_bounds, k_list_boxes, k_make_vols -- and a
     // wait for their totals before): the voxels of a pooled cloud lie inside its atom's sphere box [C - R - 1, C + R], so the box
     // around the boxes of a residue's pooled atoms -- around all of them for the domain group -- holds the group's voxels.  A
@@ -3823,7 +3807,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
             e = h2d_row(ctx, in, 1);
         }
     }
-    if (e != hipSuccess) { arena_put(ctx, gs.in_arena); return fail_dev(e, nullptr); }
+    if (e != hipSuccess) return fail_dev(e);
     PoolPaint paint;
     memset(&paint, 0, sizeof paint);
     paint.src_crs = cj->crs_dev; paint.src_off = cj->offsets_dev;
@@ -3834,7 +3818,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     const bool fused_paint = host_sized && 2 * V <= (1ll << 30) * 256 && n_pairs < (1ll << 30);      // (the device-sized path needs the gathered list for its boxes)
     if (!fused_paint) {
         e = flush_pending(ctx, &gs);      // (these two read the aux block)
-        if (e != hipSuccess) { arena_put(ctx, gs.in_arena); return fail_dev(e, nullptr); }
+        if (e != hipSuccess) return fail_dev(e);
         { PROF(ctx, "k_pool_gather"); hipLaunchKernelGGL(k_pool_gather, dim3(grid_for(2 * V, 256)), dim3(256), 0, st, cj->crs_dev, cj->offsets_dev, d_pool_cloud, d_pool_voff,
                                                          d_pool_group, (int)n_pool, V, n_rg, gs.d_crs, gs.d_item_group); }
         if (n_pairs > 0) { PROF(ctx, "k_test_overlap"); hipLaunchKernelGGL(k_test_overlap, dim3((unsigned)n_pairs), dim3(256), 0, st, cj->crs_dev, d_set_off, d_pa, d_pb, d_touch); }
@@ -3845,8 +3829,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     } else {
         rc = group_bounds(m, &gs, 2 * V, n_groups, false);      // (synchronises)
     }
-    if (rc) { arena_put(ctx, gs.in_arena); arena_put(ctx, aux); return bail(rc, clouds, nullptr); }
-    pdbeda_bloblist *uni = nullptr;
+    if (rc) return rc;
     t_pooled = now_s();
     // The union job's results: rows of its blobs, the row of the component that holds each pooled cloud, the pairs' touch flags.  The
     // host orders the rows by the pooled clouds they hold (below), not by key: the job runs UNORDERED (no k_paint_keys, no k_emit) and its
@@ -3863,7 +3846,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     static const bool unordered_on = env_unless_0("PDBEDA_UNORDERED_UNION");      // (A/B switch)
     const bool unordered = unordered_on && fused_paint && copy_kernels() && fin_bytes <= pinned_room(ctx);
     rc = grouped_job(m, gs, 2 * V, n_groups, false, 0.0f, &uni, fused_paint ? &paint : nullptr, unordered);
-    if (rc) { arena_put(ctx, aux); return bail(rc, clouds, nullptr); }
+    if (rc) return rc;
     if (unordered) {
         u_n.resize((size_t)u_cap); u_tot.resize((size_t)u_cap); u_cen.resize(3 * (size_t)u_cap); u_grp.resize((size_t)u_cap);
         Counters u_ctr;
@@ -3883,26 +3866,24 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         const int64_t fin_threads = std::max<int64_t>(std::max<int64_t>(uni->job->job.run_cap, 2 * n_pool), n_pairs);
         { PROF(ctx, "k_union_finish"); hipLaunchKernelGGL(k_union_finish, dim3(grid_for(fin_threads, 256, 1024)), dim3(256), 0, st, uni->job->job, m->geom_dev, fin); }
         e = hipGetLastError();
-        if (e != hipSuccess) return fail_dev(e, uni);
+        if (e != hipSuccess) return fail_dev(e);
         e = ctx_sync(ctx);      // (the one wait of the union job: everything above lands in the host's arrays)
-        arena_put(ctx, aux);
-        if (e != hipSuccess) return bail(fail(ctx, ctx->timed_out ? PDBEDA_ERR_TIMEOUT : PDBEDA_ERR_DEVICE, "aggregate cloud: %s", ctx->timed_out ? ctx->err.c_str() : hipGetErrorString(e)), clouds, uni);
-        if (u_ctr.unit_wait_failed) return bail(fail(ctx, PDBEDA_ERR_DEVICE, "aggregate cloud: a pooled voxel lies outside its group's volume"), clouds, uni);
-        if ((int64_t)u_ctr.n_blobs > u_cap) return bail(fail(ctx, PDBEDA_ERR_STATE, "aggregate cloud: more union components than pooled clouds"), clouds, uni);
+        if (e != hipSuccess) return fail(ctx, ctx->timed_out ? PDBEDA_ERR_TIMEOUT : PDBEDA_ERR_DEVICE, "aggregate cloud: %s", ctx->timed_out ? ctx->err.c_str() : hipGetErrorString(e));
+        if (u_ctr.unit_wait_failed) return fail(ctx, PDBEDA_ERR_DEVICE, "aggregate cloud: a pooled voxel lies outside its group's volume");
+        if ((int64_t)u_ctr.n_blobs > u_cap) return fail(ctx, PDBEDA_ERR_STATE, "aggregate cloud: more union components than pooled clouds");
         const size_t nb_u = u_ctr.n_blobs;
         u_n.resize(nb_u); u_tot.resize(nb_u); u_cen.resize(3 * nb_u); u_grp.resize(nb_u);
     } else {
         { PROF(ctx, "k_pool_component"); hipLaunchKernelGGL(k_pool_component, dim3(grid_for(2 * n_pool, 256)), dim3(256), 0, st, uni->job->job, cj->crs_dev, cj->offsets_dev, d_pool_cloud,
                                                             d_pool_group, (int)n_pool, n_rg, d_comp); }
         e = hipGetLastError();
-        if (e != hipSuccess) return fail_dev(e, uni);
+        if (e != hipSuccess) return fail_dev(e);
         // (the pairs' touch flags and the pooled clouds' components are neighbours in the aux arena: one copy brings both)
         const size_t tail_bytes = (size_t)((char *)(d_comp + 2 * n_pool) - (char *)d_touch);
         std::vector<char> tail((tail_bytes + 3) & ~(size_t)3);
         const D2HItem tail_item = {tail.data(), d_touch, tail.size()};      // (whole words: the pack kernel copies words; the carve's padding covers the round-up)
         rc = list_stats_one_trip(uni, u_cap, u_n, u_tot, u_cen, u_grp, &tail_item);   // (synchronises: comp / touch land with the statistics)
-        arena_put(ctx, aux);
-        if (rc) return bail(rc, clouds, uni);
+        if (rc) return rc;
         if (n_pairs > 0) memcpy(touch.data(), tail.data(), 4 * (size_t)n_pairs);
         memcpy(comp.data(), tail.data() + ((char *)d_comp - (char *)d_touch), 8 * (size_t)n_pool);
     }
@@ -3913,9 +3894,6 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
                 (long long)n, (long long)nb, (long long)n_pool, (long long)V, n_rg, (long long)union_totals[0], (long long)union_totals[1], (long long)nu,
                 1e3 * (t_wait1 - t_call), 1e3 * (t_pooled - t_wait1), 1e3 * (t_marks[0] - t_wait1), 1e3 * (t_marks[1] - t_marks[0]), 1e3 * (t_marks[2] - t_marks[1]),
                 1e3 * (t_marks[3] - t_marks[2]), 1e3 * (t_marks[4] - t_marks[3]), 1e3 * (t_pooled - t_marks[4]), 1e3 * (now_s() - t_pooled));
-    pdbeda_bloblist_free(uni);
-    pdbeda_bloblist_free(clouds);
-    if (rc) { delete res; *out = nullptr; return rc; }
 
     // ---- 4. host: overlap completeness, electrons per union component, emission order, totals (652-731) ----
     for (int64_t q = 0; q < n_pairs; ++q)
@@ -3947,7 +3925,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     for (int kind = 0; kind < 2; ++kind) {
         for (int64_t p = 0; p < n_pool; ++p) {
             const int32_t k = comp[(size_t)(kind * n_pool + p)];
-            if (k < 0 || k >= nu) { delete res; *out = nullptr; return fail(ctx, PDBEDA_ERR_STATE, "aggregate cloud: component rank out of range"); }
+            if (k < 0 || k >= nu) return fail(ctx, PDBEDA_ERR_STATE, "aggregate cloud: component rank out of range");
             members.emplace_back(k, named_by[(size_t)pool_atom[(size_t)p]]);
             if (p < first_pool[(size_t)k]) first_pool[(size_t)k] = p;
         }
@@ -3983,6 +3961,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
         }
     }
     res->totals[0] = num_voxels; res->totals[1] = total_electrons; res->totals[2] = total_density;
+    *out = res.release();
     return PDBEDA_OK;
 }
 
