@@ -182,7 +182,11 @@ int pdbeda_full_blobs_pm(pdbeda_map *map, float cutoff_pos, float cutoff_neg, ui
  * form group g whose sphere voxels are unioned on RAW crs (a one-atom group is the
  * single-coordinate call).  xyz: n_atoms x 3 doubles (float32 atom coordinates promoted
  * exactly); radii: per atom.  Blobs come back sorted by (group, c-major first voxel of the
- * group's bounding box). */
+ * group's bounding box).
+ * A non-finite coordinate or radius: PDBEDA_ERR_ARGUMENT, the message names the atom, before anything is staged or launched; the
+ * context stays usable.  A finite coordinate or radius beyond what the host may turn into grid indices (an index or a box
+ * half-width of 2^29 grid steps or more, a negative radius) is not refused: the device sizes that batch itself, behind one more
+ * wait, as it sizes voxel lists. */
 int pdbeda_sphere_blobs(pdbeda_map *map, const double *xyz, const float *radii, int64_t n_atoms,
                         const int64_t *group_offsets, int64_t n_groups, float density_cutoff,
                         pdbeda_bloblist **out);
@@ -343,7 +347,9 @@ int pdbeda_peaklist_free(pdbeda_peaklist *pl);
  * deduplicated on raw crs): pos = sum of density > cutoff, neg = sum of density < -cutoff
  * (strict, cutils.pyx:245), n_region = |sphere union| with no density filter
  * (densityAnalysis.py:1198), valid = utils.testValidXyzList (cutils.pyx:273-313).
- * Any output pointer may be NULL. */
+ * Any output pointer may be NULL.
+ * A non-finite coordinate or radius: PDBEDA_ERR_ARGUMENT, the message names the atom, before anything is staged or launched; a
+ * finite one beyond what the host may turn into grid indices leaves the sizing of the batch to the device (pdbeda_sphere_blobs). */
 int pdbeda_region_sums(pdbeda_map *map, const double *xyz, const float *radii, int64_t n_atoms,
                        const int64_t *group_offsets, int64_t n_groups, float cutoff,
                        double *pos, double *neg, int64_t *n_region, uint8_t *valid);
@@ -369,7 +375,8 @@ int pdbeda_region_sums(pdbeda_map *map, const double *xyz, const float *radii, i
  * folded as integers: bit-identical from run to run, within quantum / 2 per voxel of the exact sum; an empty shell is exactly 0.  Atoms do not see
  * each other: bonded atoms share voxels once radius exceeds half a bond length -- a profile is per atom, not a partition.
  * n_atoms == 0 succeeds and touches nothing.  PDBEDA_ERR_ARGUMENT before any launch: n_shells outside [1, PDBEDA_MAX_SHELLS],
- * a radius that is not finite or <= 0, a NaN cutoff, a non-finite coordinate, a box of 2^31 voxels or more.  Synchronous. */
+ * a radius that is not finite or <= 0, a NaN cutoff, a non-finite coordinate, a box of 2^31 voxels or more, a coordinate or a
+ * radius of 2^29 grid steps or more (the host makes the boxes, and casts nothing beyond that).  Synchronous. */
 #define PDBEDA_MAX_SHELLS 64
 int pdbeda_radial_profiles(pdbeda_map *map, const double *xyz, int64_t n_atoms, float radius, int32_t n_shells, float cutoff,
                            int64_t *n, double *sum, int64_t *n_sig, double *sum_sig, uint8_t *valid); /* any output may be NULL */
@@ -423,7 +430,9 @@ int pdbeda_map_partition(pdbeda_map *map, const double *xyz, int64_t n_atoms, fl
  * equally distant clouds the first in list order is the best one; a residue without a pooled cloud has no row and leaves no gap
  * in the others' ordinals, which are the caller's.  n == 0, or no pooled cloud at all, succeeds with empty tables, zero totals,
  * every owner in state 0 and a NaN cut-off when no atom has a cloud.  PDBEDA_ERR_ARGUMENT for an alias, key, owner key or bonded
- * key out of range and for decreasing residue ordinals; a failing call leaves the context usable.
+ * key out of range, for decreasing residue ordinals and for a non-finite coordinate or radius (the message names the atom; nothing
+ * was staged or launched); a failing call leaves the context usable.  A finite coordinate or radius beyond what the host may turn
+ * into grid indices leaves the sizing of both jobs to the device (pdbeda_sphere_blobs).
  *
  * The caller flattens what the reference reads from the structure, in the reference's iteration order
  * (residues with id[0] == ' ', their child atoms whose residue_atom name has an atom type and whose occupancy != 0): */

@@ -104,25 +104,35 @@ __host__ __device__ inline void crs2xyz_frac(const Geom &g, const double crs[3],
 }
 
 // DensityHeader.xyz2crsCoord (ccp4.py:288-302); Python round() = half-to-even = rint.
-__host__ __device__ inline void xyz2crs(const Geom &g, const double xyz[3], int32_t crs[3]) {
+// `ok` sees each grid position as a double BEFORE it is cast, and false ends the conversion there: how host code keeps a NaN or 1e300 away from a cast
+// that is undefined on the host (pdbeda_spherebox.h; the device's conversion saturates).  I: int32_t, or int64_t to see an index before it is narrowed.
+template <typename I, typename Ok>
+__host__ __device__ inline bool xyz2crs_if(const Geom &g, const double xyz[3], I crs[3], Ok ok) {
     int64_t grid[3];
     if (g.orthogonal) {
         for (int i = 0; i < 3; ++i) {
             double d = xyz[i] - g.origin[i];
-            grid[i] = (int64_t)rint(d / g.grid_len[i]);
+            double q = d / g.grid_len[i];
+            if (!ok(q)) return false;
+            grid[i] = (int64_t)rint(q);
         }
     } else {
         double f[3];
         matvec3(g.deortho, xyz, f);
         for (int i = 0; i < 3; ++i) {
             double p = f[i] * (double)g.xyz_interval[i];
+            if (!ok(p)) return false;
             grid[i] = (int64_t)rint(p) - sel3(g.crs_start, g.map2xyz[i]);
         }
     }
     for (int i = 0; i < 3; ++i) {
         int a = g.map2crs[i];
-        crs[i] = (int32_t)(a == 0 ? grid[0] : (a == 1 ? grid[1] : grid[2]));
+        crs[i] = (I)(a == 0 ? grid[0] : (a == 1 ? grid[1] : grid[2]));
     }
+    return true;
+}
+__host__ __device__ inline void xyz2crs(const Geom &g, const double xyz[3], int32_t crs[3]) {
+    (void)xyz2crs_if(g, xyz, crs, [](double) { return true; });
 }
 
 // ---- 64-bit word helpers (a mask word = 64 consecutive voxels along c) -------------

@@ -2492,6 +2492,7 @@ struct GroupSetup {
     int64_t total_words = 0, total_keys = 0;
     bool host_totals = false;   // the totals are the host's (per-atom spheres): nobody waited for the device's -- k_make_vols checks them
     std::vector<AtomBox> host_boxes;   // per-atom spheres: the boxes the host made (kept on the list: aggregateCloud's union volumes are boxes around them)
+    int64_t largest_box = 0;    // a batch the host planned: voxels of its largest volume
     bool atom_engine = false;   // per-atom spheres whose boxes the host made, every box one mask word a row and at most ATOM_WORDS rows: ONE launch labels the batch (k_atom_engine)
     // staged inputs whose copy into the device scratch has not been launched yet: grouped_job's k_job_init does it (one launch less), flush_pending for everybody else
     const char *pend_src = nullptr;
@@ -2568,152 +2569,83 @@ static int group_bounds(pdbeda_map *m, GroupSetup *gs, int64_t n_items, int64_t 
     return group_sized(ctx, gs, ctr.total_words, ctr.total_keys, false);
 }
 
-// The host's twin of k_init_bounds + k_atom_boxes + k_make_vols, built on the same statements (sphere_half_widths, atom_box, vol_from_bounds:
-// pdbeda_kernels.h): every atom's box, the box around the boxes of each group's atoms, the groups' volume descriptors and the batch's totals.
-// item_group == nullptr: a group per atom -- atom a's volume is its box.  *small_boxes: every volume is one mask word a row and at most ATOM_WORDS rows.
-// false: a volume, or the totals, beyond what a job addresses (the caller leaves the batch to the device, which sizes and reports).
-static bool host_sphere_volumes(const Geom &geom, const double *xyz, const float *radii, const int32_t *item_group, int64_t n_items, int64_t n_groups,
-                                AtomBox *boxes, VolDesc *vols, int64_t totals[2], bool *small_boxes) {
-    int64_t words = 0, keys = 0;
-    bool fits = true, small = true;
-    auto add_vol = [&](const int32_t *lo, const int32_t *hi, int64_t g) {
-        VolDesc vd;
-        int64_t w = 0, k = 0;
-        fits = vol_from_bounds(lo, hi, (int32_t)g, words, keys, &vd, &w, &k) && fits;
-        vols[g] = vd;
-        small = small && vd.row_words <= 1 && (int64_t)vd.dim[1] * vd.dim[2] <= ATOM_WORDS;
-        words += w;
-        keys += k;
-        fits = fits && words < (1ll << 40) && keys < (1ll << 46);
-    };
-    std::vector<int32_t> glo, ghi;
-    if (item_group) { glo.assign(3 * (size_t)n_groups, INT32_MAX); ghi.assign(3 * (size_t)n_groups, INT32_MIN); }
-    float cached_rad = NAN;      // (a handful of distinct radii, one per atom type: the half-widths are made once per run of equal radii)
-    int32_t R[3] = {0, 0, 0};
-    for (int64_t a = 0; a < n_items; ++a) {
-        if (!(radii[a] == cached_rad)) {
-            sphere_half_widths(geom, (double)radii[a], R);
-            cached_rad = radii[a];
-        }
-        int32_t C[3];
-        xyz2crs(geom, xyz + 3 * a, C);
-        AtomBox bx;
-        const bool empty = !atom_box(C, R, &bx);
-        boxes[a] = bx;
-        if (!item_group) {
-            add_vol(bx.lo, bx.hi, a);
-        } else if (!empty) {
-            const size_t g = (size_t)item_group[(size_t)a];
-            for (int k = 0; k < 3; ++k) { glo[3 * g + k] = std::min(glo[3 * g + k], bx.lo[k]); ghi[3 * g + k] = std::max(ghi[3 * g + k], bx.hi[k]); }
-        }
-    }
-    for (int64_t g = 0; item_group && g < n_groups; ++g) add_vol(&glo[3 * (size_t)g], &ghi[3 * (size_t)g], g);
-    totals[0] = words;
-    totals[1] = keys;
-    *small_boxes = small;
-    return fits;
-}
-
-// Upload atoms (or explicit voxels), then group_bounds.
+// A sphere / list batch onto the device, sized.  It validates, chooses ONE of four plans, and ships that plan:
+//   the row, left to the job    inputs, boxes, volumes and counters as they sit at the head of the scratch arena (group_alloc), made by the host
+//                               (plan_spheres: pdbeda_spherebox.h) in the pinned block; the job's first launch copies the row (pend_*)
+//   the row, copied now         the same row without copy kernels, whose launches cannot read host memory
+//   inputs only                 coordinates, radii and groups; the device makes boxes and volumes, and nobody waits for its totals: k_make_vols holds
+//                               them against the host's, which follow from the radii alone (plan_radii_totals)
+//   the device's own sizing     k_init_bounds, k_atom_boxes / k_list_boxes, k_make_vols and the WAIT for their totals: voxel lists, what the range test
+//                               or the one limit declines, what finds no room in the block
+// Per-atom spheres (a group per atom: the clouds of aggregateCloud, the per-atom region tables) and grouped spheres (a residue's atoms: the residue
+// region tables, RSCC / RSR) take the row -- three launches, the copy of the totals and one of an entry's waits less per call, and a launch costs
+// several times its 5 us when other processes' uploads hold the link.  PDBEDA_HOST_BOXES=0: the device makes boxes and volumes (A/B, and what the test of
+// the paths' equality runs against).  The inputs go through the pinned block, so nothing here needs the caller's arrays after the call returns.
 static int group_setup(pdbeda_map *m, const double *xyz, const float *radii, const int32_t *crs, int64_t n_items,
                        const int64_t *group_offsets, int64_t n_groups, GroupSetup *gs) {
+    static const bool host_boxes_on = env_unless_0("PDBEDA_HOST_BOXES");
+    static const bool atom_engine_on = env_unless_0("PDBEDA_ATOM_ENGINE");   // (A/B switch)
     pdbeda_ctx *ctx = m->ctx;
+    const bool spheres = xyz != nullptr;
+    // ---- validate ----
     std::vector<int32_t> item_group;
     if (expand_groups(group_offsets, n_groups, n_items, item_group)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "bad group_offsets");
+    for (int64_t a = 0; spheres && a < n_items; ++a) {
+        if (!std::isfinite(xyz[3 * a]) || !std::isfinite(xyz[3 * a + 1]) || !std::isfinite(xyz[3 * a + 2]) || !std::isfinite(radii[a]))
+            return fail(ctx, PDBEDA_ERR_ARGUMENT, "sphere batch: atom %lld has a non-finite coordinate or radius", (long long)a);
+    }
     int rc = group_alloc(ctx, n_items, n_groups, gs);
     if (rc) return rc;
-    // (a staged block mirrors the head of the scratch arena: `staged` is the block's twin of a device pointer)
-    auto staged = [&](char *stage, const void *dev) { return stage + ((const char *)dev - gs->in_arena.base); };
-    auto stage_inputs = [&](char *stage) {      // coordinates, radii and groups at their arena offsets
+    bool per_atom = spheres && n_items > 0 && n_groups == n_items;
+    for (int64_t g = 0; g <= n_groups && per_atom; ++g) per_atom = group_offsets[g] == g;
+    const bool grouped = spheres && n_items > 0 && n_groups > 0 && n_groups < n_items;
+    // (a staged block mirrors the head of the scratch arena, where group_alloc carves the inputs first: `staged` is the block's twin of a device pointer)
+    char *const base = gs->in_arena.base;
+    const size_t inputs = (size_t)((char *)(gs->d_item_group + n_items) - base), row = (size_t)((char *)(gs->d_ctr + 1) - base);
+    auto staged = [&](char *stage, const void *dev) { return stage + ((const char *)dev - base); };
+    // ---- decide: each plan is sized once, by the planner ----
+    enum { ROW_TO_JOB, ROW_NOW, INPUTS_ONLY, DEVICE_SIZED } ship = DEVICE_SIZED;
+    char *stage = nullptr;
+    SpherePlan plan;
+    const bool row_allowed = (per_atom || (grouped && copy_kernels())) && host_boxes_on && !ctx->debug_shrink_totals && row <= ((size_t)1 << 20);
+    if (row_allowed && (stage = pinned_take(ctx, row)) != nullptr) {      // (boxes and volumes straight into the staged row)
+        plan = plan_spheres(m->geom, xyz, radii, per_atom ? nullptr : item_group.data(), n_items, n_groups, reinterpret_cast<AtomBox *>(staged(stage, gs->d_boxes)),
+                            reinterpret_cast<VolDesc *>(staged(stage, gs->d_vols)), ATOM_WORDS);
+        if (plan.fits) ship = copy_kernels() ? ROW_TO_JOB : ROW_NOW;
+        else { pinned_untake(ctx, stage); stage = nullptr; }
+    }
+    if (ship == DEVICE_SIZED && per_atom && plan.plannable) {      // (a coordinate the host may not cast: the device's boxes are its own business, and so are its totals)
+        plan = plan_radii_totals(m->geom, radii, n_items, ATOM_WORDS);
+        if (plan.fits && (stage = pinned_take(ctx, inputs)) != nullptr) ship = INPUTS_ONLY;
+    }
+    // ---- ship ----
+    if (ship != DEVICE_SIZED) {      // coordinates, radii and groups at their arena offsets
         memcpy(staged(stage, gs->d_xyz), xyz, 24 * (size_t)n_items);
         memcpy(staged(stage, gs->d_radii), radii, 4 * (size_t)n_items);
         memcpy(staged(stage, gs->d_item_group), item_group.data(), 4 * (size_t)n_items);
-    };
-    // Per-atom spheres (a group per atom: the clouds of aggregateCloud, the per-atom region tables): an atom's box is
-    // [C - R - 1, C + R] with R = xyz2crs(origin + radius) -- its SIZE follows from the radius alone, so the host knows the
-    // job's mask words and keys without asking the device (the round trip for the totals was one of an entry's host waits).
-    // The inputs go through the pinned staging buffer, so nothing here needs the caller's arrays after the call returns.
-    // Round 6: GROUPED spheres (a residue's atoms: the residue region tables, RSCC / RSR) get their boxes and volumes from the host too -- a group's
-    // volume is the box around its atoms' boxes, which is what k_atom_boxes' atomic min / max and k_make_vols make of them on the device (the same
-    // xyz2crs, the same int32 arithmetic): k_init_bounds, k_atom_boxes, k_make_vols, the copy of their totals and the WAIT for it go (four launches and
-    // one of an entry's waits per grouped call).  PDBEDA_HOST_BOXES=0: the device makes them, as for the per-atom batches.
-    static const bool host_boxes = env_unless_0("PDBEDA_HOST_BOXES");
-    // The row the host makes: inputs, boxes, volumes and counters, as they sit at the head of the scratch arena (group_alloc), staged in the pinned
-    // block.  nullptr, and nothing taken: not allowed, no room, or volumes that do not fit.  made[2]: the batch's mask words and keys.
-    const size_t row = (size_t)((char *)(gs->d_ctr + 1) - gs->in_arena.base);
-    auto host_row = [&](const int32_t *groups, int64_t made[2], bool *small_boxes) -> char * {
-        if (!host_boxes || ctx->debug_shrink_totals || (char *)gs->d_xyz != gs->in_arena.base || row > ((size_t)1 << 20)) return nullptr;
-        char *stage = pinned_take(ctx, row);
-        if (!stage) return nullptr;
-        stage_inputs(stage);
-        if (!host_sphere_volumes(m->geom, xyz, radii, groups, n_items, n_groups, reinterpret_cast<AtomBox *>(staged(stage, gs->d_boxes)),
-                                 reinterpret_cast<VolDesc *>(staged(stage, gs->d_vols)), made, small_boxes)) { pinned_untake(ctx, stage); return nullptr; }
+    }
+    if (ship == ROW_TO_JOB || ship == ROW_NOW) {
         Counters *ctr0 = reinterpret_cast<Counters *>(staged(stage, gs->d_ctr));
         memset(ctr0, 0, sizeof *ctr0);
-        ctr0->total_words = made[0];
-        ctr0->total_keys = made[1];
-        return stage;
-    };
-    auto leave_to_job = [&](char *stage) { gs->pend_src = stage; gs->pend_dst = gs->in_arena.base; gs->pend_bytes = (row + 15) & ~(size_t)15; };   // (copied by the job's first launch; whole 16-byte units: the stage and the carve are padded)
-    int64_t made[2] = {0, 0};
-    bool small_boxes = false;
-    if (xyz && n_items > 0 && n_groups > 0 && n_groups < n_items) {
-        bool sane = true;
-        for (int64_t a = 0; a < n_items && sane; ++a) sane = radii[a] >= 0.0f && std::isfinite(radii[a]);
-        if (char *stage = sane && copy_kernels() ? host_row(item_group.data(), made, &small_boxes) : nullptr) {
-            leave_to_job(stage);
-            return group_sized(ctx, gs, made[0], made[1], true);
-        }
-    }
-    if (xyz && n_items > 0 && n_groups == n_items) {
-        bool per_atom = true;
-        for (int64_t g = 0; g <= n_groups && per_atom; ++g) per_atom = group_offsets[g] == g;
-        int64_t totals[2] = {0, 0};
-        float last_rad = NAN;
-        int64_t last_words = 0, last_keys = 0;
-        for (int64_t a = 0; a < n_items && per_atom; ++a) {
-            const float rad = radii[a];
-            if (!(rad >= 0.0f) || !std::isfinite(rad)) { per_atom = false; break; }
-            if (!(rad == last_rad)) {   // (a handful of distinct radii: one per atom type)
-                int32_t R[3];
-                sphere_half_widths(m->geom, (double)rad, R);
-                int64_t dim[3];
-                bool empty = false;
-                for (int k = 0; k < 3; ++k) { dim[k] = 2 * (int64_t)R[k] + 2; empty = empty || dim[k] <= 0; }
-                last_words = empty ? 0 : (dim[0] + 63) / 64 * dim[1] * dim[2];
-                last_keys = empty ? 0 : dim[0] * dim[1] * dim[2];
-                last_rad = rad;
-            }
-            totals[0] += last_words;
-            totals[1] += last_keys;
-            if (totals[0] >= (1ll << 40) || totals[1] >= (1ll << 46)) per_atom = false;   // (absurd: let the waiting path report it)
-        }
-        // Round 5: the host makes the boxes and the volume descriptors too (xyz2crs is one function for host and device: the same IEEE operations in
-        // the same order) -- k_init_bounds, k_atom_boxes and k_make_vols were three launches in front of every per-atom batch (the clouds of
-        // aggregateCloud, the region tables), and a launch costs several times its 5 us when other processes' uploads hold the link.
-        // PDBEDA_HOST_BOXES=0: the device makes them (A/B, and what the test of the two paths' equality runs against).
-        char *stage = per_atom ? host_row(nullptr, made, &small_boxes) : nullptr;
-        if (stage && !(made[0] == totals[0] && made[1] == totals[1])) { pinned_untake(ctx, stage); stage = nullptr; }   // (they are equal: both follow from the radii; a mismatch takes the device's path below)
-        if (stage) {
+        ctr0->total_words = plan.words;
+        ctr0->total_keys = plan.keys;
+        gs->largest_box = plan.largest;
+        if (per_atom) {
             const AtomBox *boxes = reinterpret_cast<const AtomBox *>(staged(stage, gs->d_boxes));
             gs->host_boxes.assign(boxes, boxes + n_items);
-            if (copy_kernels()) leave_to_job(stage);
-            else HIP_TRY(ctx, stage_copy(ctx, stage, gs->in_arena.base, row, true));
-            static const bool atom_engine_on = env_unless_0("PDBEDA_ATOM_ENGINE");   // (A/B switch)
-            gs->atom_engine = small_boxes && atom_engine_on && n_items < (1ll << 31);
-            return group_sized(ctx, gs, made[0], made[1], true);
+            gs->atom_engine = plan.small_boxes && atom_engine_on && n_items < (1ll << 31);
         }
-        if (ctx->debug_shrink_totals) { totals[0] /= 2; totals[1] /= 2; }
-        // (coordinates, radii and groups sit in a row at the head of the scratch arena: one staged block, one copy)
-        const size_t block = (size_t)((char *)(gs->d_item_group + n_items) - gs->in_arena.base);
-        if (char *stage = per_atom && (char *)gs->d_xyz == gs->in_arena.base ? pinned_take(ctx, block) : nullptr) {
-            stage_inputs(stage);
-            HIP_TRY(ctx, stage_copy(ctx, stage, gs->in_arena.base, block, true));
-            return group_bounds(m, gs, n_items, n_groups, true, totals);
-        }
+        if (ship == ROW_NOW) HIP_TRY(ctx, stage_copy(ctx, stage, base, row, true));
+        else { gs->pend_src = stage; gs->pend_dst = base; gs->pend_bytes = (row + 15) & ~(size_t)15; }   // (copied by the job's first launch; whole 16-byte units: the stage and the carve are padded)
+        return group_sized(ctx, gs, plan.words, plan.keys, true);
+    }
+    if (ship == INPUTS_ONLY) {
+        const int64_t totals[2] = {plan.words / (ctx->debug_shrink_totals ? 2 : 1), plan.keys / (ctx->debug_shrink_totals ? 2 : 1)};
+        HIP_TRY(ctx, stage_copy(ctx, stage, base, inputs, true));      // (a row at the head of the scratch arena: one staged block, one copy)
+        return group_bounds(m, gs, n_items, n_groups, true, totals);
     }
     if (n_items > 0) {
-        if (xyz) {
+        if (spheres) {
             const H2DItem in[3] = {{gs->d_xyz, xyz, (size_t)(24 * n_items)}, {gs->d_radii, radii, (size_t)(4 * n_items)}, {gs->d_item_group, item_group.data(), (size_t)(4 * n_items)}};
             HIP_TRY(ctx, h2d_row(ctx, in, 3));       // (a row at the head of the scratch arena: one copy)
         } else {
@@ -2721,12 +2653,18 @@ static int group_setup(pdbeda_map *m, const double *xyz, const float *radii, con
             HIP_TRY(ctx, h2d_one(ctx, gs->d_item_group, item_group.data(), (size_t)(4 * n_items)));
         }
     }
-    return group_bounds(m, gs, n_items, n_groups, xyz != nullptr);   // (synchronises: item_group may go)
+    return group_bounds(m, gs, n_items, n_groups, spheres);   // (synchronises: item_group may go)
 }
 
 // Paint the group volumes and enqueue the labelling engine on them; the input scratch is recycled in stream order.
 static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n_groups, bool spheres, float cutoff, pdbeda_bloblist **out, const PoolPaint *pool = nullptr,
                        bool unordered = false) {
+    // (PDBEDA_DEBUG_ATOM_CAPS="runs,comps": tests shrink the LDS tables' use so that small inputs run k_atom_engine's global-table path)
+    static const std::pair<int, int> atom_caps = [] {
+        int r = ATOM_RUNS, c = ATOM_COMPS;
+        if (const char *e = getenv("PDBEDA_DEBUG_ATOM_CAPS")) { int x = 0, y = 0; if (sscanf(e, "%d,%d", &x, &y) == 2) { r = std::max(0, std::min(x, ATOM_RUNS)); c = std::max(0, std::min(y, ATOM_COMPS)); } }
+        return std::make_pair(r, c);
+    }();
     pdbeda_ctx *ctx = m->ctx;
     const int64_t max_runs = gs.total_keys / 2 + gs.total_words + 1;
     if (gs.pend_bytes && m->fix_mul == 0.0 && !m->fix_refused) {
@@ -2762,13 +2700,7 @@ static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n
     const bool fused_atoms = spheres && gs.atom_engine && n_items > 0 && n_items == n_groups;
     if (e == hipSuccess && fused_atoms) {   // a per-atom batch of small boxes: paint, run index, unions, resolve and key painting in one launch
         PROF(ctx, "k_atom_engine");
-        // (PDBEDA_DEBUG_ATOM_CAPS="runs,comps": tests shrink the LDS tables' use so that small inputs run the kernel's global-table path)
-        static const std::pair<int, int> caps = [] {
-            int r = ATOM_RUNS, c = ATOM_COMPS;
-            if (const char *e = getenv("PDBEDA_DEBUG_ATOM_CAPS")) { int x = 0, y = 0; if (sscanf(e, "%d,%d", &x, &y) == 2) { r = std::max(0, std::min(x, ATOM_RUNS)); c = std::max(0, std::min(y, ATOM_COMPS)); } }
-            return std::make_pair(r, c);
-        }();
-        hipLaunchKernelGGL(k_atom_engine, dim3((unsigned)n_items), dim3(256), 0, st, job, m->geom_dev, m->dens, gs.d_xyz, gs.d_radii, gs.d_boxes, cutoff, caps.first, caps.second);
+        hipLaunchKernelGGL(k_atom_engine, dim3((unsigned)n_items), dim3(256), 0, st, job, m->geom_dev, m->dens, gs.d_xyz, gs.d_radii, gs.d_boxes, cutoff, atom_caps.first, atom_caps.second);
         e = hipGetLastError();
     } else if (e == hipSuccess && n_items > 0) {
         if (spheres)
@@ -2817,6 +2749,7 @@ extern "C" int pdbeda_list_blobs(pdbeda_map *m, const int32_t *crs, int64_t n, c
 extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float *radii, int64_t n_atoms, const int64_t *group_offsets,
                                   int64_t n_groups, float cutoff, double *pos, double *neg, int64_t *n_region, uint8_t *valid) {
     if (!m || n_atoms < 0 || n_groups < 0 || !group_offsets || (n_atoms > 0 && (!xyz || !radii))) return PDBEDA_ERR_ARGUMENT;
+    static const bool atom_region_on = env_unless_0("PDBEDA_ATOM_REGION");      // (A/B switch)
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n_groups == 0) return PDBEDA_OK;
@@ -2832,10 +2765,10 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
         }
         return PDBEDA_OK;
     };
-    {   // a group per atom whose inputs the host staged (coordinates, radii, host-made volumes in the pinned block): ONE launch, no mask (k_atom_region)
-        static const bool atom_region_on = env_unless_0("PDBEDA_ATOM_REGION");      // (A/B switch)
+    {   // a group per atom whose inputs the host staged (coordinates, radii, host-made volumes in the pinned block): ONE launch, no mask (k_atom_region).
+        // The kernel counts a box's voxels in 32 bits and does not ask for small boxes, so the gate does: the plan's largest box has fewer than 2^31.
         const size_t out_bytes = 3 * pinned_span(8 * (size_t)n_groups) + pinned_span(4 * (size_t)n_groups);
-        if (atom_region_on && n_groups == n_atoms && gs.pend_bytes && !gs.host_boxes.empty() && copy_kernels() && out_bytes <= pinned_room(ctx)) {
+        if (atom_region_on && n_groups == n_atoms && gs.pend_bytes && !gs.host_boxes.empty() && gs.largest_box < (1ll << 31) && copy_kernels() && out_bytes <= pinned_room(ctx)) {
             // (n_groups > 0: no take is empty.  As before a failed launch below keeps the takes until the next wait and, through fail(), delivers nothing)
             double *o_pos = reinterpret_cast<double *>(pinned_take(ctx, 8 * (size_t)n_groups, pos));
             double *o_neg = reinterpret_cast<double *>(pinned_take(ctx, 8 * (size_t)n_groups, neg));
@@ -2922,19 +2855,17 @@ extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t 
     std::vector<AtomBox> boxes((size_t)n_atoms);
     int64_t largest = 0;
     {
+        // (the planner's range test and box function.  There is no device sizing to fall back on here: what the host may not cast is refused)
         int32_t R[3];
-        sphere_half_widths(m->geom, (double)radius, R);
+        if (!plan_half_widths(m->geom, radius, R)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: the radius is 2^29 grid steps or more");
         for (int64_t a = 0; a < n_atoms; ++a) {
             const double *p = xyz + 3 * a;
             if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: atom %lld has a non-finite coordinate", (long long)a);
-            int32_t C[3];
-            xyz2crs(m->geom, p, C);
-            int64_t vox = atom_box(C, R, &boxes[(size_t)a]) ? 1 : 0;
-            for (int k = 0; k < 3 && vox; ++k) {
-                vox *= (int64_t)boxes[(size_t)a].hi[k] - (int64_t)boxes[(size_t)a].lo[k] + 1;      // (each width < 2^32: checked after every factor)
-                if (vox >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: the sphere box of atom %lld has 2^31 voxels or more", (long long)a);
-            }
-            largest = std::max(largest, vox);
+            if (!plan_atom_box(m->geom, p, R, &boxes[(size_t)a])) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: atom %lld lies 2^29 grid steps or more from the map's origin", (long long)a);
+            SpherePlan one;      // (the box as a plan of its own: what does not fit the planner's limit has 2^32 voxels or more -- every width of a box is even)
+            one.push(boxes[(size_t)a].lo, boxes[(size_t)a].hi, 0);
+            if (!one.fits || one.largest >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "radial profiles: the sphere box of atom %lld has 2^31 voxels or more", (long long)a);
+            largest = std::max(largest, one.largest);
         }
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3744,46 +3675,28 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     // around the boxes of a residue's pooled atoms -- around all of them for the domain group -- holds the group's voxels.  A
     // volume a little larger than its voxels' own bounds changes nothing in the result: keys are lexicographic in (c, r, s)
     // whatever the box, so the blobs come out in the same order with the same sums.
-    int64_t union_totals[2] = {0, 0};
     std::vector<VolDesc> union_vols((size_t)n_groups);
+    SpherePlan union_plan{union_vols.data(), ATOM_WORDS};
     {
-        std::vector<int64_t> lo(3 * (size_t)n_groups, INT64_MAX), hi(3 * (size_t)n_groups, INT64_MIN);
-        const bool have_boxes = (int64_t)cj->host_boxes.size() == n;      // (the sphere job's own boxes, made by the host with the same statements: two xyz2crs per pooled cloud were 0.06 ms here)
+        GroupBounds bounds(n_groups);
+        const bool have_boxes = (int64_t)cj->host_boxes.size() == n;      // (the sphere job's own boxes, made by the planner: two xyz2crs per pooled cloud were 0.06 ms here)
         int64_t last_a = -1;
-        bool cur_empty = false;
         AtomBox bx = {{0, 0, 0}, {-1, -1, -1}};
         for (int64_t p = 0; p < n_pool; ++p) {
             const int64_t a = at->alias[pool_atom[(size_t)p]];          // (the clouds are those of the coordinate's last atom: its coordinate, its radius)
             if (a != last_a) {
-                if (have_boxes) {
-                    bx = cj->host_boxes[(size_t)a];
-                } else {
-                    int32_t C[3], R[3];
-                    xyz2crs(m->geom, at->xyz + 3 * a, C);
-                    sphere_half_widths(m->geom, (double)at->radius[a], R);
-                    (void)atom_box(C, R, &bx);
-                }
-                cur_empty = bx.hi[0] < bx.lo[0];      // (an empty box holds no voxel: it has no cloud, it is not pooled -- unreachable)
+                int32_t R[3];
+                if (have_boxes) bx = cj->host_boxes[(size_t)a];
+                else if (!plan_half_widths(m->geom, at->radius[a], R) || !plan_atom_box(m->geom, at->xyz + 3 * a, R, &bx)) union_plan.plannable = union_plan.fits = false;
                 last_a = a;
             }
-            if (cur_empty) continue;
-            for (int g : {(int)pool_group[(size_t)p], n_rg})
-                for (int k = 0; k < 3; ++k) {
-                    lo[3 * (size_t)g + k] = std::min<int64_t>(lo[3 * (size_t)g + k], bx.lo[k]);
-                    hi[3 * (size_t)g + k] = std::max<int64_t>(hi[3 * (size_t)g + k], bx.hi[k]);
-                }
+            bounds.add(bx, pool_group[(size_t)p]);      // (an empty box holds no voxel: it has no cloud, it is not pooled -- unreachable, and ignored)
+            bounds.add(bx, n_rg);
         }
-        for (int g = 0; g < n_groups; ++g) {
-            int64_t words = 0, keys = 0;
-            bool fits = vol_from_bounds(&lo[3 * (size_t)g], &hi[3 * (size_t)g], g, union_totals[0], union_totals[1], &union_vols[(size_t)g], &words, &keys);
-            for (int k = 0; k < 3; ++k) fits = fits && lo[3 * (size_t)g + k] > INT32_MIN && hi[3 * (size_t)g + k] < INT32_MAX;      // (an empty group's sentinels pass)
-            if (!fits) { union_totals[0] = INT64_MAX / 2; break; }
-            union_totals[0] += words;
-            union_totals[1] += keys;
-        }
+        bounds.finish(union_plan);
     }
     t_marks[4] = now_s();
-    const bool host_sized = !ctx->debug_shrink_totals && union_totals[0] < (1ll << 31) && union_totals[1] < (1ll << 40);   // (absurd boxes, or the debug hook that wants the device's own sizing: the waiting path sizes and reports)
+    const bool host_sized = union_plan.fits && !ctx->debug_shrink_totals;   // (what the planner declines, or the debug hook that wants the device's own sizing: the waiting path sizes and reports)
     hipError_t e;
     std::vector<char> block(upload_bytes, 0);      // (staged: the copy below reads a pinned block or, too large for that, has finished reading when it returns)
     {
@@ -3825,7 +3738,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     }
     if (host_sized) {
         gs.d_vols = d_union_vols;          // (in the aux block, which outlives the job's enqueue)
-        rc = group_sized(ctx, &gs, union_totals[0], union_totals[1], true);
+        rc = group_sized(ctx, &gs, union_plan.words, union_plan.keys, true);
     } else {
         rc = group_bounds(m, &gs, 2 * V, n_groups, false);      // (synchronises)
     }
@@ -3891,7 +3804,7 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     if (cloud_trace)
         fprintf(stderr, "aggregate_cloud: %lld atoms, %lld clouds, %lld pooled clouds (%lld voxels), %d residue groups + the domain group: %lld mask words, %lld keys, %lld union blobs; "
                         "ms: clouds enqueued + waited %.3f, host pooling %.3f (voxel lists enqueued %.3f, distances + cut-off %.3f, pool loop %.3f, groups + pairs %.3f, arenas + volumes %.3f, block + staging %.3f), union job enqueued + waited %.3f\n",
-                (long long)n, (long long)nb, (long long)n_pool, (long long)V, n_rg, (long long)union_totals[0], (long long)union_totals[1], (long long)nu,
+                (long long)n, (long long)nb, (long long)n_pool, (long long)V, n_rg, (long long)union_plan.words, (long long)union_plan.keys, (long long)nu,
                 1e3 * (t_wait1 - t_call), 1e3 * (t_pooled - t_wait1), 1e3 * (t_marks[0] - t_wait1), 1e3 * (t_marks[1] - t_marks[0]), 1e3 * (t_marks[2] - t_marks[1]),
                 1e3 * (t_marks[3] - t_marks[2]), 1e3 * (t_marks[4] - t_marks[3]), 1e3 * (t_pooled - t_marks[4]), 1e3 * (now_s() - t_pooled));
 

@@ -12,18 +12,9 @@
 // runs of the 4 "earlier" neighbour rows + the previous word (26-connectivity,
 // non-periodic, cutils.pyx:44-70).
 #pragma once
-#include "pdbeda_device.h"
+#include "pdbeda_spherebox.h"
 
 namespace pdbeda {
-
-struct VolDesc {
-    int32_t dim[3];     // voxels along c, r, s
-    int32_t org[3];     // raw crs of local voxel (0,0,0)
-    int32_t row_words;  // ceil(dim[0] / 64)
-    int32_t group;      // caller-visible group id (plane for whole-map jobs)
-    int64_t word_base;  // first mask word of this volume
-    int64_t key_base;   // first key bit of this volume (key = (c*dim[1] + r)*dim[2] + s)
-};
 
 // ---- Order-independent sums --------------------------------------------------------------------------------------
 // sum(rho) and the first moments sum(rho * c / r / s) of a blob are folded from thousands of partial sums by atomics whose
@@ -1251,54 +1242,7 @@ __global__ void __launch_bounds__(256) k_pack(PackArgs a, uint32_t *__restrict__
 // ------------------------------------------------------------------------------------
 // Sphere batches (getSphereCrsFromXyz, cutils.pyx:220-248).
 // ------------------------------------------------------------------------------------
-struct AtomBox {
-    int32_t lo[3];
-    int32_t hi[3];  // inclusive; hi < lo => empty
-};
-
-// The sphere box and volume rule, stated ONCE for host and device (like xyz2crs: the same IEEE / int32 operations in the same order on both sides, so
-// the host may size and lay out a batch without asking the device -- group_setup, pdbeda_aggregate_cloud -- and k_make_vols' check of its totals holds).
-// R = xyz2crs(origin + radius): the box's half-widths follow from the radius alone.
-__host__ __device__ inline void sphere_half_widths(const Geom &g, double rad, int32_t R[3]) {
-    const double o[3] = {g.origin[0] + rad, g.origin[1] + rad, g.origin[2] + rad};
-    xyz2crs(g, o, R);
-}
-// An atom's box is [C - R - 1, C + R] in int32, C = xyz2crs(centre) (Q4); a box empty along any axis becomes lo 0 / hi -1 along all.  false: empty.
-__host__ __device__ inline bool atom_box(const int32_t C[3], const int32_t R[3], AtomBox *out) {
-    AtomBox bx;
-    bool empty = false;
-    for (int k = 0; k < 3; ++k) {
-        bx.lo[k] = C[k] - R[k] - 1;
-        bx.hi[k] = C[k] + R[k];
-        empty = empty || (bx.hi[k] < bx.lo[k]);
-    }
-    if (empty) { for (int k = 0; k < 3; ++k) { bx.lo[k] = 0; bx.hi[k] = -1; } }
-    *out = bx;
-    return !empty;
-}
-// A group's inclusive bounds (int32, or the int64 of aggregateCloud's unions; hi < lo along any axis: no voxel) -> its volume descriptor at the running
-// word / key bases, and the mask words and keys it adds to them.  An empty group is an all-zero volume.  A width is taken in int64 and stored as int32,
-// which IS k_make_vols' int32 `hi - lo + 1` for every input; false: a width of 2^30 voxels or more (the host's builders then leave the batch to the device).
-template <typename B>
-__host__ __device__ inline bool vol_from_bounds(const B *lo, const B *hi, int32_t group, int64_t word_base, int64_t key_base, VolDesc *out, int64_t *words, int64_t *keys) {
-    VolDesc vd;
-    bool empty = false, fits = true;
-    for (int k = 0; k < 3; ++k) empty = empty || hi[k] < lo[k];
-    for (int k = 0; k < 3; ++k) {
-        const int64_t d = empty ? 0 : (int64_t)hi[k] - (int64_t)lo[k] + 1;
-        fits = fits && d < (1ll << 30);
-        vd.org[k] = empty ? 0 : (int32_t)lo[k];
-        vd.dim[k] = (int32_t)d;
-    }
-    vd.row_words = (vd.dim[0] + 63) / 64;
-    vd.group = group;
-    vd.word_base = word_base;
-    vd.key_base = key_base;
-    *out = vd;
-    *words = (int64_t)vd.row_words * vd.dim[1] * vd.dim[2];
-    *keys = (int64_t)vd.dim[0] * vd.dim[1] * vd.dim[2];
-    return fits;
-}
+// (AtomBox, VolDesc and the box / volume rule -- sphere_half_widths, atom_box, vol_from_bounds: pdbeda_spherebox.h, which the host compiler reads too)
 
 // Thread per atom: centre C = xyz2crs(xyz), R = xyz2crs(origin + r); box [C-R-1, C+R] (Q4).
 __global__ void k_atom_boxes(const Geom *__restrict__ gp, const double *__restrict__ xyz, const float *__restrict__ radii,

@@ -31,3 +31,7 @@ for san in "thread" "address,undefined -fno-sanitize-recover=undefined"; do
     TSAN_OPTIONS=halt_on_error=1:second_deadlock_stack=1 ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 /tmp/upload_harness_san $scenario
   done
 done
+# The host's planner of sphere batches (pdb_eda_amd/csrc/pdbeda_spherebox.h) on tests/spherebox_harness.cpp under ASan + UBSan with
+# float-cast-overflow: tests/test_spherebox_host.py builds the harness that way itself, writes the cases and compares every line
+echo "sphere planner, -fsanitize=address,undefined,float-cast-overflow:"
+python3 -m pytest tests/test_spherebox_host.py -q -p no:cacheprovider
