@@ -91,6 +91,23 @@ def kept_images(rot, ortho, poly, cand, cutoff):
     return keep
 
 
+def kept_images_diag(ortho_diag, poly, cand, cutoff):
+    """kept_images for the identity operator and a diagonal cell with whole-number edges, vectorised over the candidates (every atom pair
+    is tried: few atoms, any number of candidates).  orthoMat.n is then the exact product n * a (no fma is needed to state it), and the
+    image coordinate ((1 x + 0 y) + 0 z + 0) + n a is x + n a."""
+    a = np.asarray(ortho_diag, dtype=np.float64).reshape(3)
+    poly = np.asarray(poly, dtype=np.float64).reshape(-1, 3)
+    cand = np.asarray(cand).reshape(-1, 4)
+    assert np.all(cand[:, 0] == 0) and np.all(a == np.round(a)) and float(np.abs(cand[:, 1:]).max(initial=0)) * a.max() < 2.0 ** 53
+    ot = cand[:, 1:4].astype(np.float64) * a
+    keep = np.zeros(len(cand), dtype=bool)
+    for xj in poly:
+        img = ((xj + 0.0) + 0.0) + ot
+        for xi in poly:
+            keep |= pair_dist(img, xi) <= cutoff
+    return keep
+
+
 def neighbours(rot, ortho, poly, images):
     """N in (image, atom) order."""
     if len(images) == 0:
