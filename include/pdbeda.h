@@ -415,6 +415,61 @@ int pdbeda_map_partition(pdbeda_map *map, const double *xyz, int64_t n_atoms, fl
                          int32_t *owner);                               /* box voxels, [s][r][c] of the box, c fastest; -1 = unowned */
                          /* any output may be NULL */
 
+/* ---- the map between voxels: trilinear density, atom Q-scores ---------------------------- */
+/* The density at arbitrary coordinates (no reference counterpart: getPointDensityFromXyz, ccp4.py:389-398, rounds to the nearest
+ * voxel).  The fractional grid position f[3] of a point x, in crs order, is xyz2crsCoord (ccp4.py:288-302) without its round():
+ * orthogonal cells q[i] = (x[i] - origin[i]) / gridLength[i]; otherwise q[i] = dot(deOrthoMat, x)[i] * xyzInterval[i] -
+ * crsStart[map2xyz[i]] (the dot product as everywhere: fma(a2, v2, fma(a0, v0, a1 * v1))); f[j] = q[map2crs[j]].
+ * b[j] = floor(f[j]), t[j] = f[j] - b[j]; the eight corners b + {0,1}^3 are read with utils.getPointDensityFromCrs (periodic wrap, 0
+ * where nothing is stored), promoted to fp64, and folded with lerp(a, b, t) = a + t * (b - a) in unfused fp64 along c first, then r,
+ * then s: t == 0 returns the base corner's value exactly whenever the other corner is finite, so the interpolant at a voxel centre IS
+ * the voxel.  valid = 1 when all eight corners are stored (utils.testValidCrs), whatever their weights, else 0.  Non-finite voxels
+ * propagate into the value.  n == 0 succeeds and touches nothing.  PDBEDA_ERR_ARGUMENT before any launch: a non-finite coordinate, a
+ * coordinate whose grid position is 2^29 steps or more (the message names the point), n >= 2^31.  Synchronous; a failing call leaves
+ * the context usable. */
+int pdbeda_interp_density(pdbeda_map *map, const double *xyz, int64_t n, double *out, uint8_t *valid); /* either output may be NULL */
+
+/* Per-atom Q-scores (Pintilie et al., Nature Methods 17, 2020): how well the map around an atom follows a reference Gaussian, read
+ * on concentric spheres and only where the atom is the nearest one -- independent of the grid, unlike the voxel counts of
+ * pdbeda_radial_profiles.  The host supplies the reference profile and the candidate directions (the device evaluates no exp, sin or
+ * cos), and the directions are FIXED lattices, not random draws: values are reproducible, and are not MapQ's digit for digit.
+ * Candidate levels: level l is the rows level_offsets[l] .. level_offsets[l + 1] of unit_pts ([..][3]); 1 <= n_levels <=
+ * PDBEDA_QSCORE_MAX_LEVELS, every level 1 .. PDBEDA_QSCORE_MAX_LEVEL_POINTS rows, 1 <= min_points <= the size of level 0,
+ * 2 <= n_shells <= PDBEDA_MAX_SHELLS.
+ * Sample point of atom a, shell k (radius R_k = k * (double)step, float32 step), direction u: p[i] = a[i] + R_k * u[i], unfused fp64.
+ * p is REJECTED when some atom b of xyz with an index other than a's has d2(p, b) < d2(p, a) (strict), d2 = (dx*dx + dy*dy) + dz*dz as
+ * pdbeda_map_partition evaluates it; d2(p, a) is evaluated from p like the others (not taken as R_k^2), so atoms on a's coordinate tie
+ * to the bit and reject nothing.  Nothing else rejects a point: acceptance does not depend on the map.
+ * Shell 0 is the single point a, always kept.  Shell k >= 1 walks the levels in order, stops at the first level with at least
+ * min_points accepted candidates and keeps ALL accepted candidates of that level; if no level reaches min_points it keeps the accepted
+ * candidates of the last level, which may be none (MapQ's "add candidates until enough survive", with fixed lattices).
+ * The value at a kept point is pdbeda_interp_density's.  Per scored atom: shell_n [n_shells] the kept points of a shell, shell_mean
+ * their mean (exactly 0 for an empty shell), n_points the total, valid = 1 when every kept point was valid in pdbeda_interp_density's
+ * sense, and q: the Pearson correlation over all kept points between the sampled value and ref[k] of the point's shell -- unchanged
+ * under rho -> alpha * rho + beta with alpha > 0, so the reference needs no amplitude or offset -- clipped to [-1, 1].  q is NaN when
+ * n_points < 2, when fewer than two shells kept a point, when the smallest and the largest sampled value are equal (an exact min /
+ * max), when a sampled value is not finite, and when ref takes one value over the shells that kept a point (nothing to correlate with).
+ * counters = {scored atoms (entries of `scored`) with more neighbours than the kernel stages at a time -- they take a slower path
+ * with the same results --, the largest neighbour count seen}; a neighbour of a is an atom of xyz with another index within
+ * 2 R_max (1 + 1e-6) of it, R_max = (n_shells - 1) * (double)step: farther atoms win no point.
+ * No floating-point atomic and no sum across atoms: two calls agree to the bit, and so do calls whose xyz is permuted (scored re-mapped).
+ * n_scored == 0 succeeds and touches nothing; with scored == NULL every atom is scored in order (n_scored is ignored) and n_all == 0
+ * is the same.  PDBEDA_ERR_ARGUMENT before any launch: a limit above, a step that is not finite or <= 0, a non-finite ref, unit_pts or
+ * coordinate, an index of scored outside [0, n_all) (repeats and any order are fine), n_all or n_scored >= 2^31, a scored atom whose
+ * grid position, or an R_max whose extent along a grid axis, is 2^29 steps or more.  Synchronous; a failing call leaves the context
+ * usable. */
+#define PDBEDA_QSCORE_MAX_LEVELS 8
+#define PDBEDA_QSCORE_MAX_LEVEL_POINTS 64
+int pdbeda_atom_qscores(pdbeda_map *map,
+                        const double *xyz, int64_t n_all,          /* every atom that competes for space: the symmetry atoms */
+                        const int32_t *scored, int64_t n_scored,   /* indices into xyz of the atoms to score; NULL: all, in order */
+                        float step, int32_t n_shells,              /* shell k has radius R_k = k * (double)step, k = 0 .. n_shells-1 */
+                        const double *ref,                         /* [n_shells] reference profile, made by the host */
+                        const double *unit_pts, const int32_t *level_offsets, int32_t n_levels, int32_t min_points,
+                        double *q, int32_t *n_points,              /* [n_scored] */
+                        int32_t *shell_n, double *shell_mean,      /* [n_scored][n_shells] */
+                        uint8_t *valid, int64_t counters[2]);      /* any output may be NULL */
+
 /* ---- aggregateCloud ------------------------------------------------------------------ */
 /* DensityAnalysis.aggregateCloud up to its statistics tail (densityAnalysis.py:571-731) as ONE call: the clouds of every
  * eligible atom (findAberrantBlobs, 603), the centroid-distance cut-off over all atoms (607), the best cloud and the pooled

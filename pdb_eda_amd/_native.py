@@ -120,6 +120,8 @@ _SIGS = {
     "pdbeda_region_sums": (C.c_int, [_p, _p, _p, _i64, _p, _i64, C.c_float, _p, _p, _p, _p]),
     "pdbeda_radial_profiles": (C.c_int, [_p, _p, _i64, C.c_float, C.c_int32, C.c_float, _p, _p, _p, _p, _p]),
     "pdbeda_map_partition": (C.c_int, [_p, _p, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pdbeda_interp_density": (C.c_int, [_p, _p, _i64, _p, _p]),
+    "pdbeda_atom_qscores": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_float, C.c_int32, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p]),
     "pdbeda_aggregate_cloud": (C.c_int, [_p, C.POINTER(CloudAtoms), C.c_float, C.c_double, C.POINTER(_p)]),
     "pdbeda_cloud_counts": (C.c_int, [_p, _p, _p]),
     "pdbeda_cloud_atom_rows": (C.c_int, [_p, _p, _p, _p, _p, _p]),
@@ -738,6 +740,40 @@ class DeviceMap(object):
                                                             _ptr(owner) if owners else None), "pdbeda_map_partition")
         if owners:
             out["owner"] = owner
+        return out
+
+    def interp_density(self, xyz):
+        """pdbeda_interp_density: the trilinear density at arbitrary coordinates -> ((n,) float64 values, (n,) bool flags: all eight
+        corners of the point are stored)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        out, valid = np.zeros(len(xyz)), np.zeros(len(xyz), dtype=np.uint8)
+        self._ctx.check(self._ctx._lib.pdbeda_interp_density(self._h, _ptr(xyz) if len(xyz) else None, len(xyz), _ptr(out), _ptr(valid)), "pdbeda_interp_density")
+        return out, valid.astype(bool)
+
+    def qscores(self, xyz, scored, step, ref, unit_pts, level_offsets, min_points):
+        """pdbeda_atom_qscores: ``xyz`` are the atoms that compete for space, ``scored`` the indices of those to score (None: all, in
+        order), ``ref`` the reference profile (one value per shell, shell k at radius k * float32(step)), ``unit_pts`` /
+        ``level_offsets`` the candidate directions by level.  A dict of the (n_scored,) arrays ``q``, ``nPoints``, ``valid``, the
+        (n_scored, n_shells) arrays ``shellN`` / ``shellMean`` and ``counters`` (atoms that overflowed the staging buffer, largest
+        neighbour count)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        if scored is not None:
+            scored = np.ascontiguousarray(scored, dtype=np.int32).reshape(-1)
+        ref = np.ascontiguousarray(ref, dtype=np.float64).reshape(-1)
+        unit = np.ascontiguousarray(unit_pts, dtype=np.float64).reshape(-1, 3)
+        off = np.ascontiguousarray(level_offsets, dtype=np.int32).reshape(-1)
+        if len(off) < 2 or len(unit) < int(off.max()):
+            raise ValueError("level_offsets must name at least one level inside unit_pts")
+        ns, shells = (len(xyz) if scored is None else len(scored)), len(ref)
+        out = {"q": np.full(ns, np.nan), "nPoints": np.zeros(ns, np.int32), "shellN": np.zeros((ns, shells), np.int32), "shellMean": np.zeros((ns, shells)),
+               "valid": np.zeros(ns, np.uint8), "counters": np.zeros(2, np.int64)}
+        if ns == 0:      # (nothing to score: the library would touch nothing; an empty ``scored`` must never read as "all")
+            out["valid"] = out["valid"].astype(bool)
+            return out
+        self._ctx.check(self._ctx._lib.pdbeda_atom_qscores(self._h, _ptr(xyz) if len(xyz) else None, len(xyz), _ptr(scored), ns, C.c_float(step), shells, _ptr(ref),
+                                                           _ptr(unit), _ptr(off), len(off) - 1, int(min_points), _ptr(out["q"]), _ptr(out["nPoints"]),
+                                                           _ptr(out["shellN"]), _ptr(out["shellMean"]), _ptr(out["valid"]), _ptr(out["counters"])), "pdbeda_atom_qscores")
+        out["valid"] = out["valid"].astype(bool)
         return out
 
     def aggregate_cloud(self, xyz, radius, weight, residue, alias, key, bonded_off, bonded, owner_key, cutoff, min_cloud_electrons):

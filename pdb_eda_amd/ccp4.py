@@ -113,6 +113,26 @@ def _dot3(mat, vec):
     return out
 
 
+def sphereLattice(n):
+    """The spherical Fibonacci lattice of ``n`` unit vectors, (n, 3) float64: z_j = 1 - (2j + 1) / n, phi_j = j pi (3 - sqrt 5),
+    u_j = (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z).  The fixed sample directions of the Q-scores."""
+    j = np.arange(int(n), dtype=np.float64)
+    z = 1.0 - (2.0 * j + 1.0) / float(n)
+    phi = j * (np.pi * (3.0 - np.sqrt(5.0)))
+    rho = np.sqrt(1.0 - z * z)
+    return np.stack([rho * np.cos(phi), rho * np.sin(phi), z], axis=1)
+
+
+def qScoreTables(sigma=0.6, step=0.1, nShells=21, nPoints=8, nLevels=4):
+    """What the host hands ``pdbeda_atom_qscores``: (ref, unit_pts, level_offsets).  ref[k] = exp(-0.5 (k step32 / sigma)^2) with
+    step32 = float(float32(step)), the radius the device uses; level l is ``sphereLattice(nPoints * 2**l)``."""
+    step32 = float(np.float32(step))
+    ref = np.exp(-0.5 * (np.arange(int(nShells), dtype=np.float64) * step32 / float(sigma)) ** 2)
+    levels = [sphereLattice(int(nPoints) * 2 ** l) for l in range(int(nLevels))]
+    offsets = np.concatenate([[0], np.cumsum([len(level) for level in levels])]).astype(np.int32)
+    return ref, np.concatenate(levels), offsets
+
+
 class DensityHeader(object):
     """CCP4 header + derived cell geometry (ref ccp4.py:130-316).
 
@@ -421,6 +441,29 @@ class DensityMatrix(object):
         ``owners``, ``owner``: an (ns', nr', nc') int32 array of the box, -1 where nobody owns the voxel."""
         xyz = np.asarray(xyzList, dtype=np.float64).reshape(-1, 3)
         return self._map.partition(xyz, maxDistance, cutoff, owners)
+
+    # -- the map between voxels: trilinear density, Q-scores (no reference counterpart) --
+    def getInterpolatedDensityFromXyz(self, xyzCoord):
+        """The trilinear density at a coordinate (a float) or at a list of coordinates (an array), in one device call
+        (``pdbeda_interp_density`` in include/pdbeda.h has the contract): the eight voxels around the point under the wrap rule of
+        ``getPointDensityFromCrs``, 0 where nothing is stored.  On a voxel centre it IS ``getPointDensityFromXyz``."""
+        single = self._is_single(xyzCoord)
+        values, _ = self._map.interp_density(np.asarray([xyzCoord] if single else xyzCoord, dtype=np.float64).reshape(-1, 3))
+        return float(values[0]) if single else values
+
+    def qScores(self, xyzList, scored=None, sigma=0.6, step=0.1, nShells=21, nPoints=8):
+        """Q-scores (Pintilie et al. 2020) of the coordinates ``scored`` (indices into ``xyzList``; None: all) among ALL of ``xyzList``,
+        in one device call (``pdbeda_atom_qscores`` in include/pdbeda.h has the contract): the map sampled on ``nShells`` spheres of
+        radius k * step around a coordinate, only where no other coordinate is nearer, correlated with exp(-r^2 / (2 sigma^2)).  The
+        sample directions are the fixed lattices of ``qScoreTables`` (``nPoints`` on the coarsest, doubled until ``nPoints`` survive): the
+        values are reproducible and are not MapQ's digit for digit.  A dict of ``q``, ``nPoints``, ``valid`` ((n,)), ``shellN`` /
+        ``shellMean`` ((n, nShells)) and ``counters``."""
+        levels = 1
+        while levels < 4 and int(nPoints) * 2 ** levels <= 64:      # (a level is one wave pass: 64 candidates at the most)
+            levels += 1
+        ref, unit, offsets = qScoreTables(sigma, step, nShells, nPoints, levels)
+        xyz = np.asarray(xyzList, dtype=np.float64).reshape(-1, 3)
+        return self._map.qscores(xyz, scored, step, ref, unit, offsets, nPoints)
 
     # -- whole-map blobs ------------------------------------------------------------
     def createFullBlobList(self, cutoff):

@@ -134,6 +134,27 @@ __host__ __device__ inline bool xyz2crs_if(const Geom &g, const double xyz[3], I
 __host__ __device__ inline void xyz2crs(const Geom &g, const double xyz[3], int32_t crs[3]) {
     (void)xyz2crs_if(g, xyz, crs, [](double) { return true; });
 }
+// The fractional grid position of a point, in crs order: xyz2crs_if's arithmetic without the rint (what is read BETWEEN voxels starts here).
+__host__ __device__ inline void xyz2frac(const Geom &g, const double xyz[3], double f[3]) {
+    double q[3];
+    if (g.orthogonal) {
+        for (int i = 0; i < 3; ++i) {
+            double d = xyz[i] - g.origin[i];
+            q[i] = d / g.grid_len[i];
+        }
+    } else {
+        double fr[3];
+        matvec3(g.deortho, xyz, fr);
+        for (int i = 0; i < 3; ++i) {
+            double p = fr[i] * (double)g.xyz_interval[i];
+            q[i] = p - (double)sel3(g.crs_start, g.map2xyz[i]);
+        }
+    }
+    for (int i = 0; i < 3; ++i) {
+        int a = g.map2crs[i];
+        f[i] = a == 0 ? q[0] : (a == 1 ? q[1] : q[2]);
+    }
+}
 
 // ---- 64-bit word helpers (a mask word = 64 consecutive voxels along c) -------------
 __host__ __device__ inline int popc64(uint64_t x) {

@@ -32,6 +32,7 @@
 #include "pdbeda_peaks.h"
 #include "pdbeda_profiles.h"
 #include "pdbeda_partition.h"
+#include "pdbeda_qscore.h"
 #include "pdbeda_blobshape.h"
 #include "pdbeda_blobnear.h"
 #include "pdbeda_basins.h"
@@ -3438,6 +3439,153 @@ extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_
         const D2HItem parts[9] = {{n, d_on, 8 * na}, {n_pos, d_on + na, 8 * na}, {n_neg, d_on + 2 * na, 8 * na}, {sum, d_os, 8 * na}, {sum_pos, d_os + na, 8 * na},
                                   {sum_neg, d_os + 2 * na, 8 * na}, {unowned_n, d_un, 24}, {unowned_sum, d_us, 32}, {owner, d_owner, 4 * (size_t)nbox}};
         for (int k = 0; k < 9; ++k)
+            if (parts[k].dst && parts[k].bytes) HIP_TRY(ctx, d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes));
+        return 0;
+    });
+}
+
+// ------------------------------------------------------------------------------------
+// The map between voxels: trilinear density and atom Q-scores (no reference counterpart; the contracts: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// A point the kernels may convert: finite, and every grid position below 2^29 in magnitude (the floor is cast to int32 and its neighbour is one more).
+static bool frac_castable(const Geom &g, const double p[3]) {
+    if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) return false;
+    double f[3];
+    xyz2frac(g, p, f);
+    for (int q = 0; q < 3; ++q)
+        if (!(std::fabs(f[q]) < (double)(1ll << 29))) return false;
+    return true;
+}
+
+// The launch graph: the points (through the pinned block when they fit, else a copy), k_interp_density, the results.  One wait.
+extern "C" int pdbeda_interp_density(pdbeda_map *m, const double *xyz, int64_t n, double *out, uint8_t *valid) {
+    if (!m || n < 0 || (n > 0 && !xyz)) return PDBEDA_ERR_ARGUMENT;
+    if (n == 0) return PDBEDA_OK;
+    pdbeda_ctx *ctx = m->ctx;
+    if (n >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "interpolated density: 2^31 points or more");
+    for (int64_t i = 0; i < n; ++i)
+        if (!frac_castable(m->geom, xyz + 3 * i))
+            return fail(ctx, PDBEDA_ERR_ARGUMENT, "interpolated density: point %lld is not finite or lies 2^29 grid steps or more from the map's origin", (long long)i);
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *d_xyz = nullptr, *d_out = nullptr;
+    uint8_t *d_valid = nullptr;
+    return with_scratch(ctx, "interpolated density", [&](Carver &cv) { cv.take(d_xyz, 3 * n); cv.take(d_out, n); cv.take(d_valid, n); }, [&]() -> int {
+        const double *in = pinned_in(ctx, xyz, (size_t)(3 * n));
+        if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, (size_t)(24 * n))); in = d_xyz; }
+        double *r_out = pinned_out(ctx, out, (size_t)n);
+        uint8_t *r_valid = pinned_out(ctx, valid, (size_t)n);
+        { PROF(ctx, "k_interp_density"); hipLaunchKernelGGL(k_interp_density, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->geom_dev, m->dens, in, n,
+                                                            out ? (r_out ? r_out : d_out) : (double *)nullptr, valid ? (r_valid ? r_valid : d_valid) : (uint8_t *)nullptr); }
+        HIP_TRY(ctx, hipGetLastError());
+        if (out && !r_out) HIP_TRY(ctx, d2h(ctx, out, d_out, 8 * (size_t)n));
+        if (valid && !r_valid) HIP_TRY(ctx, d2h(ctx, valid, d_valid, (size_t)n));
+        return 0;
+    });
+}
+
+// The launch graph: memset of the cell counts and the two counters; the atoms, the scored indices and the host's tables (reference profile,
+// candidate directions); k_grid_count_points / k_grid_scan / k_grid_scatter_indexed over the atoms inside the crop box -- the scored atoms' bounding
+// box grown by the reach, 2 R_max: an atom outside it wins no sample point --; k_atom_qscores, a wave per scored atom; the results.  One wait.
+extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_all, const int32_t *scored, int64_t n_scored, float step, int32_t n_shells,
+                                   const double *ref, const double *unit_pts, const int32_t *level_offsets, int32_t n_levels, int32_t min_points,
+                                   double *q, int32_t *n_points, int32_t *shell_n, double *shell_mean, uint8_t *valid, int64_t counters[2]) {
+    if (!m || n_all < 0 || n_scored < 0 || (n_all > 0 && !xyz)) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = m->ctx;
+    if (!scored) n_scored = n_all;
+    if (n_scored == 0) return PDBEDA_OK;
+    if (n_all >= (1ll << 31) || n_scored >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: 2^31 atoms or more");
+    if (!ref || !unit_pts || !level_offsets) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: null table");
+    if (n_shells < 2 || n_shells > PDBEDA_MAX_SHELLS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: n_shells must be 2 .. %d", PDBEDA_MAX_SHELLS);
+    if (n_levels < 1 || n_levels > PDBEDA_QSCORE_MAX_LEVELS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: n_levels must be 1 .. %d", PDBEDA_QSCORE_MAX_LEVELS);
+    if (level_offsets[0] != 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: level_offsets must start at 0");
+    for (int l = 0; l < n_levels; ++l) {
+        const int64_t rows = (int64_t)level_offsets[l + 1] - level_offsets[l];
+        if (rows < 1 || rows > PDBEDA_QSCORE_MAX_LEVEL_POINTS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: level %d has %lld candidates (1 .. %d)", l, (long long)rows, PDBEDA_QSCORE_MAX_LEVEL_POINTS);
+    }
+    if (min_points < 1 || min_points > level_offsets[1]) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: min_points must be 1 .. the size of level 0");
+    if (!std::isfinite(step) || !(step > 0.0f)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: the step must be finite and > 0");
+    const int64_t n_unit = level_offsets[n_levels];
+    if (!all_finite(ref, n_shells) || !all_finite(unit_pts, 3 * n_unit)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: non-finite reference profile or direction");
+    if (!all_finite(xyz, 3 * n_all)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: non-finite coordinate");
+    const Geom &g = m->geom;
+    const double r_max = (double)(n_shells - 1) * (double)step;
+    {   // every sample point stays castable: |f(atom)| < 2^29 and the sphere of R_max spans fewer than 2^29 steps of every grid axis
+        const double limit = (double)(1ll << 29);
+        for (int i = 0; i < 3; ++i) {
+            const double per_unit = g.orthogonal ? 1.0 / std::fabs(g.grid_len[i])
+                                                 : (std::fabs(g.deortho[3 * i]) + std::fabs(g.deortho[3 * i + 1]) + std::fabs(g.deortho[3 * i + 2])) * (double)g.xyz_interval[i];
+            if (!(r_max * per_unit < limit)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: the largest shell spans 2^29 grid steps or more");
+        }
+    }
+    double slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t i = 0; i < n_scored; ++i) {
+        const int64_t at = scored ? (int64_t)scored[i] : i;
+        if (at < 0 || at >= n_all) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: scored[%lld] = %lld is outside the %lld atoms", (long long)i, (long long)at, (long long)n_all);
+        const double *p = xyz + 3 * at;
+        if (!frac_castable(g, p)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: atom %lld lies 2^29 grid steps or more from the map's origin", (long long)at);
+        for (int k = 0; k < 3; ++k) { slo[k] = std::min(slo[k], p[k]); shi[k] = std::max(shi[k], p[k]); }
+    }
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the crop box (what can matter to a scored atom), and the grid over its intersection with the atoms' bounding box: never empty, the scored atoms lie in both
+    const double reach = 2.0 * r_max * (1.0 + 1e-6);
+    double crop_lo[3], crop_hi[3], alo[3], ahi[3], glo[3], ghi[3];
+    bbox3(xyz, n_all, alo, ahi);
+    for (int k = 0; k < 3; ++k) {
+        const double pad = reach * (1.0 + 1e-5) + 1e-8 * (std::fabs(slo[k]) + std::fabs(shi[k]) + 1.0);
+        crop_lo[k] = slo[k] - pad; crop_hi[k] = shi[k] + pad;
+        glo[k] = std::max(crop_lo[k], alo[k]); ghi[k] = std::min(crop_hi[k], ahi[k]);
+    }
+    const CellGrid grid = make_cell_grid(glo, ghi, reach, n_all, crop_lo, crop_hi);
+    const int64_t cells = grid.n_cells;
+    const size_t na = (size_t)n_all, ns = (size_t)n_scored, rows = ns * (size_t)n_shells;
+    double *d_xyz = nullptr, *d_sorted = nullptr, *d_tab = nullptr, *d_q = nullptr, *d_mean = nullptr;
+    unsigned *d_count = nullptr, *d_cursor = nullptr, *d_start = nullptr;
+    int *d_sidx = nullptr;
+    int32_t *d_scored = nullptr, *d_np = nullptr, *d_sn = nullptr;
+    uint8_t *d_valid = nullptr;
+    unsigned long long *d_ctr = nullptr;
+    return with_scratch(ctx, "atom Q-scores", [&](Carver &cv) {
+        cv.take(d_xyz, 3 * na);
+        cv.take(d_scored, scored ? ns : 0);
+        cv.take(d_tab, (size_t)n_shells + 3 * (size_t)n_unit);      // ref [n_shells] | unit_pts [n_unit][3]
+        cv.take(d_count, cells);
+        cv.take(d_cursor, cells);
+        cv.take(d_start, cells + 1);
+        cv.take(d_sorted, 3 * na);
+        cv.take(d_sidx, na);
+        cv.take(d_ctr, 2);
+        cv.take(d_q, ns);
+        cv.take(d_np, ns);
+        cv.take(d_sn, rows);
+        cv.take(d_mean, rows);
+        cv.take(d_valid, ns);
+    }, [&]() -> int {
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 4 * (size_t)cells, st));
+        HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, 16, st));
+        HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, 24 * na));
+        if (scored) HIP_TRY(ctx, h2d_one(ctx, d_scored, scored, 4 * ns));
+        {
+            const H2DItem in[2] = {{d_tab, ref, 8 * (size_t)n_shells}, {d_tab + n_shells, unit_pts, 24 * (size_t)n_unit}};
+            HIP_TRY(ctx, h2d_row(ctx, in, 2));
+        }
+        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_all, 256)), dim3(256), 0, st, d_xyz, n_all, grid, d_count); }
+        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count, (int)cells, d_start, d_cursor, nullptr); }
+        { PROF(ctx, "k_grid_scatter_indexed"); hipLaunchKernelGGL(k_grid_scatter_indexed, dim3(grid_for(n_all, 256)), dim3(256), 0, st, d_xyz, n_all, grid, d_cursor, d_sorted, d_sidx, n_all); }
+        QScoreArgs a;
+        a.geom = m->geom_dev; a.dens = m->dens; a.xyz = d_xyz; a.scored = scored ? d_scored : nullptr; a.n_scored = n_scored;
+        a.grid = grid; a.sorted = d_sorted; a.sorted_index = d_sidx; a.start = d_start;
+        a.step = (double)step; a.reach2 = reach * reach;
+        a.n_shells = n_shells; a.n_levels = n_levels; a.min_points = min_points;
+        for (int l = 0; l <= PDBEDA_QSCORE_MAX_LEVELS; ++l) a.level_off[l] = level_offsets[std::min(l, n_levels)];
+        a.ref = d_tab; a.unit = d_tab + n_shells;
+        a.q = d_q; a.n_points = d_np; a.shell_n = d_sn; a.shell_mean = d_mean; a.valid = d_valid; a.counters = d_ctr;
+        { PROF(ctx, "k_atom_qscores"); hipLaunchKernelGGL(k_atom_qscores, dim3((unsigned)((n_scored + 3) / 4)), dim3(256), 0, st, a); }
+        HIP_TRY(ctx, hipGetLastError());
+        const D2HItem parts[6] = {{q, d_q, 8 * ns}, {n_points, d_np, 4 * ns}, {shell_n, d_sn, 4 * rows}, {shell_mean, d_mean, 8 * rows}, {valid, d_valid, ns}, {counters, d_ctr, 16}};
+        for (int k = 0; k < 6; ++k)
             if (parts[k].dst && parts[k].bytes) HIP_TRY(ctx, d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes));
         return 0;
     });

@@ -414,6 +414,8 @@ class DensityAnalysis(object):
     atomRadialProfileHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'atom_type', 'electrons', 'bfactor', 'valid',
                                'shell_voxels', 'shell_density', 'shell_significant_voxels', 'shell_significant_density']
     atomTypeRadialProfileHeader = ['atom_type', 'num_atoms', 'optimized_radius', 'shell_outer_radius', 'median_cumulative_density_per_electron', 'profile_radius']
+    atomQScoreHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'valid', 'q_score', 'n_points']
+    residueQScoreHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'mean_q_score', 'min_q_score', 'num_atoms_scored']
 
     def __init__(self, pdbid, densityObj=None, diffDensityObj=None, biopdbObj=None, pdbObj=None):
         self.pdbid = pdbid
@@ -429,6 +431,7 @@ class DensityAnalysis(object):
         self._asymmetryAtomCoords = None
         self._greenBlobList = None
         self._partitions = {}
+        self._qScores = None
         self._redBlobList = None
         self._blueBlobList = None
         self._greenPeakList = None
@@ -1450,3 +1453,65 @@ class DensityAnalysis(object):
             columns["symmetry"][k] = tuple(sym)
         return [list(row) for row in zip(sizes.tolist(), unowned.tolist(), n_owners.tolist(), columns["chain"], columns["number"], columns["resname"], columns["name"],
                                          columns["symmetry"], main_voxels.tolist())]
+
+    # ---- atom Q-scores over the 2Fo-Fc map (no reference counterpart) -----------------------------
+    def _atomQScores(self):
+        """(q, n_points, valid) per atom of the structure, from ONE device call kept on the object (``pdbeda_atom_qscores`` in
+        include/pdbeda.h has the contract; ``DensityMatrix.qScores`` has the defaults): ALL symmetry atoms compete for the sample
+        points, the identity images are scored.  An atom the symmetry list does not hold -- it lies outside the map's box -- has no
+        score: NaN, 0 points, not valid."""
+        if self._qScores is None:
+            coords = self.symmetryAtomCoords
+            if len(coords) == 0:
+                raise ValueError("XB must be a 2-dimensional array.")       # (the blob table's failure for a file without operators)
+            symmetryAtoms = self.symmetryAtoms
+            own = np.nonzero(symmetryAtoms._ident)[0]
+            got = self.densityObj.qScores(np.asarray(coords, dtype=np.float64), scored=own.astype(np.int32))
+            n_atoms = len(_structure.columns(self.biopdbObj).atoms)
+            q, n_points, valid = np.full(n_atoms, np.nan), np.zeros(n_atoms, dtype=np.int64), np.zeros(n_atoms, dtype=bool)
+            where = symmetryAtoms._idx[own]
+            q[where], n_points[where], valid[where] = got["q"], got["nPoints"], got["valid"]
+            self._qScores = (q, n_points, valid, got["counters"])
+        return self._qScores[:3]
+
+    def calculateAtomQScores(self, type=""):
+        """One row per atom (``atomQScoreHeader``; the atoms and leading columns of ``calculateAtomRegionDensity``): the Q-score of the
+        atom over the 2Fo-Fc map -- how well the density around it follows a Gaussian, sampled only where this atom is the nearest of
+        all symmetry atoms -- with the number of sample points behind it; q_score is None where it is undefined (a flat or non-finite
+        neighbourhood, fewer than two shells with a point, an atom outside the map's box)."""
+        cols, pick, lead = self._atomPick(type)
+        q, n_points, valid = self._atomQScores()
+        return self._rows(*lead, cols.bfactor[pick], valid[pick], [None if v != v else v for v in q[pick].tolist()], n_points[pick])
+
+    def calculateResidueQScores(self, type=""):
+        """One row per residue (``residueQScoreHeader``; the leading columns of ``calculateResidueRegionDiscrepancies``): the mean and the
+        minimum of its atoms' Q-scores over the atoms that have one, and how many those are (None, None, 0 when none has)."""
+        cols, lead, atom_rows, off = self._residuePick(type, None, False)
+        q = self._atomQScores()[0][atom_rows]
+        mean, low, count = [], [], []
+        for k in range(len(off) - 1):
+            mine = q[off[k]:off[k + 1]]
+            mine = mine[~np.isnan(mine)]
+            count.append(len(mine))
+            mean.append(float(mine.mean()) if len(mine) else None)
+            low.append(float(mine.min()) if len(mine) else None)
+        return self._rows(*lead, mean, low, count)
+
+    def qScoreSummary(self):
+        """Mean and median Q-score, each with the number of atoms behind it, over all atoms that have a score, the backbone (N, CA, C, O
+        of residues with id[0] == ' '), the side chains (their other atoms) and the waters (HOH / WAT / DOD): a dict
+        ``<class>_mean_q_score`` / ``<class>_median_q_score`` / ``<class>_num_atoms`` (None, None, 0 for an empty class)."""
+        cols = _structure.columns(self.biopdbObj)
+        q = self._atomQScores()[0]
+        names = np.asarray(cols.name, dtype=object)
+        het = cols.res_het[cols.res_of_atom] if len(cols.atoms) else np.zeros(0, dtype=bool)
+        backbone = np.isin(names, ("N", "CA", "C", "O")) & ~het if len(cols.atoms) else np.zeros(0, dtype=bool)
+        water = np.isin(np.asarray(cols.atom_lists("resname"), dtype=object), ("HOH", "WAT", "DOD")) if len(cols.atoms) else np.zeros(0, dtype=bool)
+        have = ~np.isnan(q)
+        out = {}
+        for name, mask in (("all", have), ("backbone", have & backbone), ("side_chain", have & ~het & ~backbone), ("water", have & water)):
+            mine = q[mask]
+            out[name + "_mean_q_score"] = float(mine.mean()) if len(mine) else None
+            out[name + "_median_q_score"] = float(np.median(mine)) if len(mine) else None
+            out[name + "_num_atoms"] = int(len(mine))
+        return out

@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore")
 
 
 def numpyConverter(obj):
@@ -122,6 +122,12 @@ def _partitionSummaryTable(analyzer, o):
     return [[summary[name] for name in _PARTITION_SUMMARY]]
 
 
+def _qScoreSummaryTable(analyzer, o):
+    summary = analyzer.qScoreSummary()
+    return [[summary[name] for name in _QSCORE_SUMMARY]]
+
+
+_QSCORE_SUMMARY = [cls + "_" + what for cls in ("all", "backbone", "side_chain", "water") for what in ("mean_q_score", "median_q_score", "num_atoms")]
 _PARTITION_SUMMARY = ["max_distance", "num_sd", "box_voxels", "asymmetric_unit_voxels", "symmetry_voxels", "unowned_voxels", "unowned_fraction", "unowned_mean",
                       "unowned_std", "map_mean", "map_std"] + [prefix + cls + "_" + sign + "_discrepancy" for cls in ("asymmetric_unit", "symmetry", "unowned")
                                                               for sign in ("positive", "negative") for prefix in ("", "num_electrons_")]
@@ -167,6 +173,10 @@ TABLES = {
     ("partition", "residue"): (lambda an: _DA.residuePartitionHeader, lambda an, o: an.calculateResiduePartitionDiscrepancies(o["radius"], o["numSD"], o["type"])),
     ("partition", "summary"): (lambda an: list(_PARTITION_SUMMARY), _partitionSummaryTable),
     ("partition", "blob"): (lambda an: _DA.blobOwnershipHeader, _partitionBlobTable),
+    # (no reference counterpart: Q-scores over the 2Fo-Fc map, all symmetry atoms competing for the sample points)
+    ("qscore", "atom"): (lambda an: _DA.atomQScoreHeader, lambda an, o: an.calculateAtomQScores(o["type"])),
+    ("qscore", "residue"): (lambda an: _DA.residueQScoreHeader, lambda an, o: an.calculateResidueQScores(o["type"])),
+    ("qscore", "summary"): (lambda an: list(_QSCORE_SUMMARY), _qScoreSummaryTable),
     ("statistics", "residue"): (lambda an: an.residueMetricsHeaderList, lambda an, o: an.residueMetrics()),
     ("statistics", "atom"): (lambda an: an.atomMetricsHeaderList, lambda an, o: _plainColumns(an.atomMetrics(), **_SYM)),
 }
@@ -176,9 +186,9 @@ def rows(analyzer, mode, level="atom", radius=None, numSD=None, type="", atomMas
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin;  level: atom | residue | domain | symmetry-atom
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore;  level: atom | residue | domain | symmetry-atom
     (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak, basin, shape and dipole) | atom-type (profile) | summary | blob
-    (partition);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
+    (partition) | summary (qscore: atom | residue | summary, no other option applies);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
     (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
     maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default);  dipole: always the fused green
     and red lists (numSD default 3.0), ``radius`` is the largest gap between the two blobs when given (else 2.5 A);  radius default 3.5 elsewhere."""
