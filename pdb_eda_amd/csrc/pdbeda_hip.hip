@@ -1393,14 +1393,21 @@ static void launch_tile_label(pdbeda_ctx *ctx, unsigned n_tiles, const Job &job,
 }
 
 // fused: the launch also ranks the roots and writes the blob table (k_emit_tiles is then not launched) -- see k_labels_tiles
+// (a fused launch of a job whose rank counters come in groups of 16 -- maps up to 2^25 keys -- takes the instantiation that
+//  builds the rank table under its second trip: UNDER in k_labels_tiles; every other launch is the kernel as it was)
+template <bool FUSED, bool UNDER>
+static void launch_labels_cw(pdbeda_ctx *ctx, const Job &job, const TileDims &td, int32_t *labels_dev, const Geom *geom_dev) {
+    switch (td.cw) {
+        case 1: hipLaunchKernelGGL((k_labels_tiles<1, FUSED, UNDER>), dim3(td.ctiles, td.rtiles, td.stiles), dim3(PDBEDA_LABELS_NT_THREADS), 0, ctx->stream, job, td, labels_dev, geom_dev); break;
+        case 2: hipLaunchKernelGGL((k_labels_tiles<2, FUSED, UNDER>), dim3(td.ctiles, td.rtiles, td.stiles), dim3(PDBEDA_LABELS_NT_THREADS), 0, ctx->stream, job, td, labels_dev, geom_dev); break;
+        case 3: hipLaunchKernelGGL((k_labels_tiles<3, FUSED, UNDER>), dim3(td.ctiles, td.rtiles, td.stiles), dim3(PDBEDA_LABELS_NT_THREADS), 0, ctx->stream, job, td, labels_dev, geom_dev); break;
+        default: hipLaunchKernelGGL((k_labels_tiles<4, FUSED, UNDER>), dim3(td.ctiles, td.rtiles, td.stiles), dim3(PDBEDA_LABELS_NT_THREADS), 0, ctx->stream, job, td, labels_dev, geom_dev); break;
+    }
+}
 template <bool FUSED>
 static void launch_labels(pdbeda_ctx *ctx, const Job &job, const TileDims &td, int32_t *labels_dev, const Geom *geom_dev) {
-    switch (td.cw) {
-        case 1: hipLaunchKernelGGL((k_labels_tiles<1, FUSED>), dim3(td.ctiles, td.rtiles, td.stiles), dim3(PDBEDA_LABELS_NT_THREADS), 0, ctx->stream, job, td, labels_dev, geom_dev); break;
-        case 2: hipLaunchKernelGGL((k_labels_tiles<2, FUSED>), dim3(td.ctiles, td.rtiles, td.stiles), dim3(PDBEDA_LABELS_NT_THREADS), 0, ctx->stream, job, td, labels_dev, geom_dev); break;
-        case 3: hipLaunchKernelGGL((k_labels_tiles<3, FUSED>), dim3(td.ctiles, td.rtiles, td.stiles), dim3(PDBEDA_LABELS_NT_THREADS), 0, ctx->stream, job, td, labels_dev, geom_dev); break;
-        default: hipLaunchKernelGGL((k_labels_tiles<4, FUSED>), dim3(td.ctiles, td.rtiles, td.stiles), dim3(PDBEDA_LABELS_NT_THREADS), 0, ctx->stream, job, td, labels_dev, geom_dev); break;
-    }
+    if (FUSED && job.fine_shift == 4) launch_labels_cw<FUSED, FUSED>(ctx, job, td, labels_dev, geom_dev);
+    else launch_labels_cw<FUSED, false>(ctx, job, td, labels_dev, geom_dev);
 }
 
 // Enqueue a whole-map job.  tier 0 carves the arena for what maps need in practice -- unit-tile run / component ids for a quarter of

@@ -793,6 +793,10 @@ __device__ __forceinline__ uint32_t sum_u16_first(const uint4 q, int take) {
     return acc;
 }
 
+// A workgroup barrier for LDS traffic only: __syncthreads() also waits for the wave's global loads and stores
+// (s_waitcnt vmcnt(0)), which is what a kernel that has loads or fire-and-forget stores in flight must NOT do.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // Exclusive prefix table over groups of fine_per_group counters, built by the calling block in LDS; returns the total.
 // A thread owns KEY_GROUPS / 256 = 4 consecutive groups: all its loads are in flight at once (the table is one memory
 // round trip + one block scan, not a loop of dependent trips; 32 KiB per block at 256^3).  fine_count is padded to whole
@@ -807,14 +811,25 @@ struct RankTableLoads {
     uint32_t v[PER];
     bool summed;
 };
-template <int NT = 256, typename JobRef = Job>
+// G16: the caller has seen that the groups hold 16 counters (fine_shift == 4) -- the quads and nothing else
+template <int NT = 256, bool G16 = false, typename JobRef = Job>
 __device__ __forceinline__ void rank_table_issue(const JobRef &job, RankTableLoads<NT> &ld) {
     constexpr int PER = KEY_GROUPS / NT;
     const int tid = threadIdx.x;
-    const int G = job.fine_per_group, n_groups = job.n_groups, Q = G / 8;   // quads (8 counters = 16 B) per group
+    const int G = G16 ? 16 : job.fine_per_group, n_groups = job.n_groups, Q = G / 8;   // quads (8 counters = 16 B) per group
     const uint4 *fine4 = reinterpret_cast<const uint4 *>(job.fine_count);
     ld.summed = Q != 2;
-    if (Q == 2) {   // (maps up to 2^25 keys: 256^3 fused)
+    if (G16) {
+        // unguarded: a group past the last one reads the last one (group 0 is always there: job_carve), and rank_table_sum
+        // drops it -- no branch and no zeroed register between the loads, which the compiler then keeps together
+        const int last = max(n_groups - 1, 0);
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int e = min(tid * PER + k, last);
+            ld.q[2 * k] = fine4[(size_t)e * 2];
+            ld.q[2 * k + 1] = fine4[(size_t)e * 2 + 1];
+        }
+    } else if (Q == 2) {   // (maps up to 2^25 keys: 256^3 fused)
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int e = tid * PER + k;
@@ -839,26 +854,38 @@ __device__ __forceinline__ void rank_table_issue(const JobRef &job, RankTableLoa
         }
     }
 }
+// The quads of a thread's groups down to the groups' sums (2 * PER quads -> PER words), for a caller that issues further loads
+// between rank_table_issue and rank_table_finish and wants the quads' registers for them.
+// (n_groups: of the job, behind an issue with G16, whose loads are unguarded)
 template <int NT = 256>
+__device__ __forceinline__ void rank_table_sum(RankTableLoads<NT> &ld, int n_groups = KEY_GROUPS) {
+    constexpr int PER = KEY_GROUPS / NT;
+    if (!ld.summed) {
+#pragma unroll
+        for (int k = 0; k < PER; ++k) ld.v[k] = (int)threadIdx.x * PER + k < n_groups ? sum_u16x8(ld.q[2 * k]) + sum_u16x8(ld.q[2 * k + 1]) : 0u;
+        ld.summed = true;
+    }
+}
+// LDS_ONLY: the two barriers wait for LDS alone (lds_barrier) -- for a caller that has global loads in flight across the scan,
+// which a __syncthreads() would wait for.  The table is LDS traffic, so nothing else is needed; such a caller's own later
+// barrier orders whatever it has in global memory.
+template <int NT = 256, bool LDS_ONLY = false>
 __device__ __forceinline__ uint32_t rank_table_finish(RankTableLoads<NT> &ld, uint32_t *s_pre /* [KEY_GROUPS] */, uint32_t *s_wave /* [NT / 64] */) {
     constexpr int PER = KEY_GROUPS / NT;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (!ld.summed) {
-#pragma unroll
-        for (int k = 0; k < PER; ++k) ld.v[k] = sum_u16x8(ld.q[2 * k]) + sum_u16x8(ld.q[2 * k + 1]);
-    }
+    rank_table_sum<NT>(ld);
     uint32_t mine = 0;
 #pragma unroll
     for (int k = 0; k < PER; ++k) mine += ld.v[k];
     const uint32_t x = wave_scan(mine);   // (six DPP adds: the shuffle form went through the LDS crossbar six times, one after the other)
     if (lane == 63) s_wave[wv] = x;
-    __syncthreads();
+    if (LDS_ONLY) lds_barrier(); else __syncthreads();
     uint32_t pre = x - mine, total = 0;
 #pragma unroll
     for (int k = 0; k < NT / 64; ++k) { const uint32_t w = s_wave[k]; pre += k < wv ? w : 0u; total += w; }
 #pragma unroll
     for (int k = 0; k < PER; ++k) { s_pre[tid * PER + k] = pre; pre += ld.v[k]; }
-    __syncthreads();
+    if (LDS_ONLY) lds_barrier(); else __syncthreads();
     return total;
 }
 // Exclusive prefix table over groups of fine_per_group counters, built by the calling block in LDS; returns the total.
@@ -904,6 +931,23 @@ __device__ __forceinline__ void rank_issue(const JobRef &job, unsigned long long
     ld.mid = reinterpret_cast<const uint2 *>(job.mid_count)[f];
     const ulonglong2 *bits2 = reinterpret_cast<const ulonglong2 *>(job.key_bits + (kw & ~3u));
     ld.b0 = bits2[0]; ld.b1 = bits2[1];
+}
+// For a caller that does other work between rank_issue and rank_finish, placed where that work ends: the compiler takes no use
+// of a loaded value (the masking of rank_finish is plain arithmetic, free to move) up in front of this statement, so the
+// wait for the loads stays behind it.
+__device__ __forceinline__ void rank_loads_hold(RankLoads &ld) {
+    // (whole register tuples, as the loads wrote them: word by word the register allocator copied words out of the tuples
+    //  first -- behind waits of its own)
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+    u32x4 q0 = {ld.q0.x, ld.q0.y, ld.q0.z, ld.q0.w}, q1 = {ld.q1.x, ld.q1.y, ld.q1.z, ld.q1.w};
+    u32x2 mid = {ld.mid.x, ld.mid.y};
+    u64x2 b0 = {ld.b0.x, ld.b0.y}, b1 = {ld.b1.x, ld.b1.y};
+    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(mid), "+v"(b0), "+v"(b1));
+    ld.q0 = make_uint4(q0.x, q0.y, q0.z, q0.w); ld.q1 = make_uint4(q1.x, q1.y, q1.z, q1.w);
+    ld.mid = make_uint2(mid.x, mid.y);
+    ld.b0.x = b0.x; ld.b0.y = b0.y; ld.b1.x = b1.x; ld.b1.y = b1.y;
 }
 __device__ __forceinline__ uint32_t rank_finish(const uint32_t *s_pre, unsigned long long key, const RankLoads &ld) {
     const uint32_t kw = (uint32_t)(key >> 6), f = kw / (uint32_t)KEY_FINE, e = f >> 4;

@@ -106,9 +106,7 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// A workgroup barrier for LDS traffic only: __syncthreads() also waits for the wave's global stores to be acknowledged
-// (s_waitcnt vmcnt(0)), which is what a kernel that has fire-and-forget stores in flight must NOT do.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (lds_barrier(), the workgroup barrier for LDS traffic only: pdbeda_kernels.h, beside the rank table that takes it)
 
 // A 32-bit word of global memory that no workgroup of the running kernel writes (an earlier kernel of the job did), read
 // through the SCALAR cache: the address is block-uniform, the load rides on lgkmcnt beside the kernel arguments -- not on
@@ -1260,7 +1258,7 @@ constexpr int LCAP = 4096;  // word-runs of a tile whose run -> component bytes 
 #ifndef PDBEDA_LABELS_NT_THREADS
 #define PDBEDA_LABELS_NT_THREADS 512
 #endif
-template <int CW, bool FUSED>
+template <int CW, bool FUSED, bool UNDER = false>
 __global__ void __launch_bounds__(PDBEDA_LABELS_NT_THREADS, FUSED ? 8 : 1) k_labels_tiles(Job job_arg, TileDims td, int32_t *__restrict__ labels, const Geom *__restrict__ gp) {
     // the job is read from the kernel-argument segment where it is used (see PDBEDA_LATE_JOB): its ~45 pointers do not fit the
     // scalar registers beside the row loop -- passed by value they were copied to scratch at entry
@@ -1378,67 +1376,97 @@ __global__ void __launch_bounds__(PDBEDA_LABELS_NT_THREADS, FUSED ? 8 : 1) k_lab
         for (int k = 0; k < 5; ++k) (&s_acc[0][0])[tid + NTL * k] = 0ull;
         if (tid < CCAP) s_accn[tid] = 0u;
         /*@L7*/
-        total_blobs = rank_table_lds<NTL>(lj, s_pre, s_wave);   // (two barriers inside)
-        /*@L1*/
-        n_in = min(n_in, (uint32_t)INBOX_CAP);
-        write_mask_tables();   // (the masks are back by now; their registers are free for the second trip)
-        // ---- second trip: waves 0-3 fetch the tile's inbox (an entry per thread) and rank the roots of their components;
-        //      waves 4-7 fetch the records of the tile's own roots.  Everything is issued before anything is consumed. ----
+        // ---- the two trips.  UNDER (the host launches this form for groups of 16 counters, fine_shift == 4: maps up to 2^25
+        //      keys): the rank counters ride in the FIRST trip, and the table's scan -- LDS work and two barriers -- runs UNDER
+        //      the second trip, none of whose addresses needs the table: a rank's loads need the key (kpar, first trip;
+        //      key_base1, an argument), the inbox its count, the records kpar.  Larger groups keep the earlier order: the
+        //      table (from group_count, or a loop of loads) with its barriers, then the second trip.  (A kernel of its own and
+        //      no branch: with both orders in one body the loads of the one were pending registers in the other for the
+        //      compiler's wait counts, and the quads of the table went out in two trips behind a vmcnt(0).) ----
         static_assert(INBOX_CAP <= 256, "an inbox entry per thread of the lower half");
-        const bool used = kp != KP_UNUSED;
-        // an inbox entry is eleven 8-byte words (local | n, the seven FixSums fields, sum c / r / s): thread t of the lower half
-        // takes words 0-4 of entry t, thread t + 256 words 5-10 (and word 0 again, for the slot).  The two halves of the
-        // workgroup run DIFFERENT code from here to the barrier (whole waves: no divergence), and what one half holds is
-        // defined inside its own region -- a value loaded in front of the other half's code would be live across it for the
-        // register allocator (22 registers of entry + 24 of record beside the rank loads spilled to scratch).
         static_assert(sizeof(InboxEntry) == 88, "eleven words");
-        const bool have = (uint32_t)(tid & 255) < n_in;
-        const unsigned long long *ew = reinterpret_cast<const unsigned long long *>(lj.inbox + (size_t)bid * INBOX_CAP + (tid & 255));
-        my_root = tid >= 256 && used && kp_id(kp) == jd;   // a root of this tile: its blob's table row is mine
-        if (tid < 256) {
-            unsigned long long e_head = 0ull, e_w[4] = {0ull, 0ull, 0ull, 0ull};
-            if (have) {
-                e_head = ew[0];
+        static_assert(FUSED || !UNDER, "the table under the second trip: a form of the fused writer");
+        {
+            RankTableLoads<NTL> tl;
+            if (UNDER) {
+                rank_table_issue<NTL, true>(lj, tl);
+                // the first trip's loads land together: wait for all of it HERE (the quads are its last loads), take the quads
+                // down to their groups' sums (16 registers -> 2), and let no load of the second trip be issued in front of that
+                rank_table_sum<NTL>(tl, lj.n_groups);
+                static_assert(RankTableLoads<NTL>::PER == 2, "two sums a thread");
+                asm volatile("" : "+v"(tl.v[0]), "+v"(tl.v[1]) : : "memory");
+            } else total_blobs = rank_table_lds<NTL>(lj, s_pre, s_wave);   // (two barriers inside)
+            /*@L1*/
+            n_in = min(n_in, (uint32_t)INBOX_CAP);
+            write_mask_tables();   // (the masks are back by now; their registers are free for the second trip)
+            // second trip: waves 0-3 fetch the tile's inbox (an entry per thread) and rank the roots of their components; waves
+            // 4-7 fetch the records of the tile's own roots.  Everything is issued before anything is consumed.
+            const bool used = kp != KP_UNUSED;
+            // an inbox entry is eleven 8-byte words (local | n, the seven FixSums fields, sum c / r / s): thread t of the lower
+            // half takes words 0-4 of entry t, thread t + 256 words 5-10 (and word 0 again, for the slot).  The two halves of
+            // the workgroup run DIFFERENT code from here to the barrier (whole waves, a scalar branch: no divergence), and
+            // what one half holds is defined inside its own region -- a value loaded in front of the other half's code would be
+            // live across it for the register allocator (22 registers of entry + 24 of record beside the rank loads spilled
+            // to scratch).  So each region has the scan inside it, between its loads and their use: every wave passes the
+            // same two barriers, in whichever region it runs.
+            const bool have = (uint32_t)(tid & 255) < n_in;
+            const unsigned long long *ew = reinterpret_cast<const unsigned long long *>(lj.inbox + (size_t)bid * INBOX_CAP + (tid & 255));
+            my_root = tid >= 256 && used && kp_id(kp) == jd;   // a root of this tile: its blob's table row is mine
+            if (wvs < 4) {
+                unsigned long long e_head = 0ull, e_w[4] = {0ull, 0ull, 0ull, 0ull};
+                if (have) {
+                    e_head = ew[0];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) e_w[k] = ew[1 + k];
-            }
-            // thread 255 also ranks the first key of volume 1 (= the blobs of volume 0): in the slot of its own component if
-            // that id is unused, as it nearly always is -- a second pass otherwise
-            const bool vol0_lane = tid == 255 && key_base1 != INT64_MAX;
-            int32_t raw = 0;
-            if (used || vol0_lane) {
+                    for (int k = 0; k < 4; ++k) e_w[k] = ew[1 + k];
+                }
+                // thread 255 also ranks the first key of volume 1 (= the blobs of volume 0): in the slot of its own component
+                // if that id is unused, as it nearly always is -- a second pass otherwise
+                const bool vol0_lane = tid == 255 && key_base1 != INT64_MAX;
+                const bool ranks = used || vol0_lane;
                 const uint32_t key32 = (uint32_t)(kp >> 32);
                 const int plane = used ? (int)(key32 >> 31) : 1;
                 const unsigned long long key = (unsigned long long)(plane ? key_base1 : 0) + (used ? (key32 & 0x7fffffffu) : 0u);
-                const int32_t rank = (int32_t)rank_of_key(lj, s_pre, key);
-                if (used) raw = lj.vol_sign[plane] > 0 ? 1 + rank : -1 - rank;
-                else s_vol0 = (uint32_t)rank;
-            }
-            if (vol0_lane && used) s_vol0 = rank_of_key(lj, s_pre, (unsigned long long)key_base1);   // (a tile with all 256 ids in use)
-            if (tid == 255 && key_base1 == INT64_MAX) s_vol0 = total_blobs;
-            s_lab[tid] = raw;
-            if (have) {   // (the accumulators were cleared in front of the table's barriers)
-                const uint32_t l = (uint32_t)e_head;
-                atomicAdd(&s_accn[l], (uint32_t)(e_head >> 32));
+                RankLoads rl;
+                if (UNDER) {
+                    // (every thread: one that has nothing to rank loads key 0's words and drops them -- a branch around the
+                    //  loads had the compiler copy loaded registers at its end, behind a wait, in front of the scan)
+                    rank_issue(lj, ranks ? key : 0ull, rl);
+                    total_blobs = rank_table_finish<NTL, true>(tl, s_pre, s_wave);   // (barriers that wait for LDS alone)
+                    rank_loads_hold(rl);
+                }
+                int32_t raw = 0;
+                if (ranks) {
+                    const int32_t rank = (int32_t)(UNDER ? rank_finish(s_pre, key, rl) : rank_of_key(lj, s_pre, key));
+                    if (used) raw = lj.vol_sign[plane] > 0 ? 1 + rank : -1 - rank;
+                    else s_vol0 = (uint32_t)rank;
+                }
+                if (vol0_lane && used) s_vol0 = rank_of_key(lj, s_pre, (unsigned long long)key_base1);   // (a tile with all 256 ids in use)
+                if (tid == 255 && key_base1 == INT64_MAX) s_vol0 = total_blobs;
+                s_lab[tid] = raw;
+                if (have) {   // (the accumulators were cleared in front of the table's barriers)
+                    const uint32_t l = (uint32_t)e_head;
+                    atomicAdd(&s_accn[l], (uint32_t)(e_head >> 32));
 #pragma unroll
-                for (int k = 0; k < 4; ++k) atomicAdd(&s_acc[k][l], e_w[k]);
-            }
-        } else {
-            unsigned long long e_head = 0ull, e_w[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
-            if (have) {
-                e_head = ew[0];
+                    for (int k = 0; k < 4; ++k) atomicAdd(&s_acc[k][l], e_w[k]);
+                }
+            } else {
+                unsigned long long e_head = 0ull, e_w[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+                if (have) {
+                    e_head = ew[0];
 #pragma unroll
-                for (int k = 0; k < 6; ++k) e_w[k] = ew[5 + k];
-            }
-            if (my_root) {
-                rec_n = lj.r_n[jd];
-                rec_f = fix_load(lj, jd);
-                rec_c = lj.r_c[jd]; rec_r = lj.r_r[jd]; rec_s = lj.r_s[jd];
-            }
-            if (have) {
-                const uint32_t l = (uint32_t)e_head;
+                    for (int k = 0; k < 6; ++k) e_w[k] = ew[5 + k];
+                }
+                if (my_root) {
+                    rec_n = lj.r_n[jd];
+                    rec_f = fix_load(lj, jd);
+                    rec_c = lj.r_c[jd]; rec_r = lj.r_r[jd]; rec_s = lj.r_s[jd];
+                }
+                if (UNDER) total_blobs = rank_table_finish<NTL, true>(tl, s_pre, s_wave);
+                if (have) {
+                    const uint32_t l = (uint32_t)e_head;
 #pragma unroll
-                for (int k = 0; k < 6; ++k) atomicAdd(&s_acc[4 + k][l], e_w[k]);
+                    for (int k = 0; k < 6; ++k) atomicAdd(&s_acc[4 + k][l], e_w[k]);
+                }
             }
         }
         /*@L2*/

@@ -31,9 +31,9 @@ if sys.argv[1] == "build":
     h = h.replace(anchor, "    (void)hipMemsetAsync(job.stamps, 0, 4096 * 16 * 8, ctx->stream);\n" + anchor)
     h += '''
 extern "C" int pdbeda_bloblist_stamps(pdbeda_bloblist *bl, unsigned long long *out, int64_t n) {
-    pdbeda_ctx *ctx = bl->ctx;
+    pdbeda_ctx *ctx = bl->job->ctx;   // (the lists are views of one job record)
     HIP_TRY(ctx, ctx_sync(ctx));
-    HIP_TRY(ctx, hipMemcpy(out, bl->job.stamps, 8 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out, bl->job->job.stamps, 8 * n, hipMemcpyDeviceToHost));
     return 0;
 }
 '''
