@@ -470,6 +470,49 @@ int pdbeda_atom_qscores(pdbeda_map *map,
                         int32_t *shell_n, double *shell_mean,      /* [n_scored][n_shells] */
                         uint8_t *valid, int64_t counters[2]);      /* any output may be NULL */
 
+/* ---- from the model to a map: calculated density, map-model sums ------------------------- */
+/* The density of a list of Gaussian atoms on the grid of a map (no reference counterpart: every other entry point reads observed
+ * maps; ChimeraX calls this molmap).  Atom a is n_terms Gaussians, rho_a(d) = sum_j amp[a][j] * exp(-expo[a][j] * d^2), cut off at
+ * radii[a].
+ * Output and domain: *out is a NEW map owned by the library on the geometry of `like` -- ownership and lifetime are those of
+ * pdbeda_map_combine's result (pdbeda_map_free).  Only the geometry of `like` is read, never its density.  The domain is ALL stored
+ * voxels ncrs, not just the non-repeating box: the result is a complete map for every call that takes one.  Nothing wraps:
+ * periodicity comes from the caller passing the symmetry images, as for pdbeda_map_partition.
+ * A pair: p = crs2xyzCoord(v) (ccp4.py:304-316); d2 = (dx*dx + dy*dy) + dz*dz in unfused fp64, as pdbeda_map_partition evaluates
+ * it; atom a contributes to voxel v iff sqrt(d2) <= (double)radii[a] (IEEE sqrt, inclusive) -- the sphere test of
+ * pdbeda_region_sums.
+ * A term: t = amp[a][j] * exp(-(expo[a][j] * d2)) with the device library's fp64 exp, one rounding for the product inside and one
+ * for the product outside.  Amplitudes may be negative (omit and difference use); expo >= 0 (0: a constant inside the sphere).
+ * Order independence: every term is rounded ONCE, half to even, to the quantum 2^-S and the terms of a voxel are added as 64-bit
+ * integers; a thread owns its voxel, so there is no atomic at all.  S is the largest integer <= 40 with n_gridded * A_max * 2^S <=
+ * 2^62, evaluated by the host in fp64: A_max = max over ALL atoms of sum_j |amp[a][j]| (added in index order), n_gridded = the atoms
+ * inside the xyz bounding box of the stored voxels grown by slightly more than the largest radius (all others reach nothing);
+ * S = 40 when A_max == 0 or no atom is gridded.  The voxel is float32((double)sum * 2^-S): one conversion, an exact scaling, one
+ * rounding to nearest.  A voxel that no atom reaches is exactly +0.0f.  The value of a pair does not depend on the tile, the staging
+ * run or the cell that meets it: two calls agree to the bit, and so do calls whose atom list is permuted.  Before the last
+ * rounding a voxel is within (terms of the voxel) * 2^-S / 2 plus the error of exp of the exact sum.
+ * counters = {S, the largest number of atoms a tile staged, the tiles that needed more than one staging run}.
+ * n_atoms == 0 succeeds: an all-zero map.  PDBEDA_ERR_ARGUMENT before any launch: n_terms outside 1 .. PDBEDA_MODEL_MAX_TERMS, a
+ * non-finite coordinate, amplitude or exponent, a negative exponent, a radius that is not finite or <= 0, n_atoms >= 2^31, a
+ * radius whose extent along a grid axis is 2^29 steps or more, amplitudes whose n_gridded * A_max is not finite.  Synchronous; a
+ * failing call leaves the context usable and *out untouched. */
+#define PDBEDA_MODEL_MAX_TERMS 6
+int pdbeda_model_density(pdbeda_map *like,
+                         const double *xyz, int64_t n_atoms,      /* the atoms that contribute: the symmetry atoms for a crystal */
+                         int32_t n_terms,                          /* Gaussians per atom, 1 .. PDBEDA_MODEL_MAX_TERMS */
+                         const double *amp, const double *expo,    /* [n_atoms][n_terms] */
+                         const float *radii,                       /* [n_atoms] cut-off distance of each atom */
+                         pdbeda_map **out, int64_t counters[3]);   /* counters may be NULL */
+
+/* The sums that correlate two maps of one grid shape: over the voxels of the non-repeating box header.uniqueNcrs (the domain of the
+ * whole-map lists) where both values are finite and (double)b > (double)b_floor (strict; -INFINITY keeps every finite pair), n and
+ * sums = {Sa, Sb, Saa, Sbb, Sab} in fp64, products unfused.  They give the correlation coefficient and the least-squares scale and
+ * offset of a against b.  The fold has a fixed order -- a number of workgroups fixed by the box, per-workgroup partials, one block
+ * over the partials in index order, as pdbeda_map_partition folds sum_sq --: the same maps give the same bits in every run.  An
+ * empty selection gives n = 0 and sums of exactly 0.  PDBEDA_ERR_ARGUMENT: maps of different shapes or contexts, a NaN b_floor.
+ * Synchronous; either output may be NULL. */
+int pdbeda_map_pair_moments(pdbeda_map *a, pdbeda_map *b, float b_floor, int64_t *n, double sums[5]);  /* Sa, Sb, Saa, Sbb, Sab */
+
 /* ---- aggregateCloud ------------------------------------------------------------------ */
 /* DensityAnalysis.aggregateCloud up to its statistics tail (densityAnalysis.py:571-731) as ONE call: the clouds of every
  * eligible atom (findAberrantBlobs, 603), the centroid-distance cut-off over all atoms (607), the best cloud and the pooled

@@ -122,6 +122,8 @@ _SIGS = {
     "pdbeda_map_partition": (C.c_int, [_p, _p, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pdbeda_interp_density": (C.c_int, [_p, _p, _i64, _p, _p]),
     "pdbeda_atom_qscores": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_float, C.c_int32, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p]),
+    "pdbeda_model_density": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, _p, C.POINTER(_p), _p]),
+    "pdbeda_map_pair_moments": (C.c_int, [_p, _p, C.c_float, C.POINTER(_i64), _p]),
     "pdbeda_aggregate_cloud": (C.c_int, [_p, C.POINTER(CloudAtoms), C.c_float, C.c_double, C.POINTER(_p)]),
     "pdbeda_cloud_counts": (C.c_int, [_p, _p, _p]),
     "pdbeda_cloud_atom_rows": (C.c_int, [_p, _p, _p, _p, _p, _p]),
@@ -576,6 +578,37 @@ class DeviceMap(object):
         a._ctx.check(a._ctx._lib.pdbeda_map_combine(a._h, b._h, C.c_double(alpha), C.byref(h)), "pdbeda_map_combine")
         self._h = h
         return self
+
+    @classmethod
+    def model_density(cls, like, xyz, amp, expo, radii):
+        """pdbeda_model_density: a new resident map on the geometry of ``like`` -- the density of the Gaussian atoms ``xyz`` (n x 3), each
+        ``amp[a][j] * exp(-expo[a][j] * d^2)`` summed over its terms and cut off at ``radii[a]``; ``amp`` / ``expo`` are (n,) or
+        (n, n_terms).  The map carries ``model_counters``: {"shift", "maxStaged", "multiRunTiles"}."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        na = len(xyz)
+        amp = np.ascontiguousarray(amp, dtype=np.float64).reshape(na, -1) if na else np.zeros((0, 1))      # (no atom: one term of nothing)
+        expo = np.ascontiguousarray(expo, dtype=np.float64).reshape(na, -1) if na else np.zeros((0, 1))
+        radii = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+        if amp.shape != expo.shape or len(radii) != na:
+            raise ValueError("amp and expo must have one shape, (n_atoms, n_terms), and radii one value per atom")
+        self = cls.__new__(cls)
+        self._ctx, self._geom, self._keep, self.unique_shape = like._ctx, like._geom, None, like.unique_shape
+        h = C.c_void_p()
+        ctr = np.zeros(3, dtype=np.int64)
+        like._ctx.check(like._ctx._lib.pdbeda_model_density(like._h, _ptr(xyz) if na else None, na, int(amp.shape[1]), _ptr(amp) if na else None, _ptr(expo) if na else None,
+                                                            _ptr(radii) if na else None, C.byref(h), _ptr(ctr)), "pdbeda_model_density")
+        self._h = h
+        self.model_counters = {"shift": int(ctr[0]), "maxStaged": int(ctr[1]), "multiRunTiles": int(ctr[2])}
+        return self
+
+    def pair_moments(self, other, floor=None):
+        """pdbeda_map_pair_moments: (n, [Sa, Sb, Saa, Sbb, Sab]) over the voxels of the unique box where this map (a) and ``other`` (b) are
+        finite and b > float32(floor) (strict; None: every finite pair)."""
+        n = C.c_int64(0)
+        sums = np.zeros(5, dtype=np.float64)
+        self._ctx.check(self._ctx._lib.pdbeda_map_pair_moments(self._h, other._h, C.c_float(-np.inf if floor is None else floor), C.byref(n), _ptr(sums)),
+                        "pdbeda_map_pair_moments")
+        return int(n.value), sums
 
     def abs_order_statistics(self, other, alpha, cut_a, cut_b, which, ranks=None):
         """Exact order statistics of |a| (which = 0) or |a + alpha * other| (which = 1) over the voxels of the unique box with

@@ -12,6 +12,7 @@ There is no CPU fallback: constructing a ``DensityMatrix`` without the HIP libra
 a GPU raises.
 """
 import collections.abc
+import math
 import os
 import sys
 
@@ -131,6 +132,29 @@ def qScoreTables(sigma=0.6, step=0.1, nShells=21, nPoints=8, nLevels=4):
     levels = [sphereLattice(int(nPoints) * 2 ** l) for l in range(int(nLevels))]
     offsets = np.concatenate([[0], np.cumsum([len(level) for level in levels])]).astype(np.int32)
     return ref, np.concatenate(levels), offsets
+
+
+MODEL_MIN_B = 10.0       # B' never falls below this: sigma = sqrt(B' / (8 pi^2)) >= 0.36 A, which a 0.5 .. 1 A grid still samples
+MODEL_N_SIGMA = 4.0      # the cut-off of an atom in sigmas: 0.11 % of its electrons lie beyond it, its last term is exp(-8) = 3.4e-4 of the peak
+
+
+def gaussianAtomTerms(electrons, bfactors, occupancies, blur=0.0, minB=MODEL_MIN_B):
+    """The single-Gaussian point-atom model that ``DensityMatrix.modelDensity`` takes: (amp, expo, bEff), (n,) float64 each.
+    B' = max(B + blur, minB); rho(d) = amp exp(-expo d^2) with amp = occ Z (4 pi / B')^(3/2) and expo = 4 pi^2 / B' -- the Fourier
+    transform of Z exp(-B' s^2 / 4), which integrates to occ Z electrons.  ``minB`` (default 10 A^2) keeps an atom wider than the grid:
+    below it the Gaussian (sigma < 0.36 A) falls between the voxels of a 0.5 - 1 A grid and the sum over voxels no longer finds its
+    electrons; ``blur`` adds to every B (a map sharpened or blurred by as much).  The kernel takes up to six terms per atom, so a caller
+    with form-factor tables passes its own (n, n_terms) arrays instead; none are shipped."""
+    z = np.asarray(electrons, dtype=np.float64).reshape(-1)
+    b = np.maximum(np.asarray(bfactors, dtype=np.float64).reshape(-1) + float(blur), float(minB))
+    occ = np.asarray(occupancies, dtype=np.float64).reshape(-1)
+    return occ * z * (4.0 * np.pi / b) ** 1.5, 4.0 * np.pi ** 2 / b, b
+
+
+def modelRadii(bEff, nSigma=MODEL_N_SIGMA):
+    """The cut-off radius of every atom of ``gaussianAtomTerms``: float32(nSigma sqrt(B' / (8 pi^2))), ``nSigma`` standard deviations of
+    its Gaussian (default 4: erfc(4 / sqrt 2) + sqrt(2 / pi) 4 exp(-8) = 0.11 % of the electrons lie outside)."""
+    return (float(nSigma) * np.sqrt(np.asarray(bEff, dtype=np.float64) / (8.0 * np.pi ** 2))).astype(np.float32)
 
 
 class DensityHeader(object):
@@ -464,6 +488,38 @@ class DensityMatrix(object):
         ref, unit, offsets = qScoreTables(sigma, step, nShells, nPoints, levels)
         xyz = np.asarray(xyzList, dtype=np.float64).reshape(-1, 3)
         return self._map.qscores(xyz, scored, step, ref, unit, offsets, nPoints)
+
+    # -- from the model to a map (no reference counterpart) ------------------------------
+    def modelDensity(self, xyz, amp, expo, radii):
+        """The calculated density of Gaussian atoms on THIS map's grid, as a device-made DensityMatrix (``pdbeda_model_density`` in
+        include/pdbeda.h has the contract): atom a adds sum_j amp[a][j] exp(-expo[a][j] d^2) to every stored voxel within radii[a] of
+        it.  ``amp`` / ``expo`` are (n,) or (n, n_terms <= 6) -- ``gaussianAtomTerms`` / ``modelRadii`` make the one-term model.
+        Nothing wraps: pass the symmetry atoms.  This map's density is not read.  ``modelCounters`` of the result: the shift S of the
+        integer sums, the most atoms a tile staged, the tiles that staged more than once."""
+        device_map = type(self._map).model_density(self._map, xyz, amp, expo, radii)
+        out = DensityMatrix.fromDeviceMap(self.header, self.origin, device_map, self.pdbid, self._ctx)
+        out.modelCounters = device_map.model_counters
+        return out
+
+    def pairMoments(self, other, floor=None):
+        """(n, Sa, Sb, Saa, Sbb, Sab) of this map (a) and ``other`` (b) over the voxels of the non-repeating box where both are finite
+        and b > floor (strict; None keeps every finite pair), in one device call with a fixed summation order
+        (``pdbeda_map_pair_moments``)."""
+        n, sums = self._map.pair_moments(other._map, floor)
+        return (n,) + tuple(float(v) for v in sums)
+
+    def correlate(self, other, floor=None):
+        """The correlation of this map with ``other`` over ``pairMoments``' voxels and the least-squares fit self ~ scale * other +
+        offset: a dict ``n``, ``cc``, ``scale``, ``offset``.  cc is NaN where either variance is zero (or n == 0), scale and offset
+        where ``other``'s is."""
+        n, sa, sb, saa, sbb, sab = self.pairMoments(other, floor)
+        nan = float("nan")
+        if n == 0:
+            return {"n": 0, "cc": nan, "scale": nan, "offset": nan}
+        va, vb, cov = saa - sa * sa / n, sbb - sb * sb / n, sab - sa * sb / n
+        scale = cov / vb if vb > 0 else nan
+        return {"n": n, "cc": min(1.0, max(-1.0, cov / math.sqrt(va * vb))) if va > 0 and vb > 0 else nan, "scale": scale,
+                "offset": (sa - scale * sb) / n if vb > 0 else nan}
 
     # -- whole-map blobs ------------------------------------------------------------
     def createFullBlobList(self, cutoff):

@@ -33,6 +33,7 @@
 #include "pdbeda_profiles.h"
 #include "pdbeda_partition.h"
 #include "pdbeda_qscore.h"
+#include "pdbeda_model.h"
 #include "pdbeda_blobshape.h"
 #include "pdbeda_blobnear.h"
 #include "pdbeda_basins.h"
@@ -3596,6 +3597,173 @@ extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_a
             if (parts[k].dst && parts[k].bytes) HIP_TRY(ctx, d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes));
         return 0;
     });
+}
+
+// ------------------------------------------------------------------------------------
+// From the model to a map: the density of Gaussian atoms, the sums that correlate two maps (no reference counterpart; the contracts: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// The shift of the model density's integer sums: the largest S <= 40 with n_gridded * a_max * 2^S <= 2^62 (fp64; ldexp is exact).
+static int model_shift(int64_t n_gridded, double a_max) {
+    const double prod = (double)n_gridded * a_max;
+    int S = 40;
+    if (!(prod > 0.0)) return S;
+    while (S > -1000 && ldexp(prod, S) > 0x1p62) --S;
+    return S;
+}
+
+// The launch graph: memset of the cell counts and the two counters; the atoms' coordinates, amplitudes, exponents and radii in one row of scratch;
+// k_grid_count_points / k_grid_scan / k_grid_scatter_indexed over the atoms inside the crop box -- the xyz bounding box of the STORED box grown by the
+// largest radius: an atom outside it reaches no voxel, and the grid never grows with atoms that lie far from the map --; k_model_tile, a workgroup per
+// tile of stored voxels, which writes the float32 voxels itself; the counters.  One wait.  The new map's arena is taken first and goes back to the pool
+// with the half-made map when anything fails: *out is written last.
+extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t n_atoms, int32_t n_terms, const double *amp, const double *expo, const float *radii,
+                                    pdbeda_map **out, int64_t counters[3]) {
+    if (!like || !out || n_atoms < 0 || (n_atoms > 0 && (!xyz || !amp || !expo || !radii))) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = like->ctx;
+    if (n_terms < 1 || n_terms > PDBEDA_MODEL_MAX_TERMS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: n_terms must be 1 .. %d", PDBEDA_MODEL_MAX_TERMS);
+    if (n_atoms >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: 2^31 atoms or more");
+    if (!all_finite(xyz, 3 * n_atoms)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: non-finite coordinate");
+    const int64_t n_pairs = n_atoms * n_terms;
+    if (!all_finite(amp, n_pairs) || !all_finite(expo, n_pairs)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: non-finite amplitude or exponent");
+    for (int64_t i = 0; i < n_pairs; ++i)
+        if (expo[i] < 0.0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the exponent of atom %lld is negative", (long long)(i / n_terms));
+    float r_top = 0.0f;
+    for (int64_t i = 0; i < n_atoms; ++i) {
+        if (!std::isfinite(radii[i]) || !(radii[i] > 0.0f)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the radius of atom %lld is not finite or <= 0", (long long)i);
+        r_top = std::max(r_top, radii[i]);
+    }
+    const Geom &g = like->geom;
+    const double r_max = n_atoms > 0 ? (double)r_top : 1.0;      // (no atom: any cell edge will do)
+    {   // (pdbeda_atom_qscores' rule for its largest shell)
+        const double limit = (double)(1ll << 29);
+        for (int i = 0; i < 3; ++i) {
+            const double per_unit = g.orthogonal ? 1.0 / std::fabs(g.grid_len[i])
+                                                 : (std::fabs(g.deortho[3 * i]) + std::fabs(g.deortho[3 * i + 1]) + std::fabs(g.deortho[3 * i + 2])) * (double)g.xyz_interval[i];
+            if (!(r_max * per_unit < limit)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the largest radius spans 2^29 grid steps or more");
+        }
+    }
+    const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
+    const int tiles_c = (nc + PT_C - 1) / PT_C, tiles_r = (nr + PT_R - 1) / PT_R, tiles_s = (ns + PT_S - 1) / PT_S;
+    const int64_t n_tiles = (int64_t)tiles_c * tiles_r * tiles_s;
+    if (like->n_vox <= 0 || n_tiles >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the map is empty or has 2^31 tiles or more");
+    // the crop box, and the grid over its intersection with the atoms' bounding box (pdbeda_map_partition's, over the stored box)
+    double crop_lo[3] = {INFINITY, INFINITY, INFINITY}, crop_hi[3] = {-INFINITY, -INFINITY, -INFINITY}, alo[3], ahi[3], glo[3], ghi[3];
+    for (int k = 0; k < 8; ++k) {
+        double p[3];
+        crs2xyz(g, (k & 1) ? nc - 1 : 0, (k & 2) ? nr - 1 : 0, (k & 4) ? ns - 1 : 0, p);
+        for (int q = 0; q < 3; ++q) { crop_lo[q] = std::min(crop_lo[q], p[q]); crop_hi[q] = std::max(crop_hi[q], p[q]); }
+    }
+    bbox3(xyz, n_atoms, alo, ahi);
+    bool empty = n_atoms == 0;
+    for (int q = 0; q < 3; ++q) {
+        const double pad = r_max * (1.0 + 1e-5) + 1e-8 * (std::fabs(crop_lo[q]) + std::fabs(crop_hi[q]) + 1.0);      // (wider than a tile's own margin)
+        crop_lo[q] -= pad; crop_hi[q] += pad;
+        glo[q] = std::max(crop_lo[q], alo[q]); ghi[q] = std::min(crop_hi[q], ahi[q]);
+        if (!(glo[q] <= ghi[q])) empty = true;
+    }
+    if (empty)
+        for (int q = 0; q < 3; ++q) glo[q] = ghi[q] = crop_lo[q];      // (one cell, and no atom in it)
+    // S: from the atoms the grid will hold (grid_cropped's comparisons, on the host) and the largest sum of |amplitudes| of ANY atom
+    int64_t n_gridded = 0;
+    double a_max = 0.0;
+    for (int64_t i = 0; i < n_atoms; ++i) {
+        const double *p = xyz + 3 * i;
+        if (p[0] >= crop_lo[0] && p[0] <= crop_hi[0] && p[1] >= crop_lo[1] && p[1] <= crop_hi[1] && p[2] >= crop_lo[2] && p[2] <= crop_hi[2]) ++n_gridded;
+        double t = 0.0;
+        for (int j = 0; j < n_terms; ++j) t += std::fabs(amp[i * n_terms + j]);
+        a_max = std::max(a_max, t);
+    }
+    if (!std::isfinite((double)std::max<int64_t>(n_gridded, 1) * a_max)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the amplitudes of an atom add up beyond fp64");
+    const int S = model_shift(n_gridded, a_max);
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const CellGrid grid = make_cell_grid(glo, ghi, r_max, n_atoms, crop_lo, crop_hi);
+    const int64_t cells = grid.n_cells;
+    const size_t na = (size_t)n_atoms, np = (size_t)n_pairs;
+
+    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
+    m->ctx = ctx;
+    m->geom = like->geom;
+    m->n_vox = like->n_vox;
+    float *d_out = nullptr;
+    if (int rc = arena_carve(ctx, "model density", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d_out, (size_t)m->n_vox); })) return rc;
+    double *d_xyz = nullptr, *d_amp = nullptr, *d_expo = nullptr, *d_sorted = nullptr;
+    float *d_radii = nullptr;
+    unsigned *d_count = nullptr, *d_cursor = nullptr, *d_start = nullptr;
+    int *d_sidx = nullptr;
+    unsigned long long *d_ctr = nullptr;
+    int64_t seen[2] = {0, 0};
+    const int rc = with_scratch(ctx, "model density", [&](Carver &cv) {
+        cv.take(d_xyz, 3 * na);
+        cv.take(d_amp, np);
+        cv.take(d_expo, np);
+        cv.take(d_radii, na);
+        cv.take(d_count, cells);
+        cv.take(d_cursor, cells);
+        cv.take(d_start, cells + 1);
+        cv.take(d_sorted, 3 * na);
+        cv.take(d_sidx, na);
+        cv.take(d_ctr, 2);
+    }, [&]() -> int {
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 4 * (size_t)cells, st));
+        HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, 16, st));
+        HIP_TRY(ctx, h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom)));
+        if (n_atoms > 0) {
+            const H2DItem in[4] = {{d_xyz, xyz, 24 * na}, {d_amp, amp, 8 * np}, {d_expo, expo, 8 * np}, {d_radii, radii, 4 * na}};
+            HIP_TRY(ctx, h2d_row(ctx, in, 4));
+        }
+        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_atoms, 256)), dim3(256), 0, st, d_xyz, n_atoms, grid, d_count); }
+        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count, (int)cells, d_start, d_cursor, nullptr); }
+        { PROF(ctx, "k_grid_scatter_indexed"); hipLaunchKernelGGL(k_grid_scatter_indexed, dim3(grid_for(n_atoms, 256)), dim3(256), 0, st, d_xyz, n_atoms, grid, d_cursor, d_sorted, d_sidx, n_atoms); }
+        ModelArgs a;
+        a.geom = m->geom_dev; a.tiles_c = tiles_c; a.tiles_r = tiles_r;
+        a.grid = grid; a.sorted = d_sorted; a.sorted_index = d_sidx; a.start = d_start;
+        a.amp = d_amp; a.expo = d_expo; a.radii = d_radii; a.n_terms = n_terms;
+        a.r_max = r_max; a.fix_mul = ldexp(1.0, S); a.fix_inv = ldexp(1.0, -S);
+        a.out = d_out; a.counters = d_ctr;
+        { PROF(ctx, "k_model_tile"); hipLaunchKernelGGL(k_model_tile, dim3((unsigned)n_tiles), dim3(256), 0, st, a); }
+        HIP_TRY(ctx, hipGetLastError());
+        if (counters) HIP_TRY(ctx, d2h(ctx, seen, d_ctr, 16));
+        return 0;
+    });
+    if (rc) return rc;
+    if (counters) { counters[0] = S; counters[1] = seen[0]; counters[2] = seen[1]; }
+    m->dens = d_out;
+    m->own_dens = true;
+    ctx->live_handles++;
+    *out = m.release();
+    return PDBEDA_OK;
+}
+
+// The launch graph: k_pair_moments over a number of workgroups fixed by the box, k_pair_moments_fold, the six results.  One wait.
+extern "C" int pdbeda_map_pair_moments(pdbeda_map *a, pdbeda_map *b, float b_floor, int64_t *n, double sums[5]) {
+    if (!a || !b) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = a->ctx;
+    if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts");
+    if (a->n_vox != b->n_vox || memcmp(a->geom.ncrs, b->geom.ncrs, sizeof a->geom.ncrs) != 0 || memcmp(a->geom.unique_ncrs, b->geom.unique_ncrs, sizeof a->geom.unique_ncrs) != 0)
+        return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different shapes");
+    if (std::isnan(b_floor)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "pair moments: the floor is NaN");
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    const Geom &g = a->geom;
+    const int uc = g.unique_ncrs[0], ur = g.unique_ncrs[1], us = g.unique_ncrs[2];
+    const int64_t nbox = (int64_t)uc * ur * us;
+    if (nbox <= 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "pair moments: the box is empty");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const unsigned blocks = grid_for(nbox, 256, PM_BLOCKS);
+    double *d_part = nullptr, *d_res = nullptr;
+    double res[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int rc = with_scratch(ctx, "pair moments", [&](Carver &cv) { cv.take(d_part, 6 * (size_t)blocks); cv.take(d_res, 6); }, [&]() -> int {
+        { PROF(ctx, "k_pair_moments"); hipLaunchKernelGGL(k_pair_moments, dim3(blocks), dim3(256), 0, ctx->stream, a->dens, b->dens, g.ncrs[0], g.ncrs[1], uc, ur, us, (double)b_floor, d_part); }
+        { PROF(ctx, "k_pair_moments_fold"); hipLaunchKernelGGL(k_pair_moments_fold, dim3(1), dim3(256), 0, ctx->stream, d_part, (int)blocks, d_res); }
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, d2h(ctx, res, d_res, 48));
+        return 0;
+    });
+    if (rc) return rc;
+    if (n) *n = (int64_t)res[0];
+    if (sums) memcpy(sums, res + 1, 40);
+    return PDBEDA_OK;
 }
 
 // ------------------------------------------------------------------------------------

@@ -35,6 +35,10 @@ atomTypeLengthGlobal = None
 ccp4folder = './ccp4_data/'
 pdbfolder = './pdb_data/'
 
+# the calculated (model) density: added to every B-factor (A^2), and the cut-off of an atom in standard deviations of its Gaussian
+modelBlur = 0.0
+modelSigmas = ccp4.MODEL_N_SIGMA
+
 
 def setGlobals(params):
     """ref densityAnalysis.py:48-68."""
@@ -416,6 +420,8 @@ class DensityAnalysis(object):
     atomTypeRadialProfileHeader = ['atom_type', 'num_atoms', 'optimized_radius', 'shell_outer_radius', 'median_cumulative_density_per_electron', 'profile_radius']
     atomQScoreHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'valid', 'q_score', 'n_points']
     residueQScoreHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'mean_q_score', 'min_q_score', 'num_atoms_scored']
+    atomModelCorrelationHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'rscc_model', 'rsr_model']
+    residueModelCorrelationHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'rscc_model', 'rsr_model']
 
     def __init__(self, pdbid, densityObj=None, diffDensityObj=None, biopdbObj=None, pdbObj=None):
         self.pdbid = pdbid
@@ -432,6 +438,8 @@ class DensityAnalysis(object):
         self._greenBlobList = None
         self._partitions = {}
         self._qScores = None
+        self._model = None
+        self._modelDifference = None
         self._redBlobList = None
         self._blueBlobList = None
         self._greenPeakList = None
@@ -1072,6 +1080,10 @@ class DensityAnalysis(object):
         """RSCC and RSR of every group of coordinates: ONE sphere batch (all voxels of the sphere union, de-duplicated on the
         raw crs like the reference's set), two gathers (2Fo-Fc and Fo-Fc values under the wrap contract), then segmented
         float64 sums.  Pearson r as scipy.stats.pearsonr computes it (centre, normalise, dot, clip)."""
+        return self._groupCorrelations(groups, radius, lambda crs, fo: fo - self.diffDensityObj._map.point_density(crs) * 2)
+
+    def _groupCorrelations(self, groups, radius, calculated):
+        """``_rsccRsr`` for any calculated map: ``calculated(crs, fo)`` gives its values at the gathered voxels."""
         xyz = np.array([c for g in groups for c in g], dtype=np.float64).reshape(-1, 3)
         off = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)
         bl = self.densityObj._map.sphere_blobs(xyz, np.full(len(xyz), radius, dtype=np.float32), off, 0.0)
@@ -1081,7 +1093,7 @@ class DensityAnalysis(object):
         order = np.argsort(vgroup, kind="stable")
         crs, vgroup = crs[order], vgroup[order]
         fo = self.densityObj._map.point_density(crs)
-        fc = fo - self.diffDensityObj._map.point_density(crs) * 2
+        fc = calculated(crs, fo)
         n_groups = len(groups)
         cnt = np.bincount(vgroup, minlength=n_groups).astype(np.int64)
         start = np.concatenate([[0], np.cumsum(cnt)])[:-1]
@@ -1515,3 +1527,85 @@ class DensityAnalysis(object):
             out[name + "_median_q_score"] = float(np.median(mine)) if len(mine) else None
             out[name + "_num_atoms"] = int(len(mine))
         return out
+
+    # ---- the calculated density of the model and its agreement with the 2Fo-Fc map (no reference counterpart) ----
+    def _modelAtoms(self):
+        """What ``modelDensityObj`` is made from: (xyz, amp, expo, radii, electrons placed) of ALL symmetry atoms whose 'RES_ATOM' name has
+        electrons in the parameter tables and whose occupancy is not 0 (the atoms ``aggregateCloud`` would not skip), under the
+        single-Gaussian model of ``ccp4.gaussianAtomTerms`` with the module's ``modelBlur`` and ``modelSigmas``."""
+        _requireParams()
+        coords = np.asarray(self.symmetryAtomCoords, dtype=np.float64).reshape(-1, 3)
+        cols = _structure.columns(self.biopdbObj)
+        rows = self.symmetryAtoms._idx
+        names = cols.pair_names
+        electrons = _pairTables(names, max(len(names), 1))["electrons"][cols.pair_of_atom[rows]] if len(rows) else np.zeros(0)
+        occupancy = cols.occupancy[rows] if len(rows) else np.zeros(0)
+        keep = ~np.isnan(electrons) & (occupancy != 0)
+        amp, expo, bEff = ccp4.gaussianAtomTerms(electrons[keep], cols.bfactor[rows][keep] if len(rows) else np.zeros(0), occupancy[keep], blur=modelBlur)
+        return coords[keep], amp, expo, ccp4.modelRadii(bEff, modelSigmas), float(np.sum(electrons[keep] * occupancy[keep]))
+
+    @property
+    def modelDensityObj(self):
+        """The calculated density of the model on the grid of the 2Fo-Fc map, in electrons per A^3, made on the device on first use
+        (``DensityMatrix.modelDensity``).  It never leaves HBM unless somebody reads ``.density``."""
+        if self._model is None:
+            xyz, amp, expo, radii, placed = self._modelAtoms()
+            self._model = (self.densityObj.modelDensity(xyz, amp, expo, radii), placed)
+        return self._model[0]
+
+    def modelCorrelation(self, floor=None):
+        """``densityObj.correlate(modelDensityObj, floor)``: n, cc, and the scale and offset of 2Fo-Fc ~ scale * model + offset over the
+        voxels of the non-repeating box (with ``floor``: only where the model exceeds it -- the part of the map the model says is
+        occupied)."""
+        return self.densityObj.correlate(self.modelDensityObj, floor)
+
+    @property
+    def modelDifferenceObj(self):
+        """2Fo-Fc - scale * model on the device (``pdbeda_map_combine``), scale from ``modelCorrelation()``: an observed-minus-model map that
+        ``createFullBlobList`` / ``findPeaks`` and everything behind them take as it is.  Leave a ligand out of the structure and this
+        is its omit map."""
+        if self._modelDifference is None:
+            d, model = self.densityObj, self.modelDensityObj
+            scale = self.modelCorrelation()["scale"]
+            if scale != scale:
+                raise RuntimeError("the model density is constant over the map: there is no scale to subtract it with")
+            self._modelDifference = ccp4.DensityMatrix.fromDeviceMap(d.header, d.origin, type(d._map).combine(d._map, model._map, -scale), d.pdbid, d._ctx)
+        return self._modelDifference
+
+    def _modelRsccRsr(self, groups, radius):
+        """``_rsccRsr`` against the calculated map: the model's density at the gathered voxels, brought to the observed map's scale by the
+        whole-map fit of ``modelCorrelation()`` (RSR compares magnitudes; RSCC does not see the fit)."""
+        fit = self.modelCorrelation()
+        model = self.modelDensityObj._map
+        return self._groupCorrelations(groups, radius, lambda crs, fo: model.point_density(crs) * fit["scale"] + fit["offset"])
+
+    def calculateAtomModelCorrelations(self, radius=None):
+        """One row per atom (``atomModelCorrelationHeader``; the atoms and leading columns of ``calculateAtomRegionDensity``): RSCC and RSR
+        of the 2Fo-Fc map against the calculated map over the sphere of ``radius`` around the atom (None: the resolution-dependent
+        radius of ``atomMetrics``) -- ``atomMetrics`` with a calculated map that comes from the atoms instead of from the two observed
+        maps.  None where a value is undefined."""
+        cols, pick, lead = self._atomPick("")
+        radius = self._metricsRadius() if radius is None else radius
+        rscc, rsr = self._modelRsccRsr([[c] for c in cols.coord[pick]], radius)
+        clean = lambda v: [None if x != x else x for x in v.tolist()]
+        return self._rows(*lead, cols.bfactor[pick], clean(rscc), clean(rsr))
+
+    def calculateResidueModelCorrelations(self, radius=None):
+        """One row per residue (``residueModelCorrelationHeader``; the leading columns of ``calculateResidueRegionDiscrepancies``): RSCC and
+        RSR of the 2Fo-Fc map against the calculated map over the de-duplicated union of the spheres of its atoms."""
+        cols, lead, atom_rows, off = self._residuePick("", None, False)
+        radius = self._metricsRadius() if radius is None else radius
+        coord = cols.coord[atom_rows]
+        rscc, rsr = self._modelRsccRsr([coord[off[k]:off[k + 1]] for k in range(len(off) - 1)], radius)
+        clean = lambda v: [None if x != x else x for x in v.tolist()]
+        return self._rows(*lead, clean(rscc), clean(rsr))
+
+    def modelSummary(self):
+        """The whole-map agreement of the model: ``cc``, ``scale``, ``offset`` and ``n`` of ``modelCorrelation()``, ``electrons_placed`` (sum
+        of occupancy * Z over the symmetry atoms the map was made from) and ``electrons_found`` (sum of the calculated map over the
+        non-repeating box times the voxel volume: the electrons that landed inside the box, less what the cut-off radius drops)."""
+        model = self.modelDensityObj
+        fit = self.modelCorrelation()
+        total = model.pairMoments(model)[1]
+        return {"cc": fit["cc"], "scale": fit["scale"], "offset": fit["offset"], "n": fit["n"], "electrons_placed": self._model[1],
+                "electrons_found": total * self.densityObj.header.unitVolume}
