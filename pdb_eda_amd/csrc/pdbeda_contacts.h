@@ -1,49 +1,12 @@
-// Crystal contacts (crystalContacts.py of the reference) without pymol: a uniform cell grid over a point set (counting sort), the
-// symmetry images of the asymmetric unit's polymer atoms that come within the cutoff of it, and the minimum distance of every query
-// point to the atoms of the kept images.  Included from pdbeda_hip.hip.  All coordinates and distances are fp64;
-// a distance is scipy cdist's sqrt((dx*dx + dy*dy) + dz*dz) (the library builds with -ffp-contract=off), as k_nearest_atom computes it.
+// Crystal contacts (crystalContacts.py of the reference) without pymol: the counting sort of a point set into a uniform cell grid (pdbeda_cellgrid.h:
+// count, scan, scatter -- the sort of every atom-grid entry point), the symmetry images of the asymmetric unit's polymer atoms that come within the
+// cutoff of it, and the minimum distance of every query point to the atoms of the kept images.  Included from pdbeda_hip.hip.  All coordinates and
+// distances are fp64; a distance is scipy cdist's sqrt((dx*dx + dy*dy) + dz*dz) (the library builds with -ffp-contract=off), as k_nearest_atom computes it.
 #pragma once
 #include "pdbeda_kernels.h"
+#include "pdbeda_cellgrid.h"
 
 namespace pdbeda {
-
-// A uniform grid: cell (cx, cy, cz) = floor((x - lo) / edge) per axis, cell number (cz * dim[1] + cy) * dim[0] + cx.  edge > cutoff
-// (strictly, with a relative margin far above the rounding of the division): two points within the cutoff of each other lie in the same
-// or in adjacent cells, so the 27 cells around a point hold every point within the cutoff of it.  Points that lie outside the crop box
-// are not gridded (the box is the query set's bounding box grown by more than the cutoff: no such point can be within the cutoff of a
-// query); points inside it whose cell falls outside [0, dim) by rounding are clamped to the border cell, which keeps adjacent cells adjacent.
-struct CellGrid {
-    double lo[3];
-    double edge;
-    double crop_lo[3], crop_hi[3];
-    int dim[3];
-    int n_cells;
-};
-
-__device__ inline bool grid_cropped(const CellGrid &g, const double v[3]) {
-    return !(v[0] >= g.crop_lo[0] && v[0] <= g.crop_hi[0] && v[1] >= g.crop_lo[1] && v[1] <= g.crop_hi[1] && v[2] >= g.crop_lo[2] && v[2] <= g.crop_hi[2]);
-}
-
-__device__ inline int grid_cell(const CellGrid &g, const double v[3]) {
-    int c[3];
-    for (int q = 0; q < 3; ++q) {
-        const double f = floor((v[q] - g.lo[q]) / g.edge);
-        c[q] = f < 0.0 ? 0 : (f > (double)(g.dim[q] - 1) ? g.dim[q] - 1 : (int)f);
-    }
-    return (c[2] * g.dim[1] + c[1]) * g.dim[0] + c[0];
-}
-
-// The cells a point at v has to search: its own cell +- 1 per axis, inside the grid.  False when no gridded point can be within the cutoff.
-__device__ inline bool grid_range(const CellGrid &g, const double v[3], int lo[3], int hi[3]) {
-    for (int q = 0; q < 3; ++q) {
-        const double f = floor((v[q] - g.lo[q]) / g.edge);
-        if (!(f >= -1.0 && f <= (double)g.dim[q])) return false;
-        const int c = (int)f;
-        lo[q] = c - 1 < 0 ? 0 : c - 1;
-        hi[q] = c + 1 > g.dim[q] - 1 ? g.dim[q] - 1 : c + 1;
-    }
-    return true;
-}
 
 __device__ inline double contact_dist(const double a[3], const double *__restrict__ b) {
     const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
@@ -73,15 +36,23 @@ __global__ void __launch_bounds__(256) k_grid_count_points(const double *__restr
     }
 }
 
-// Within a cell the order of the points depends on the atomics; a minimum distance does not.  `room` bounds every write.
-__global__ void __launch_bounds__(256) k_grid_scatter_points(const double *__restrict__ xyz, int64_t n, CellGrid g, unsigned *__restrict__ cursor,
-                                                             double *__restrict__ sorted, int64_t room) {
+// Within a cell the order of the points depends on the atomics; a minimum distance does not.  `room` bounds every write.  INDEXED: each point's
+// ORIGINAL index goes with it (a tie rule by atom index needs it, and so do per-atom rows).  Two kernel names over one body: profiles key on them.
+template <bool INDEXED>
+__device__ inline void grid_scatter(const double *__restrict__ xyz, int64_t n, const CellGrid &g, unsigned *__restrict__ cursor, double *__restrict__ sorted, int *__restrict__ sorted_index, int64_t room) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const double v[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
         if (grid_cropped(g, v)) continue;
         const unsigned pos = atomicAdd(&cursor[grid_cell(g, v)], 1u);
-        if ((int64_t)pos < room) { sorted[3 * pos] = v[0]; sorted[3 * pos + 1] = v[1]; sorted[3 * pos + 2] = v[2]; }
+        if ((int64_t)pos < room) { sorted[3 * pos] = v[0]; sorted[3 * pos + 1] = v[1]; sorted[3 * pos + 2] = v[2]; if (INDEXED) sorted_index[pos] = (int)i; }
     }
+}
+__global__ void __launch_bounds__(256) k_grid_scatter_points(const double *__restrict__ xyz, int64_t n, CellGrid g, unsigned *__restrict__ cursor, double *__restrict__ sorted, int64_t room) {
+    grid_scatter<false>(xyz, n, g, cursor, sorted, nullptr, room);
+}
+__global__ void __launch_bounds__(256) k_grid_scatter_indexed(const double *__restrict__ xyz, int64_t n, CellGrid g, unsigned *__restrict__ cursor, double *__restrict__ sorted,
+                                                              int *__restrict__ sorted_index, int64_t room) {
+    grid_scatter<true>(xyz, n, g, cursor, sorted, sorted_index, room);
 }
 
 // Inclusive scan of one value per lane across a 1024-lane block; `total` gets the block's sum.
@@ -143,12 +114,11 @@ __global__ void __launch_bounds__(256) k_image_select(const double *__restrict__
         int lo[3], hi[3];
         if (!grid_range(g, v, lo, hi)) continue;
         bool hit = false;
-        for (int z = lo[2]; z <= hi[2] && !hit; ++z)
-            for (int y = lo[1]; y <= hi[1] && !hit; ++y) {
-                const int row = (z * g.dim[1] + y) * g.dim[0];
-                for (unsigned k = start[row + lo[0]]; k < start[row + hi[0] + 1]; ++k)      // (cells lo[0]..hi[0] of a row are consecutive)
-                    if (contact_dist(v, sorted + 3 * k) <= cutoff) { hit = true; break; }
-            }
+        for_each_cell_row(g, start, lo, hi, [&](unsigned b, unsigned e) {
+            for (unsigned k = b; k < e; ++k)
+                if (contact_dist(v, sorted + 3 * k) <= cutoff) { hit = true; break; }
+            return hit;
+        });
         if (hit) keep[c] = 1u;
     }
 }
@@ -210,11 +180,10 @@ __global__ void __launch_bounds__(256) k_contact_min(const double *__restrict__ 
         double best = INFINITY;
         int lo[3], hi[3];
         if (grid_range(g, v, lo, hi))
-            for (int z = lo[2]; z <= hi[2]; ++z)
-                for (int y = lo[1]; y <= hi[1]; ++y) {
-                    const int row = (z * g.dim[1] + y) * g.dim[0];
-                    for (unsigned k = start[row + lo[0]]; k < start[row + hi[0] + 1]; ++k) best = fmin(best, contact_dist(v, sorted + 3 * k));
-                }
+            for_each_cell_row(g, start, lo, hi, [&](unsigned b, unsigned e) {
+                for (unsigned k = b; k < e; ++k) best = fmin(best, contact_dist(v, sorted + 3 * k));
+                return false;
+            });
         dist[i] = best;
     }
 }

@@ -3093,42 +3093,39 @@ static bool all_finite(const double *v, int64_t n) {
     return true;
 }
 
-static void bbox3(const double *xyz, int64_t n, double lo[3], double hi[3]) {
-    for (int q = 0; q < 3; ++q) { lo[q] = INFINITY; hi[q] = -INFINITY; }
-    for (int64_t i = 0; i < n; ++i)
-        for (int q = 0; q < 3; ++q) { lo[q] = std::min(lo[q], xyz[3 * i + q]); hi[q] = std::max(hi[q], xyz[3 * i + q]); }
-}
-
-// Grid over the box [lo, hi] (pdbeda_contacts.h): edge just above the cutoff, enlarged until the cells number at most 8 per point (at least
-// 4096, at most 2^22: the single-block scan stays short).  Correctness only needs edge > cutoff.
-static CellGrid make_cell_grid(const double lo[3], const double hi[3], double cutoff, int64_t n_points, const double crop_lo[3], const double crop_hi[3]) {
-    const double cap = (double)std::min<int64_t>(1 << 22, std::max<int64_t>(4096, 8 * n_points));
-    double edge = cutoff * (1.0 + 1e-6);
-    for (;;) {
-        double cells = 1.0;
-        for (int q = 0; q < 3; ++q) cells *= std::floor((hi[q] - lo[q]) / edge) + 1.0;
-        if (cells <= cap) break;
-        edge *= 1.25;
+// The device side of one cell grid (the host plans it: pdbeda_cellgrid.h): the arrays of its counting sort in a carve, and the sort itself.  The counts are
+// carved apart from the rest where a call zeroes them with zeros that ride in its one input copy, in a row with those inputs.  sorted_index: when kept.
+struct GridBuild {
+    unsigned *count = nullptr, *cursor = nullptr, *start = nullptr;
+    double *sorted = nullptr;
+    int *sorted_index = nullptr;
+    void carve_counts(Carver &cv, int64_t cells) { cv.take(count, cells); }
+    void carve_rest(Carver &cv, int64_t cells, int64_t n_points, bool indexed) {
+        cv.take(cursor, cells); cv.take(start, cells + 1); cv.take(sorted, 3 * n_points);
+        if (indexed) cv.take(sorted_index, n_points);
     }
-    CellGrid g;
-    g.edge = edge;
-    g.n_cells = 1;
-    for (int q = 0; q < 3; ++q) {
-        g.lo[q] = lo[q];
-        g.dim[q] = (int)std::floor((hi[q] - lo[q]) / edge) + 1;
-        g.n_cells *= g.dim[q];
-        g.crop_lo[q] = crop_lo[q];
-        g.crop_hi[q] = crop_hi[q];
+    void carve(Carver &cv, int64_t cells, int64_t n_points, bool indexed) { carve_counts(cv, cells); carve_rest(cv, cells, n_points, indexed); }
+    void scan(pdbeda_ctx *ctx, const CellGrid &g, unsigned *total_out) const {      // (the total also into the pinned block when given)
+        PROF(ctx, "k_grid_scan");
+        hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, ctx->stream, count, g.n_cells, start, cursor, total_out);
     }
-    return g;
-}
+    void sort_points(pdbeda_ctx *ctx, const CellGrid &g, const double *d_xyz, int64_t n) const {
+        hipStream_t st = ctx->stream;
+        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n, 256)), dim3(256), 0, st, d_xyz, n, g, count); }
+        scan(ctx, g, nullptr);
+        if (sorted_index) { PROF(ctx, "k_grid_scatter_indexed"); hipLaunchKernelGGL(k_grid_scatter_indexed, dim3(grid_for(n, 256)), dim3(256), 0, st, d_xyz, n, g, cursor, sorted, sorted_index, n); }
+        else { PROF(ctx, "k_grid_scatter_points"); hipLaunchKernelGGL(k_grid_scatter_points, dim3(grid_for(n, 256)), dim3(256), 0, st, d_xyz, n, g, cursor, sorted, n); }
+    }
+};
 
-// The grid a query set searches: its bounding box grown by twice the cutoff, which is also the crop box of the points gridded into it.
-static CellGrid query_grid(const double *q_xyz, int64_t n_q, double cutoff, int64_t n_points) {
+// The contacts entry points accept any finite coordinate, so the extent of a point set may overflow fp64: such a box has no grid (make_cell_grid).
+static int refuse_extent(pdbeda_ctx *ctx, const char *set, const double lo[3], const double hi[3]) {
+    const int q = std::max(bad_extent(lo, hi), 0);
+    return fail(ctx, PDBEDA_ERR_ARGUMENT, "the extent of the %s along %c, %g .. %g, overflows fp64: no cell grid can be laid over it", set, "xyz"[q], lo[q], hi[q]);
+}
+static int contacts_query_grid(pdbeda_ctx *ctx, const double *q_xyz, int64_t n_q, double cutoff, int64_t n_points, CellGrid *out) {
     double lo[3], hi[3];
-    bbox3(q_xyz, n_q, lo, hi);
-    for (int q = 0; q < 3; ++q) { lo[q] -= 2 * cutoff; hi[q] += 2 * cutoff; }
-    return make_cell_grid(lo, hi, cutoff, n_points, lo, hi);
+    return query_grid(q_xyz, n_q, cutoff, n_points, out, lo, hi) ? PDBEDA_OK : refuse_extent(ctx, "query points (grown by twice the cutoff)", lo, hi);
 }
 
 static int check_images(pdbeda_ctx *ctx, const double *rot, int32_t n_ops, const double *ortho, const int32_t *cand, int64_t n_cand) {
@@ -3178,20 +3175,18 @@ extern "C" int pdbeda_coord_contacts(pdbeda_ctx *ctx, const double *q_xyz, int64
     if (int rc = check_contacts_args(ctx, q_xyz, n_q, p_xyz, n_p, cutoff, out_index, out_distance, cap)) return rc;
     if (n_q == 0 || n_p == 0) return PDBEDA_OK;      // nothing to be near to: no rows (cdist + np.min would raise on an empty list)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const CellGrid g = query_grid(q_xyz, n_q, cutoff, n_q + n_p);
+    CellGrid g;
+    if (int rc = contacts_query_grid(ctx, q_xyz, n_q, cutoff, n_q + n_p, &g)) return rc;
     const int64_t cells = g.n_cells;
     std::vector<unsigned> zeros((size_t)cells, 0u);
     int64_t total = 0;
-    double *d_q = nullptr, *d_p = nullptr, *d_sorted = nullptr, *d_dist = nullptr, *d_odist = nullptr;
-    unsigned *d_count = nullptr, *d_start = nullptr, *d_cursor = nullptr;
+    double *d_q = nullptr, *d_p = nullptr, *d_dist = nullptr, *d_odist = nullptr;
+    GridBuild gb;
     int64_t *d_idx = nullptr, *d_nout = nullptr;
     int rc = with_scratch(ctx, "coord contacts", [&](Carver &cv) {
         cv.take(d_q, 3 * n_q);
         cv.take(d_p, 3 * n_p);
-        cv.take(d_count, cells);
-        cv.take(d_sorted, 3 * n_p);
-        cv.take(d_start, cells + 1);
-        cv.take(d_cursor, cells);
+        gb.carve(cv, cells, n_p, false);
         cv.take(d_dist, n_q);
         cv.take(d_idx, n_q);
         cv.take(d_odist, n_q);
@@ -3199,14 +3194,12 @@ extern "C" int pdbeda_coord_contacts(pdbeda_ctx *ctx, const double *q_xyz, int64
     }, [&]() -> int {
         hipStream_t st = ctx->stream;
         {
-            const H2DItem in[3] = {{d_q, q_xyz, (size_t)(24 * n_q)}, {d_p, p_xyz, (size_t)(24 * n_p)}, {d_count, zeros.data(), (size_t)(4 * cells)}};
+            const H2DItem in[3] = {{d_q, q_xyz, (size_t)(24 * n_q)}, {d_p, p_xyz, (size_t)(24 * n_p)}, {gb.count, zeros.data(), (size_t)(4 * cells)}};
             // ONE copy whenever the pinned block holds it beside the rows (else one per item); the cell counts start from the zeros that ride in it
             HIP_TRY(ctx, h2d_row(ctx, in, 3, pinned_room_beside(ctx, 16 * (size_t)n_q + 64)));
         }
-        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_p, 256)), dim3(256), 0, st, d_p, n_p, g, d_count); }
-        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count, (int)cells, d_start, d_cursor, nullptr); }
-        { PROF(ctx, "k_grid_scatter_points"); hipLaunchKernelGGL(k_grid_scatter_points, dim3(grid_for(n_p, 256)), dim3(256), 0, st, d_p, n_p, g, d_cursor, d_sorted, n_p); }
-        { PROF(ctx, "k_contact_min"); hipLaunchKernelGGL(k_contact_min, dim3(grid_for(n_q, 256)), dim3(256), 0, st, d_q, n_q, d_sorted, d_start, g, d_dist); }
+        gb.sort_points(ctx, g, d_p, n_p);
+        { PROF(ctx, "k_contact_min"); hipLaunchKernelGGL(k_contact_min, dim3(grid_for(n_q, 256)), dim3(256), 0, st, d_q, n_q, gb.sorted, gb.start, g, d_dist); }
         HIP_TRY(ctx, hipGetLastError());
         return enqueue_compact(ctx, d_dist, n_q, cutoff, out_index, out_distance, cap, &total, d_idx, d_odist, d_nout);
     });
@@ -3230,16 +3223,18 @@ extern "C" int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int
     double plo[3], phi[3];
     bbox3(poly_xyz, n_poly, plo, phi);
     const double inf_lo[3] = {-INFINITY, -INFINITY, -INFINITY}, inf_hi[3] = {INFINITY, INFINITY, INFINITY};
-    const CellGrid gp = make_cell_grid(plo, phi, cutoff, n_poly, inf_lo, inf_hi);
-    const CellGrid gn = n_q > 0 ? query_grid(q_xyz, n_q, cutoff, n_q + n_poly) : gp;
+    CellGrid gp, gn = {};      // (no query: no neighbour grid)
+    if (!make_cell_grid(plo, phi, cutoff, n_poly, inf_lo, inf_hi, &gp)) return refuse_extent(ctx, "polymer atoms", plo, phi);
+    if (int rc = n_q > 0 ? contacts_query_grid(ctx, q_xyz, n_q, cutoff, n_q + n_poly, &gn) : 0) return rc;
     const int64_t cells_p = gp.n_cells, cells_n = n_q > 0 ? gn.n_cells : 0;
     std::vector<unsigned> zeros((size_t)std::max({cells_p, cells_n, n_cand}), 0u);
     std::vector<unsigned> h_keep((size_t)n_cand);
     unsigned h_total = 0;
     int64_t rows = 0;
-    double *d_poly = nullptr, *d_q = nullptr, *d_rot = nullptr, *d_ortho = nullptr, *d_sorted_p = nullptr, *d_dist = nullptr, *d_odist = nullptr;
+    double *d_poly = nullptr, *d_q = nullptr, *d_rot = nullptr, *d_ortho = nullptr, *d_dist = nullptr, *d_odist = nullptr;
     int32_t *d_cand = nullptr;
-    unsigned *d_count_p = nullptr, *d_keep = nullptr, *d_count_n = nullptr, *d_start_p = nullptr, *d_cursor_p = nullptr, *d_start_n = nullptr, *d_cursor_n = nullptr;
+    unsigned *d_keep = nullptr;
+    GridBuild bp, bn;      // over the polymer; over the neighbours (counted and scattered by the image kernels: its points come in a second arena)
     int64_t *d_idx = nullptr, *d_nout = nullptr;
     Arena A, B;
     int rc = arena_carve(ctx, "crystal contacts", &A, [&](Carver &cv) {
@@ -3248,14 +3243,11 @@ extern "C" int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int
         cv.take(d_rot, 12 * n_ops);
         cv.take(d_ortho, 9);
         cv.take(d_cand, 4 * n_cand);
-        cv.take(d_count_p, cells_p);
+        bp.carve_counts(cv, cells_p);
         cv.take(d_keep, n_cand);
-        cv.take(d_count_n, cells_n);
-        cv.take(d_sorted_p, 3 * n_poly);
-        cv.take(d_start_p, cells_p + 1);
-        cv.take(d_cursor_p, cells_p);
-        cv.take(d_start_n, cells_n + 1);
-        cv.take(d_cursor_n, cells_n);
+        bn.carve_counts(cv, cells_n);
+        bp.carve_rest(cv, cells_p, n_poly, false);
+        bn.carve_rest(cv, cells_n, 0, false);
         cv.take(d_dist, n_q);
         cv.take(d_idx, n_q);
         cv.take(d_odist, n_q);
@@ -3266,23 +3258,21 @@ extern "C" int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int
         hipStream_t st = ctx->stream;
         {   // inputs and the zeroed counters and flags in a row: ONE copy whenever the pinned block holds them (up to ~80 000 atoms), else one per item
             const H2DItem in[8] = {{d_poly, poly_xyz, (size_t)(24 * n_poly)}, {d_q, q_xyz, (size_t)(24 * n_q)}, {d_rot, rot, (size_t)(96 * n_ops)},
-                                   {d_ortho, ortho, 72}, {d_cand, cand, (size_t)(16 * n_cand)}, {d_count_p, zeros.data(), (size_t)(4 * cells_p)},
-                                   {d_keep, zeros.data(), (size_t)(4 * n_cand)}, {d_count_n, zeros.data(), (size_t)(4 * cells_n)}};
+                                   {d_ortho, ortho, 72}, {d_cand, cand, (size_t)(16 * n_cand)}, {bp.count, zeros.data(), (size_t)(4 * cells_p)},
+                                   {d_keep, zeros.data(), (size_t)(4 * n_cand)}, {bn.count, zeros.data(), (size_t)(4 * cells_n)}};
             HIP_TRY(ctx, h2d_row(ctx, in, 8, pinned_room_beside(ctx, 4 * (size_t)n_cand + 64)));
         }
         const int64_t lanes = n_cand * n_poly;
-        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_poly, 256)), dim3(256), 0, st, d_poly, n_poly, gp, d_count_p); }
-        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count_p, (int)cells_p, d_start_p, d_cursor_p, nullptr); }
-        { PROF(ctx, "k_grid_scatter_points"); hipLaunchKernelGGL(k_grid_scatter_points, dim3(grid_for(n_poly, 256)), dim3(256), 0, st, d_poly, n_poly, gp, d_cursor_p, d_sorted_p, n_poly); }
-        { PROF(ctx, "k_image_select"); hipLaunchKernelGGL(k_image_select, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_sorted_p, d_start_p, gp, cutoff, d_keep); }
+        bp.sort_points(ctx, gp, d_poly, n_poly);
+        { PROF(ctx, "k_image_select"); hipLaunchKernelGGL(k_image_select, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, bp.sorted, bp.start, gp, cutoff, d_keep); }
         if (n_q > 0) {      // (the keep flags and the neighbour count go to the host from inside these two launches: no copy launch)
             unsigned *r_keep = pinned_out(ctx, h_keep.data(), (size_t)n_cand);
             unsigned *r_total = pinned_out(ctx, &h_total, 1);
-            { PROF(ctx, "k_image_count"); hipLaunchKernelGGL(k_image_count, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_keep, gn, d_count_n, r_keep); }
-            { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count_n, (int)cells_n, d_start_n, d_cursor_n, r_total); }
+            { PROF(ctx, "k_image_count"); hipLaunchKernelGGL(k_image_count, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_keep, gn, bn.count, r_keep); }
+            bn.scan(ctx, gn, r_total);
             HIP_TRY(ctx, hipGetLastError());
             if (!r_keep) HIP_TRY(ctx, d2h(ctx, h_keep.data(), d_keep, 4 * (size_t)n_cand));
-            if (!r_total) HIP_TRY(ctx, d2h(ctx, &h_total, d_start_n + cells_n, 4));
+            if (!r_total) HIP_TRY(ctx, d2h(ctx, &h_total, bn.start + cells_n, 4));
         } else {
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, d2h(ctx, h_keep.data(), d_keep, 4 * (size_t)n_cand));
@@ -3292,10 +3282,9 @@ extern "C" int pdbeda_crystal_contacts(pdbeda_ctx *ctx, const double *q_xyz, int
             for (int64_t c = 0; c < n_cand; ++c) kept_out[c] = h_keep[(size_t)c] ? 1 : 0;
         if (n_q == 0 || h_total == 0) return 0;
         if ((int64_t)h_total > lanes) return fail(ctx, PDBEDA_ERR_DEVICE, "neighbour grid holds %u points of at most %lld", h_total, (long long)lanes);
-        double *d_sorted_n = nullptr;
-        if (int e = arena_carve(ctx, "crystal contacts: neighbours", &B, [&](Carver &cv) { cv.take(d_sorted_n, 3 * (size_t)h_total); })) return e;
-        { PROF(ctx, "k_image_scatter"); hipLaunchKernelGGL(k_image_scatter, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_keep, gn, d_cursor_n, d_sorted_n, (int64_t)h_total); }
-        { PROF(ctx, "k_contact_min"); hipLaunchKernelGGL(k_contact_min, dim3(grid_for(n_q, 256)), dim3(256), 0, st, d_q, n_q, d_sorted_n, d_start_n, gn, d_dist); }
+        if (int e = arena_carve(ctx, "crystal contacts: neighbours", &B, [&](Carver &cv) { cv.take(bn.sorted, 3 * (size_t)h_total); })) return e;
+        { PROF(ctx, "k_image_scatter"); hipLaunchKernelGGL(k_image_scatter, dim3(grid_for(lanes, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, d_keep, gn, bn.cursor, bn.sorted, (int64_t)h_total); }
+        { PROF(ctx, "k_contact_min"); hipLaunchKernelGGL(k_contact_min, dim3(grid_for(n_q, 256)), dim3(256), 0, st, d_q, n_q, bn.sorted, bn.start, gn, d_dist); }
         HIP_TRY(ctx, hipGetLastError());
         if (int e = enqueue_compact(ctx, d_dist, n_q, cutoff, out_index, out_distance, cap, &rows, d_idx, d_odist, d_nout)) return e;
         HIP_TRY(ctx, ctx_sync(ctx));                 // wait 2: the rows
@@ -3345,11 +3334,9 @@ extern "C" int pdbeda_image_coords(pdbeda_ctx *ctx, const double *poly_xyz, int6
 // ------------------------------------------------------------------------------------
 // Nearest-atom partition of a map (no reference counterpart; the contract: include/pdbeda.h)
 // ------------------------------------------------------------------------------------
-// The launch graph: memset of the cell counts and the integer tables; k_grid_count_points / k_grid_scan (the contacts grid's) and
-// k_grid_scatter_indexed over the atoms inside the crop box -- the xyz bounding box of the map's box grown by the maximum distance: an atom
-// outside it owns nothing, and the grid never grows with atoms that lie far from the map; k_partition_tile, a workgroup per voxel tile;
-// k_partition_finish.  One wait.  make_cell_grid counts cells in fp64 and enlarges the EDGE until they number at most 2^22, so a box that is
-// huge beside the maximum distance costs longer cell lists, never an overflowing dimension.
+// The launch graph: memset of the cell counts and the integer tables; the grid build (GridBuild, with each atom's original index) over the atoms
+// inside the crop box -- the xyz bounding box of the map's box grown by the maximum distance (crop_cell_grid): an atom outside it owns nothing, and
+// the grid never grows with atoms that lie far from the map; k_partition_tile, a workgroup per voxel tile; k_partition_finish.  One wait.
 // Measured and removed: the same tile walking the 27 cells around every voxel in global memory instead of staging.
 extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_atoms, float max_distance, float cutoff,
                                     int64_t *n, double *sum, int64_t *n_pos, double *sum_pos, int64_t *n_neg, double *sum_neg,
@@ -3373,39 +3360,21 @@ extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_
         if (rc && !m->fix_refused) return rc;
     }
     const double maxd = (double)max_distance;
-    // the crop box, and the grid over its intersection with the atoms' bounding box
-    double crop_lo[3] = {INFINITY, INFINITY, INFINITY}, crop_hi[3] = {-INFINITY, -INFINITY, -INFINITY}, alo[3], ahi[3], glo[3], ghi[3];
-    for (int k = 0; k < 8; ++k) {
-        double p[3];
-        crs2xyz(g, (k & 1) ? uc - 1 : 0, (k & 2) ? ur - 1 : 0, (k & 4) ? us - 1 : 0, p);
-        for (int q = 0; q < 3; ++q) { crop_lo[q] = std::min(crop_lo[q], p[q]); crop_hi[q] = std::max(crop_hi[q], p[q]); }
-    }
-    bbox3(xyz, n_atoms, alo, ahi);
-    bool empty = n_atoms == 0;
-    for (int q = 0; q < 3; ++q) {
-        const double pad = maxd * (1.0 + 1e-5) + 1e-8 * (std::fabs(crop_lo[q]) + std::fabs(crop_hi[q]) + 1.0);      // (wider than a tile's own margin)
-        crop_lo[q] -= pad; crop_hi[q] += pad;
-        glo[q] = std::max(crop_lo[q], alo[q]); ghi[q] = std::min(crop_hi[q], ahi[q]);
-        if (!(glo[q] <= ghi[q])) empty = true;
-    }
-    if (empty)
-        for (int q = 0; q < 3; ++q) glo[q] = ghi[q] = crop_lo[q];      // (one cell, and no atom in it)
-    const CellGrid grid = make_cell_grid(glo, ghi, maxd, n_atoms, crop_lo, crop_hi);
+    const int32_t first[3] = {0, 0, 0}, last[3] = {uc - 1, ur - 1, us - 1};      // the grid of the atoms within the maximum distance of the box
+    double blo[3], bhi[3];
+    crs_box_xyz(g, first, last, blo, bhi);
+    CellGrid grid;
+    if (!crop_cell_grid(blo, bhi, maxd, xyz, n_atoms, &grid)) return fail(ctx, PDBEDA_ERR_STATE, "map partition: no cell grid over a finite box");
     const int64_t cells = grid.n_cells;
     const size_t na = (size_t)n_atoms, tables = 6 * na + 8;
-    double *d_xyz = nullptr, *d_sorted = nullptr, *d_tsq = nullptr, *d_os = nullptr;
-    unsigned *d_count = nullptr, *d_cursor = nullptr, *d_start = nullptr;
-    int *d_sidx = nullptr;
+    double *d_xyz = nullptr, *d_tsq = nullptr, *d_os = nullptr;
+    GridBuild gb;
     unsigned long long *d_tab = nullptr;
     long long *d_on = nullptr, *d_un = nullptr;
     int32_t *d_owner = nullptr;
     return with_scratch(ctx, "map partition", [&](Carver &cv) {
         cv.take(d_xyz, 3 * na);
-        cv.take(d_count, cells);
-        cv.take(d_cursor, cells);
-        cv.take(d_start, cells + 1);
-        cv.take(d_sorted, 3 * na);
-        cv.take(d_sidx, na);
+        gb.carve(cv, cells, n_atoms, true);
         cv.take(d_tab, tables);      // atom_n [3][n] | atom_sum [3][n] | unowned [6] | range [1]
         cv.take(d_tsq, n_tiles);
         cv.take(d_on, 3 * na);
@@ -3415,7 +3384,7 @@ extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_
     }, [&]() -> int {
         double *d_us = reinterpret_cast<double *>(d_un + 3);
         hipStream_t st = ctx->stream;
-        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 4 * (size_t)cells, st));
+        HIP_TRY(ctx, hipMemsetAsync(gb.count, 0, 4 * (size_t)cells, st));
         HIP_TRY(ctx, hipMemsetAsync(d_tab, 0, 8 * tables, st));
         double fix_mul = m->fix_mul;
         if (m->fix_refused) {      // NaN / infinite voxels: they enter no sum, and the quantum comes from the finite voxels of the box
@@ -3431,13 +3400,11 @@ extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_
             fix_mul = ldexp(1.0, std::max(-900, std::min(S, 900)));
         }
         if (n_atoms > 0) HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, 24 * na));
-        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_atoms, 256)), dim3(256), 0, st, d_xyz, n_atoms, grid, d_count); }
-        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count, (int)cells, d_start, d_cursor, nullptr); }
-        { PROF(ctx, "k_grid_scatter_indexed"); hipLaunchKernelGGL(k_grid_scatter_indexed, dim3(grid_for(n_atoms, 256)), dim3(256), 0, st, d_xyz, n_atoms, grid, d_cursor, d_sorted, d_sidx, n_atoms); }
+        gb.sort_points(ctx, grid, d_xyz, n_atoms);
         PartitionArgs a;
         a.geom = m->geom_dev; a.dens = m->dens;
         a.uc = uc; a.ur = ur; a.us = us; a.tiles_c = tiles_c; a.tiles_r = tiles_r;
-        a.grid = grid; a.sorted = d_sorted; a.sorted_index = d_sidx; a.start = d_start;
+        a.grid = grid; a.sorted = gb.sorted; a.sorted_index = gb.sorted_index; a.start = gb.start;
         a.max_distance = maxd; a.cutoff = (double)cutoff; a.fix_mul = fix_mul;
         a.atom_n = d_tab; a.atom_sum = d_tab + 3 * na; a.n_atoms = n_atoms; a.unowned = d_tab + 6 * na;
         a.tile_sq = d_tsq; a.owner = d_owner;
@@ -3493,8 +3460,8 @@ extern "C" int pdbeda_interp_density(pdbeda_map *m, const double *xyz, int64_t n
 }
 
 // The launch graph: memset of the cell counts and the two counters; the atoms, the scored indices and the host's tables (reference profile,
-// candidate directions); k_grid_count_points / k_grid_scan / k_grid_scatter_indexed over the atoms inside the crop box -- the scored atoms' bounding
-// box grown by the reach, 2 R_max: an atom outside it wins no sample point --; k_atom_qscores, a wave per scored atom; the results.  One wait.
+// candidate directions); the grid build (GridBuild) over the atoms inside the crop box -- the scored atoms' bounding box grown by the reach,
+// 2 R_max (crop_cell_grid): an atom outside it wins no sample point --; k_atom_qscores, a wave per scored atom; the results.  One wait.
 extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_all, const int32_t *scored, int64_t n_scored, float step, int32_t n_shells,
                                    const double *ref, const double *unit_pts, const int32_t *level_offsets, int32_t n_levels, int32_t min_points,
                                    double *q, int32_t *n_points, int32_t *shell_n, double *shell_mean, uint8_t *valid, int64_t counters[2]) {
@@ -3518,14 +3485,8 @@ extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_a
     if (!all_finite(xyz, 3 * n_all)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: non-finite coordinate");
     const Geom &g = m->geom;
     const double r_max = (double)(n_shells - 1) * (double)step;
-    {   // every sample point stays castable: |f(atom)| < 2^29 and the sphere of R_max spans fewer than 2^29 steps of every grid axis
-        const double limit = (double)(1ll << 29);
-        for (int i = 0; i < 3; ++i) {
-            const double per_unit = g.orthogonal ? 1.0 / std::fabs(g.grid_len[i])
-                                                 : (std::fabs(g.deortho[3 * i]) + std::fabs(g.deortho[3 * i + 1]) + std::fabs(g.deortho[3 * i + 2])) * (double)g.xyz_interval[i];
-            if (!(r_max * per_unit < limit)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: the largest shell spans 2^29 grid steps or more");
-        }
-    }
+    // every sample point stays castable: |f(atom)| < 2^29 and the sphere of R_max spans fewer than 2^29 steps of every grid axis
+    if (!reach_below_2p29_steps(g, r_max)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom Q-scores: the largest shell spans 2^29 grid steps or more");
     double slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int64_t i = 0; i < n_scored; ++i) {
         const int64_t at = scored ? (int64_t)scored[i] : i;
@@ -3536,21 +3497,14 @@ extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_a
     }
     if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the crop box (what can matter to a scored atom), and the grid over its intersection with the atoms' bounding box: never empty, the scored atoms lie in both
+    // the grid of the atoms that can matter to a scored atom: those within the reach, 2 R_max, of the scored atoms' bounding box
     const double reach = 2.0 * r_max * (1.0 + 1e-6);
-    double crop_lo[3], crop_hi[3], alo[3], ahi[3], glo[3], ghi[3];
-    bbox3(xyz, n_all, alo, ahi);
-    for (int k = 0; k < 3; ++k) {
-        const double pad = reach * (1.0 + 1e-5) + 1e-8 * (std::fabs(slo[k]) + std::fabs(shi[k]) + 1.0);
-        crop_lo[k] = slo[k] - pad; crop_hi[k] = shi[k] + pad;
-        glo[k] = std::max(crop_lo[k], alo[k]); ghi[k] = std::min(crop_hi[k], ahi[k]);
-    }
-    const CellGrid grid = make_cell_grid(glo, ghi, reach, n_all, crop_lo, crop_hi);
+    CellGrid grid;
+    if (!crop_cell_grid(slo, shi, reach, xyz, n_all, &grid)) return fail(ctx, PDBEDA_ERR_STATE, "atom Q-scores: no cell grid over a finite box");
     const int64_t cells = grid.n_cells;
     const size_t na = (size_t)n_all, ns = (size_t)n_scored, rows = ns * (size_t)n_shells;
-    double *d_xyz = nullptr, *d_sorted = nullptr, *d_tab = nullptr, *d_q = nullptr, *d_mean = nullptr;
-    unsigned *d_count = nullptr, *d_cursor = nullptr, *d_start = nullptr;
-    int *d_sidx = nullptr;
+    double *d_xyz = nullptr, *d_tab = nullptr, *d_q = nullptr, *d_mean = nullptr;
+    GridBuild gb;
     int32_t *d_scored = nullptr, *d_np = nullptr, *d_sn = nullptr;
     uint8_t *d_valid = nullptr;
     unsigned long long *d_ctr = nullptr;
@@ -3558,11 +3512,7 @@ extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_a
         cv.take(d_xyz, 3 * na);
         cv.take(d_scored, scored ? ns : 0);
         cv.take(d_tab, (size_t)n_shells + 3 * (size_t)n_unit);      // ref [n_shells] | unit_pts [n_unit][3]
-        cv.take(d_count, cells);
-        cv.take(d_cursor, cells);
-        cv.take(d_start, cells + 1);
-        cv.take(d_sorted, 3 * na);
-        cv.take(d_sidx, na);
+        gb.carve(cv, cells, n_all, true);
         cv.take(d_ctr, 2);
         cv.take(d_q, ns);
         cv.take(d_np, ns);
@@ -3571,7 +3521,7 @@ extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_a
         cv.take(d_valid, ns);
     }, [&]() -> int {
         hipStream_t st = ctx->stream;
-        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 4 * (size_t)cells, st));
+        HIP_TRY(ctx, hipMemsetAsync(gb.count, 0, 4 * (size_t)cells, st));
         HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, 16, st));
         HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, 24 * na));
         if (scored) HIP_TRY(ctx, h2d_one(ctx, d_scored, scored, 4 * ns));
@@ -3579,12 +3529,10 @@ extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_a
             const H2DItem in[2] = {{d_tab, ref, 8 * (size_t)n_shells}, {d_tab + n_shells, unit_pts, 24 * (size_t)n_unit}};
             HIP_TRY(ctx, h2d_row(ctx, in, 2));
         }
-        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_all, 256)), dim3(256), 0, st, d_xyz, n_all, grid, d_count); }
-        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count, (int)cells, d_start, d_cursor, nullptr); }
-        { PROF(ctx, "k_grid_scatter_indexed"); hipLaunchKernelGGL(k_grid_scatter_indexed, dim3(grid_for(n_all, 256)), dim3(256), 0, st, d_xyz, n_all, grid, d_cursor, d_sorted, d_sidx, n_all); }
+        gb.sort_points(ctx, grid, d_xyz, n_all);
         QScoreArgs a;
         a.geom = m->geom_dev; a.dens = m->dens; a.xyz = d_xyz; a.scored = scored ? d_scored : nullptr; a.n_scored = n_scored;
-        a.grid = grid; a.sorted = d_sorted; a.sorted_index = d_sidx; a.start = d_start;
+        a.grid = grid; a.sorted = gb.sorted; a.sorted_index = gb.sorted_index; a.start = gb.start;
         a.step = (double)step; a.reach2 = reach * reach;
         a.n_shells = n_shells; a.n_levels = n_levels; a.min_points = min_points;
         for (int l = 0; l <= PDBEDA_QSCORE_MAX_LEVELS; ++l) a.level_off[l] = level_offsets[std::min(l, n_levels)];
@@ -3612,8 +3560,8 @@ static int model_shift(int64_t n_gridded, double a_max) {
 }
 
 // The launch graph: memset of the cell counts and the two counters; the atoms' coordinates, amplitudes, exponents and radii in one row of scratch;
-// k_grid_count_points / k_grid_scan / k_grid_scatter_indexed over the atoms inside the crop box -- the xyz bounding box of the STORED box grown by the
-// largest radius: an atom outside it reaches no voxel, and the grid never grows with atoms that lie far from the map --; k_model_tile, a workgroup per
+// the grid build (GridBuild) over the atoms inside the crop box -- the xyz bounding box of the STORED box grown by the largest radius
+// (crop_cell_grid): an atom outside it reaches no voxel, and the grid never grows with atoms that lie far from the map --; k_model_tile, a workgroup per
 // tile of stored voxels, which writes the float32 voxels itself; the counters.  One wait.  The new map's arena is taken first and goes back to the pool
 // with the half-made map when anything fails: *out is written last.
 extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t n_atoms, int32_t n_terms, const double *amp, const double *expo, const float *radii,
@@ -3634,41 +3582,21 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
     }
     const Geom &g = like->geom;
     const double r_max = n_atoms > 0 ? (double)r_top : 1.0;      // (no atom: any cell edge will do)
-    {   // (pdbeda_atom_qscores' rule for its largest shell)
-        const double limit = (double)(1ll << 29);
-        for (int i = 0; i < 3; ++i) {
-            const double per_unit = g.orthogonal ? 1.0 / std::fabs(g.grid_len[i])
-                                                 : (std::fabs(g.deortho[3 * i]) + std::fabs(g.deortho[3 * i + 1]) + std::fabs(g.deortho[3 * i + 2])) * (double)g.xyz_interval[i];
-            if (!(r_max * per_unit < limit)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the largest radius spans 2^29 grid steps or more");
-        }
-    }
+    if (!reach_below_2p29_steps(g, r_max)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the largest radius spans 2^29 grid steps or more");
     const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
     const int tiles_c = (nc + PT_C - 1) / PT_C, tiles_r = (nr + PT_R - 1) / PT_R, tiles_s = (ns + PT_S - 1) / PT_S;
     const int64_t n_tiles = (int64_t)tiles_c * tiles_r * tiles_s;
     if (like->n_vox <= 0 || n_tiles >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the map is empty or has 2^31 tiles or more");
-    // the crop box, and the grid over its intersection with the atoms' bounding box (pdbeda_map_partition's, over the stored box)
-    double crop_lo[3] = {INFINITY, INFINITY, INFINITY}, crop_hi[3] = {-INFINITY, -INFINITY, -INFINITY}, alo[3], ahi[3], glo[3], ghi[3];
-    for (int k = 0; k < 8; ++k) {
-        double p[3];
-        crs2xyz(g, (k & 1) ? nc - 1 : 0, (k & 2) ? nr - 1 : 0, (k & 4) ? ns - 1 : 0, p);
-        for (int q = 0; q < 3; ++q) { crop_lo[q] = std::min(crop_lo[q], p[q]); crop_hi[q] = std::max(crop_hi[q], p[q]); }
-    }
-    bbox3(xyz, n_atoms, alo, ahi);
-    bool empty = n_atoms == 0;
-    for (int q = 0; q < 3; ++q) {
-        const double pad = r_max * (1.0 + 1e-5) + 1e-8 * (std::fabs(crop_lo[q]) + std::fabs(crop_hi[q]) + 1.0);      // (wider than a tile's own margin)
-        crop_lo[q] -= pad; crop_hi[q] += pad;
-        glo[q] = std::max(crop_lo[q], alo[q]); ghi[q] = std::min(crop_hi[q], ahi[q]);
-        if (!(glo[q] <= ghi[q])) empty = true;
-    }
-    if (empty)
-        for (int q = 0; q < 3; ++q) glo[q] = ghi[q] = crop_lo[q];      // (one cell, and no atom in it)
-    // S: from the atoms the grid will hold (grid_cropped's comparisons, on the host) and the largest sum of |amplitudes| of ANY atom
+    const int32_t first[3] = {0, 0, 0}, last[3] = {nc - 1, nr - 1, ns - 1};      // the grid of the atoms within the largest radius of the STORED box
+    double blo[3], bhi[3];
+    crs_box_xyz(g, first, last, blo, bhi);
+    CellGrid grid;
+    if (!crop_cell_grid(blo, bhi, r_max, xyz, n_atoms, &grid)) return fail(ctx, PDBEDA_ERR_STATE, "model density: no cell grid over a finite box");
+    // S: from the atoms the grid will hold and the largest sum of |amplitudes| of ANY atom
     int64_t n_gridded = 0;
     double a_max = 0.0;
     for (int64_t i = 0; i < n_atoms; ++i) {
-        const double *p = xyz + 3 * i;
-        if (p[0] >= crop_lo[0] && p[0] <= crop_hi[0] && p[1] >= crop_lo[1] && p[1] <= crop_hi[1] && p[2] >= crop_lo[2] && p[2] <= crop_hi[2]) ++n_gridded;
+        if (!grid_cropped(grid, xyz + 3 * i)) ++n_gridded;
         double t = 0.0;
         for (int j = 0; j < n_terms; ++j) t += std::fabs(amp[i * n_terms + j]);
         a_max = std::max(a_max, t);
@@ -3677,7 +3605,6 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
     const int S = model_shift(n_gridded, a_max);
     if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const CellGrid grid = make_cell_grid(glo, ghi, r_max, n_atoms, crop_lo, crop_hi);
     const int64_t cells = grid.n_cells;
     const size_t na = (size_t)n_atoms, np = (size_t)n_pairs;
 
@@ -3687,10 +3614,9 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
     m->n_vox = like->n_vox;
     float *d_out = nullptr;
     if (int rc = arena_carve(ctx, "model density", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d_out, (size_t)m->n_vox); })) return rc;
-    double *d_xyz = nullptr, *d_amp = nullptr, *d_expo = nullptr, *d_sorted = nullptr;
+    double *d_xyz = nullptr, *d_amp = nullptr, *d_expo = nullptr;
     float *d_radii = nullptr;
-    unsigned *d_count = nullptr, *d_cursor = nullptr, *d_start = nullptr;
-    int *d_sidx = nullptr;
+    GridBuild gb;
     unsigned long long *d_ctr = nullptr;
     int64_t seen[2] = {0, 0};
     const int rc = with_scratch(ctx, "model density", [&](Carver &cv) {
@@ -3698,27 +3624,21 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
         cv.take(d_amp, np);
         cv.take(d_expo, np);
         cv.take(d_radii, na);
-        cv.take(d_count, cells);
-        cv.take(d_cursor, cells);
-        cv.take(d_start, cells + 1);
-        cv.take(d_sorted, 3 * na);
-        cv.take(d_sidx, na);
+        gb.carve(cv, cells, n_atoms, true);
         cv.take(d_ctr, 2);
     }, [&]() -> int {
         hipStream_t st = ctx->stream;
-        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 4 * (size_t)cells, st));
+        HIP_TRY(ctx, hipMemsetAsync(gb.count, 0, 4 * (size_t)cells, st));
         HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, 16, st));
         HIP_TRY(ctx, h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom)));
         if (n_atoms > 0) {
             const H2DItem in[4] = {{d_xyz, xyz, 24 * na}, {d_amp, amp, 8 * np}, {d_expo, expo, 8 * np}, {d_radii, radii, 4 * na}};
             HIP_TRY(ctx, h2d_row(ctx, in, 4));
         }
-        { PROF(ctx, "k_grid_count_points"); hipLaunchKernelGGL(k_grid_count_points, dim3(grid_for(n_atoms, 256)), dim3(256), 0, st, d_xyz, n_atoms, grid, d_count); }
-        { PROF(ctx, "k_grid_scan"); hipLaunchKernelGGL(k_grid_scan, dim3(1), dim3(1024), 0, st, d_count, (int)cells, d_start, d_cursor, nullptr); }
-        { PROF(ctx, "k_grid_scatter_indexed"); hipLaunchKernelGGL(k_grid_scatter_indexed, dim3(grid_for(n_atoms, 256)), dim3(256), 0, st, d_xyz, n_atoms, grid, d_cursor, d_sorted, d_sidx, n_atoms); }
+        gb.sort_points(ctx, grid, d_xyz, n_atoms);
         ModelArgs a;
         a.geom = m->geom_dev; a.tiles_c = tiles_c; a.tiles_r = tiles_r;
-        a.grid = grid; a.sorted = d_sorted; a.sorted_index = d_sidx; a.start = d_start;
+        a.grid = grid; a.sorted = gb.sorted; a.sorted_index = gb.sorted_index; a.start = gb.start;
         a.amp = d_amp; a.expo = d_expo; a.radii = d_radii; a.n_terms = n_terms;
         a.r_max = r_max; a.fix_mul = ldexp(1.0, S); a.fix_inv = ldexp(1.0, -S);
         a.out = d_out; a.counters = d_ctr;

@@ -3,9 +3,9 @@
 // include/pdbeda.h.  Included from pdbeda_hip.hip.
 //
 //   k_model_tile             a workgroup of 256 per tile of PT_C x PT_R x PT_S STORED voxels (the partition's tile over ncrs, not over the
-//                            unique box), one thread per voxel (c fastest).  The tile's xyz bounding box comes from its 8 corners, grown by
-//                            the LARGEST radius; the atoms of the grid cells that box touches (the partition's counting sort, cell edge from
-//                            the largest radius) are streamed through an LDS buffer of MD_STAGE atoms: coordinates, the radius, the square
+//                            unique box), one thread per voxel (c fastest).  The atoms of the grid cells within the LARGEST radius of the
+//                            tile (pdbeda_cellgrid.h: tile_voxel, tile_cell_range, stage_cell_rows; the cell edge comes from that radius)
+//                            are streamed through an LDS buffer of MD_STAGE atoms: coordinates, the radius, the square
 //                            that rejects without a square root, and the n_terms amplitude / exponent pairs, every one an fp64 array of its
 //                            own -- all lanes read the SAME atom, a broadcast without bank conflicts.  Every thread keeps ONE long long: a
 //                            term amp * exp(-(expo * d2)) is rounded once to 2^-S and added as an integer, so neither the staging run, nor
@@ -48,41 +48,26 @@ __global__ void __launch_bounds__(256) k_model_tile(ModelArgs a) {
     __shared__ double s_amp[MD_TERMS][MD_STAGE], s_expo[MD_TERMS][MD_STAGE];
     const int tid = threadIdx.x;
     const Geom &g = *a.geom;
-    const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
-    const int64_t tile = blockIdx.x;
-    const int tc = (int)(tile % a.tiles_c), tr = (int)((tile / a.tiles_c) % a.tiles_r), ts = (int)(tile / ((int64_t)a.tiles_c * a.tiles_r));
-    const int c0 = tc * PT_C, r0 = tr * PT_R, s0 = ts * PT_S;
-    const int c = c0 + (tid & (PT_C - 1)), r = r0 + ((tid / PT_C) & (PT_R - 1)), s = s0 + tid / (PT_C * PT_R);
-    const bool live = c < nc && r < nr && s < ns;
-
-    // the cells the tile has to search: k_partition_tile's box of the 8 corners, grown by the largest radius and the same margins
+    const int nc = g.ncrs[0], nr = g.ncrs[1];
+    const TileVoxel tv = tile_voxel<PT_C, PT_R, PT_S>(blockIdx.x, a.tiles_c, a.tiles_r, g.ncrs, tid);
+    const int c = tv.c, r = tv.r, s = tv.s;
+    const bool live = tv.live;
     int lo[3], hi[3];
-    bool any = true;
-    {
-        const int c1 = min(c0 + PT_C, nc) - 1, r1 = min(r0 + PT_R, nr) - 1, s1 = min(s0 + PT_S, ns) - 1;
-        double blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int k = 0; k < 8; ++k) {
-            double p[3];
-            crs2xyz(g, (k & 1) ? c1 : c0, (k & 2) ? r1 : r0, (k & 4) ? s1 : s0, p);
-            for (int q = 0; q < 3; ++q) { blo[q] = fmin(blo[q], p[q]); bhi[q] = fmax(bhi[q], p[q]); }
-        }
-        for (int q = 0; q < 3; ++q) {
-            const double pad = a.r_max * (1.0 + 1e-6) + 1e-9 * (fabs(blo[q]) + fabs(bhi[q]) + 1.0);
-            const double fl = floor(((blo[q] - pad) - a.grid.lo[q]) / a.grid.edge), fh = floor(((bhi[q] + pad) - a.grid.lo[q]) / a.grid.edge);
-            if (!(fh >= 0.0 && fl <= (double)(a.grid.dim[q] - 1))) any = false;      // (beside the grid, or NaN)
-            lo[q] = fl < 0.0 ? 0 : (int)fmin(fl, (double)(a.grid.dim[q] - 1));
-            hi[q] = fh > (double)(a.grid.dim[q] - 1) ? a.grid.dim[q] - 1 : (int)fmax(fh, 0.0);
-        }
-    }
+    const bool any = tile_cell_range(g, a.grid, tv.c0, tv.c1, a.r_max, lo, hi);
 
     double p[3] = {0.0, 0.0, 0.0};
     if (live) crs2xyz(g, c, r, s, p);
     long long acc = 0;
     const int nt = a.n_terms;
-    int fill = 0, runs = 0;
-    long long staged = 0;
-    // (uniform control flow: every thread walks the same rows and segments)
-    auto gather = [&](int count) {
+    const StageReport rep = !any ? StageReport{0, 0, 0} : stage_cell_rows<MD_STAGE>(a.grid, a.start, lo, hi, [&](int slot, unsigned k) {
+        const double *q = a.sorted + 3 * (size_t)k;
+        const size_t at = (size_t)a.sorted_index[k];
+        const double rad = (double)a.radii[at];
+        s_x[slot] = q[0]; s_y[slot] = q[1]; s_z[slot] = q[2];
+        s_rad[slot] = rad;
+        s_r2[slot] = (rad * rad) * (1.0 + 0x1p-50);
+        for (int j = 0; j < nt; ++j) { s_amp[j][slot] = a.amp[at * nt + j]; s_expo[j][slot] = a.expo[at * nt + j]; }
+    }, [&](int count) {
         __syncthreads();
         if (live)
             for (int k = 0; k < count; ++k) {
@@ -96,40 +81,11 @@ __global__ void __launch_bounds__(256) k_model_tile(ModelArgs a) {
                     acc += fix_of(t, a.fix_mul);
                 }
             }
-        ++runs;
-    };
-    if (any && a.grid.n_cells > 0)
-        for (int z = lo[2]; z <= hi[2]; ++z)
-            for (int y = lo[1]; y <= hi[1]; ++y) {
-                const int64_t row = ((int64_t)z * a.grid.dim[1] + y) * a.grid.dim[0];
-                unsigned b = a.start[row + lo[0]];
-                const unsigned e = a.start[row + hi[0] + 1];      // (cells lo[0]..hi[0] of a row are consecutive)
-                staged += (long long)(e - b);
-                while (b < e) {
-                    const int take = (int)min((unsigned)(MD_STAGE - fill), e - b);
-                    for (int i = tid; i < take; i += 256) {
-                        const double *q = a.sorted + 3 * (size_t)(b + i);
-                        const size_t at = (size_t)a.sorted_index[b + i];
-                        const double rad = (double)a.radii[at];
-                        s_x[fill + i] = q[0]; s_y[fill + i] = q[1]; s_z[fill + i] = q[2];
-                        s_rad[fill + i] = rad;
-                        s_r2[fill + i] = (rad * rad) * (1.0 + 0x1p-50);
-                        for (int j = 0; j < nt; ++j) { s_amp[j][fill + i] = a.amp[at * nt + j]; s_expo[j][fill + i] = a.expo[at * nt + j]; }
-                    }
-                    fill += take;
-                    b += (unsigned)take;
-                    if (fill == MD_STAGE) {
-                        gather(fill);
-                        __syncthreads();      // (the buffer is written again)
-                        fill = 0;
-                    }
-                }
-            }
-    if (fill > 0) gather(fill);
+    });
     if (live) a.out[((int64_t)s * nr + r) * nc + c] = (float)((double)acc * a.fix_inv);      // (a power of two: the product is exact; 0 -> +0.0f)
     if (tid == 0) {
-        if (staged > 0) atomicMax(&a.counters[0], (unsigned long long)staged);
-        if (runs > 1) atomicAdd(&a.counters[1], 1ull);
+        if (rep.staged > 0) atomicMax(&a.counters[0], (unsigned long long)rep.staged);
+        if (rep.runs > 1) atomicAdd(&a.counters[1], 1ull);
     }
 }
 

@@ -2,18 +2,16 @@
 // nearest to it (within one maximum distance) or to nobody, and the density is summed per owner.  No reference counterpart; the
 // contract is spelled out at pdbeda_map_partition in include/pdbeda.h.  Included from pdbeda_hip.hip.
 //
-//   k_grid_scatter_indexed   the scatter of the contacts grid's counting sort (pdbeda_contacts.h: count, scan, scatter) that also
-//                            keeps each point's ORIGINAL index: the tie rule (lowest atom index) needs it, and so do the rows.
 //   k_partition_range        only for a map that holds NaN / infinite voxels (the map's own quantum is refused then): max finite |rho|
 //                            of the box by an integer atomic max on the bit pattern.
-//   k_partition_tile         a workgroup of 256 per tile of PT_C x PT_R x PT_S voxels, one thread per voxel (c fastest).  The tile's
-//                            xyz bounding box comes from its 8 corners (crs2xyz is affine: right on skewed cells too), grown by the
-//                            maximum distance; the atoms of the grid cells that box touches are streamed through an LDS buffer of
-//                            PT_STAGE atoms (coordinates as three fp64 arrays: every lane reads the SAME atom, a broadcast without
-//                            bank conflicts) and every lane keeps its best (d2, index) with the tie rule.  A tile whose atoms fit ONE
-//                            buffer -- every tile of a protein at 3.5 A -- sums per staged atom in LDS (integers) and issues one global
-//                            integer atomic per (atom, tile, column) that owns something; a tile with more atoms runs the buffer
-//                            several times and sends each voxel's contribution to global memory itself: slower, and as right.
+//   k_partition_tile         a workgroup of 256 per tile of PT_C x PT_R x PT_S voxels, one thread per voxel (c fastest).  The atoms of
+//                            the grid cells within the maximum distance of the tile (pdbeda_cellgrid.h: tile_voxel, tile_cell_range,
+//                            stage_cell_rows; the atoms were sorted with their ORIGINAL index, which the tie rule and the rows need)
+//                            are streamed through an LDS buffer of PT_STAGE atoms (coordinates as three fp64 arrays: every lane
+//                            reads the SAME atom, a broadcast without bank conflicts) and every lane keeps its best (d2, index) with
+//                            the tie rule.  A tile whose atoms fit ONE buffer -- every tile of a protein at 3.5 A -- sums per staged
+//                            atom in LDS (integers) and issues one global integer atomic per (atom, tile, column) that owns something;
+//                            a tile with more atoms runs the buffer several times and sends each voxel's contribution to global memory itself.
 //   k_partition_finish       integers -> the caller's columns (sum = integer / 2^shift, exact), and the sum of squares of the unowned voxels
 //                            folded from the per-workgroup partials in index order by one block.
 //
@@ -47,16 +45,6 @@ struct PartitionArgs {
     int32_t *owner;                      // box voxels, or nullptr
 };
 
-__global__ void __launch_bounds__(256) k_grid_scatter_indexed(const double *__restrict__ xyz, int64_t n, CellGrid g, unsigned *__restrict__ cursor,
-                                                              double *__restrict__ sorted, int *__restrict__ sorted_index, int64_t room) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double v[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-        if (grid_cropped(g, v)) continue;
-        const unsigned pos = atomicAdd(&cursor[grid_cell(g, v)], 1u);
-        if ((int64_t)pos < room) { sorted[3 * pos] = v[0]; sorted[3 * pos + 1] = v[1]; sorted[3 * pos + 2] = v[2]; sorted_index[pos] = (int)i; }
-    }
-}
-
 // max finite |rho| over the box as the bit pattern of a non-negative double (ordered like the integers); *out starts at 0.
 __global__ void __launch_bounds__(256) k_partition_range(const float *__restrict__ dens, int n0, int n1, int uc, int ur, int us, unsigned long long *out) {
     const int64_t total = (int64_t)uc * ur * us;
@@ -85,39 +73,22 @@ __global__ void __launch_bounds__(256) k_partition_tile(PartitionArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const Geom &g = *a.geom;
     const int64_t tile = blockIdx.x;
-    const int tc = (int)(tile % a.tiles_c), tr = (int)((tile / a.tiles_c) % a.tiles_r), ts = (int)(tile / ((int64_t)a.tiles_c * a.tiles_r));
-    const int c0 = tc * PT_C, r0 = tr * PT_R, s0 = ts * PT_S;
-    const int c = c0 + (tid & (PT_C - 1)), r = r0 + ((tid / PT_C) & (PT_R - 1)), s = s0 + tid / (PT_C * PT_R);
-    const bool live = c < a.uc && r < a.ur && s < a.us;
-
-    // the cells the tile has to search: its corners' bounding box, grown by the maximum distance and by a margin far above the rounding
-    // of crs2xyz and of the distance (an interior voxel may leave the corners' box by an ulp; the cell of a point is monotonic in it)
+    const int box[3] = {a.uc, a.ur, a.us};
+    const TileVoxel tv = tile_voxel<PT_C, PT_R, PT_S>(tile, a.tiles_c, a.tiles_r, box, tid);
+    const int c = tv.c, r = tv.r, s = tv.s;
+    const bool live = tv.live;
     int lo[3], hi[3];
-    bool any = true;
-    {
-        const int c1 = min(c0 + PT_C, a.uc) - 1, r1 = min(r0 + PT_R, a.ur) - 1, s1 = min(s0 + PT_S, a.us) - 1;
-        double blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int k = 0; k < 8; ++k) {
-            double p[3];
-            crs2xyz(g, (k & 1) ? c1 : c0, (k & 2) ? r1 : r0, (k & 4) ? s1 : s0, p);
-            for (int q = 0; q < 3; ++q) { blo[q] = fmin(blo[q], p[q]); bhi[q] = fmax(bhi[q], p[q]); }
-        }
-        for (int q = 0; q < 3; ++q) {
-            const double pad = a.max_distance * (1.0 + 1e-6) + 1e-9 * (fabs(blo[q]) + fabs(bhi[q]) + 1.0);
-            const double fl = floor(((blo[q] - pad) - a.grid.lo[q]) / a.grid.edge), fh = floor(((bhi[q] + pad) - a.grid.lo[q]) / a.grid.edge);
-            if (!(fh >= 0.0 && fl <= (double)(a.grid.dim[q] - 1))) any = false;      // (beside the grid, or NaN)
-            lo[q] = fl < 0.0 ? 0 : (int)fmin(fl, (double)(a.grid.dim[q] - 1));
-            hi[q] = fh > (double)(a.grid.dim[q] - 1) ? a.grid.dim[q] - 1 : (int)fmax(fh, 0.0);
-        }
-    }
+    const bool any = tile_cell_range(g, a.grid, tv.c0, tv.c1, a.max_distance, lo, hi);
 
     double p[3] = {0.0, 0.0, 0.0};
     if (live) crs2xyz(g, c, r, s, p);
     double best = INFINITY;
     int best_idx = 0x7fffffff, best_slot = -1;
-    int fill = 0, runs = 0;
-    // (uniform control flow: every thread walks the same rows and segments)
-    auto search = [&](int count) {
+    const StageReport rep = !any ? StageReport{0, 0, 0} : stage_cell_rows<PT_STAGE>(a.grid, a.start, lo, hi, [&](int slot, unsigned k) {
+        const double *q = a.sorted + 3 * (size_t)k;
+        s_x[slot] = q[0]; s_y[slot] = q[1]; s_z[slot] = q[2];
+        s_idx[slot] = a.sorted_index[k];
+    }, [&](int count) {
         __syncthreads();
         if (live)
             for (int k = 0; k < count; ++k) {
@@ -126,34 +97,10 @@ __global__ void __launch_bounds__(256) k_partition_tile(PartitionArgs a) {
                 const int idx = s_idx[k];
                 if (d2 < best || (d2 == best && idx < best_idx)) { best = d2; best_idx = idx; best_slot = k; }
             }
-        ++runs;
-    };
-    if (any && a.grid.n_cells > 0)
-        for (int z = lo[2]; z <= hi[2]; ++z)
-            for (int y = lo[1]; y <= hi[1]; ++y) {
-                const int64_t row = ((int64_t)z * a.grid.dim[1] + y) * a.grid.dim[0];
-                unsigned b = a.start[row + lo[0]];
-                const unsigned e = a.start[row + hi[0] + 1];      // (cells lo[0]..hi[0] of a row are consecutive)
-                while (b < e) {
-                    const int take = (int)min((unsigned)(PT_STAGE - fill), e - b);
-                    for (int i = tid; i < take; i += 256) {
-                        const double *q = a.sorted + 3 * (size_t)(b + i);
-                        s_x[fill + i] = q[0]; s_y[fill + i] = q[1]; s_z[fill + i] = q[2];
-                        s_idx[fill + i] = a.sorted_index[b + i];
-                    }
-                    fill += take;
-                    b += (unsigned)take;
-                    if (fill == PT_STAGE) {
-                        search(fill);
-                        __syncthreads();      // (the buffer is written again)
-                        fill = 0;
-                    }
-                }
-            }
-    const int full_runs = runs;
-    if (fill > 0) search(fill);
+    });
     // one buffer held every atom of the tile: best_slot names the owner's row of the LDS sums
-    const bool lds_sums = full_runs == 0 && fill > 0;
+    const int fill = rep.last;
+    const bool lds_sums = rep.runs == 1 && fill > 0;
     if (lds_sums) {
         for (int k = tid; k < fill; k += 256) {
             s_cnt[0][k] = 0u; s_cnt[1][k] = 0u; s_cnt[2][k] = 0u;

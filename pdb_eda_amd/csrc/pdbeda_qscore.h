@@ -6,7 +6,7 @@
 //                        promoted to fp64 and folded by lerp(a, b, t) = a + t * (b - a) along c, then r, then s.
 //   k_interp_density     one thread per point.
 //   k_atom_qscores       a wave of 64 per scored atom, four to a workgroup of 256.  The wave gathers into its LDS slice the atoms of the
-//                        cells around its atom (the cell grid of pdbeda_contacts.h, edge > 2 R_max) that lie within 2 R_max of it -- the only
+//                        cells around its atom (the cell grid of pdbeda_cellgrid.h, edge > 2 R_max) that lie within 2 R_max of it -- the only
 //                        atoms that can be nearer to a sample point than the atom itself -- as three fp64 arrays (every lane reads the SAME
 //                        atom: a broadcast without bank conflicts).  Per shell and candidate level lane j owns candidate j: it tests its
 //                        point against the staged atoms, a __ballot counts the accepted, and at the level the shell stops at the accepted
@@ -114,24 +114,22 @@ __global__ void __launch_bounds__(256) k_atom_qscores(QScoreArgs a) {
         at[0] = a.xyz[3 * (int64_t)self]; at[1] = a.xyz[3 * (int64_t)self + 1]; at[2] = a.xyz[3 * (int64_t)self + 2];
         // the neighbours: every other atom (by index; an atom on the same coordinate is one) of the 27 cells around the atom within the reach
         if (grid_range(cg, at, lo, hi))
-            for (int z = lo[2]; z <= hi[2]; ++z)
-                for (int y = lo[1]; y <= hi[1]; ++y) {
-                    const int64_t row = ((int64_t)z * cg.dim[1] + y) * cg.dim[0];
-                    const unsigned b = a.start[row + lo[0]], e = a.start[row + hi[0] + 1];      // (cells lo[0]..hi[0] of a row are consecutive)
-                    for (unsigned k0 = b; k0 < e; k0 += 64) {
-                        const unsigned k = k0 + (unsigned)lane;
-                        bool near = false;
-                        double x = 0.0, y2 = 0.0, z2 = 0.0;
-                        if (k < e) {
-                            x = a.sorted[3 * (size_t)k]; y2 = a.sorted[3 * (size_t)k + 1]; z2 = a.sorted[3 * (size_t)k + 2];
-                            near = a.sorted_index[k] != self && qs_d2(at, x, y2, z2) <= a.reach2;
-                        }
-                        const unsigned long long m = __ballot(near);
-                        const int pos = n_nb + __popcll(m & ((1ull << lane) - 1ull));
-                        if (near && pos < QS_STAGE) { s_x[wv][pos] = x; s_y[wv][pos] = y2; s_z[wv][pos] = z2; }
-                        n_nb += __popcll(m);
+            for_each_cell_row(cg, a.start, lo, hi, [&](unsigned b, unsigned e) {
+                for (unsigned k0 = b; k0 < e; k0 += 64) {
+                    const unsigned k = k0 + (unsigned)lane;
+                    bool near = false;
+                    double x = 0.0, y2 = 0.0, z2 = 0.0;
+                    if (k < e) {
+                        x = a.sorted[3 * (size_t)k]; y2 = a.sorted[3 * (size_t)k + 1]; z2 = a.sorted[3 * (size_t)k + 2];
+                        near = a.sorted_index[k] != self && qs_d2(at, x, y2, z2) <= a.reach2;
                     }
+                    const unsigned long long m = __ballot(near);
+                    const int pos = n_nb + __popcll(m & ((1ull << lane) - 1ull));
+                    if (near && pos < QS_STAGE) { s_x[wv][pos] = x; s_y[wv][pos] = y2; s_z[wv][pos] = z2; }
+                    n_nb += __popcll(m);
                 }
+                return false;
+            });
         else { lo[0] = lo[1] = lo[2] = 0; hi[0] = hi[1] = hi[2] = -1; }
     }
     __syncthreads();      // (the one barrier: every wave reaches it; the slices are only read from here on)
@@ -171,14 +169,12 @@ __global__ void __launch_bounds__(256) k_atom_qscores(QScoreArgs a) {
                 for (int j = 0; j < n_nb; ++j)      // (unrolled: four broadcast reads in flight instead of one LDS round trip per neighbour)
                     if (qs_d2(p, s_x[wv][j], s_y[wv][j], s_z[wv][j]) < d_self) acc = false;
             } else {
-                for (int z = lo[2]; z <= hi[2]; ++z)
-                    for (int y = lo[1]; y <= hi[1]; ++y) {
-                        const int64_t row = ((int64_t)z * cg.dim[1] + y) * cg.dim[0];
-                        const unsigned b = a.start[row + lo[0]], e = a.start[row + hi[0] + 1];
+                for_each_cell_row(cg, a.start, lo, hi, [&](unsigned b, unsigned e) {
 #pragma unroll 4
-                        for (unsigned j = b; j < e; ++j)      // (every lane reads the same atom)
-                            if (a.sorted_index[j] != self && qs_d2(p, a.sorted[3 * (size_t)j], a.sorted[3 * (size_t)j + 1], a.sorted[3 * (size_t)j + 2]) < d_self) acc = false;
-                    }
+                    for (unsigned j = b; j < e; ++j)      // (every lane reads the same atom)
+                        if (a.sorted_index[j] != self && qs_d2(p, a.sorted[3 * (size_t)j], a.sorted[3 * (size_t)j + 1], a.sorted[3 * (size_t)j + 2]) < d_self) acc = false;
+                    return false;
+                });
             }
             kept = __ballot(acc);
             if (__popcll(kept) >= a.min_points) break;      // (else the next level; the last level's accepted are kept, maybe none)

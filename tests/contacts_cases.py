@@ -1,7 +1,7 @@
 """Inputs of the crystal-contact edge tests (tests/test_contacts_host.py proves on the CPU that each reaches the corner it is named for,
 tests/test_gpu_contacts_edges.py runs them on the device), as functions of a seed, and a plain-Python restatement of the host's grid rule
-(make_cell_grid / query_grid in pdbeda_hip.hip).  The restatement only proves that a case reaches its corner; an expected result always
-comes from tests/contacts_checker.py."""
+(make_cell_grid / query_grid in pdb_eda_amd/csrc/pdbeda_cellgrid.h; tests/test_cellgrid_host.py holds the planner itself against it).
+The restatement only proves that a case reaches its corner; an expected result always comes from tests/contacts_checker.py."""
 import functools
 import itertools
 import math
@@ -17,7 +17,11 @@ MAX_SHIFT = 1 << 20             # check_images: the largest cell shift
 
 # ---- the grid rule ------------------------------------------------------------------------------------------------------------------------
 def cell_grid(lo, hi, cutoff, n_points):
-    """make_cell_grid: (edge, dims, n_cells, coarsening steps).  The same operations in the same order, in Python floats (fp64)."""
+    """make_cell_grid: (edge, dims, n_cells, coarsening steps), or None where it refuses -- an extent that is negative or not finite.  The same
+    operations in the same order, in Python floats (fp64)."""
+    extents = [float(hi[q]) - float(lo[q]) for q in range(3)]
+    if not all(e >= 0.0 and math.isfinite(e) for e in extents):
+        return None
     cap = float(min(1 << 22, max(4096, 8 * int(n_points))))
     edge = float(cutoff) * (1.0 + 1e-6)
     steps = 0

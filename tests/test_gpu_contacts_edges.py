@@ -240,6 +240,53 @@ def test_largest_shift_is_accepted_and_one_more_refused(gpu_ctx):
     assert sum(calls for calls, _ in launched.values()) == 0, launched          # (refused before any launch)
 
 
+# ---- 7b. extents that overflow fp64 ---------------------------------------------------------------------------------------------------------------
+def _within(seconds, call):
+    """call() on a thread of its own (the library releases the GIL): its result or exception, or a failure when it has not returned in time."""
+    import threading
+    box = {}
+
+    def work():
+        try:
+            box["value"] = call()
+        except BaseException as e:      # (handed to the test's thread)
+            box["error"] = e
+
+    t = threading.Thread(target=work, daemon=True)
+    t.start()
+    t.join(seconds)
+    assert not t.is_alive(), "the call has not returned after %g s" % seconds
+    if "error" in box:
+        raise box["error"]
+    return box["value"]
+
+
+@pytest.mark.parametrize("entry", ["coord", "crystal"])
+def test_an_overflowing_extent_is_refused_not_searched_for_ever(gpu_ctx, entry):
+    """Two query points at +-1e308 among ordinary ones: every coordinate is finite, the extent of their box is not.  No cell grid can be laid
+    over it (make_cell_grid once enlarged its edge for ever): PDBEDA_ERR_ARGUMENT that names the extent, before anything is staged or
+    launched, and the context answers the next ordinary call as before."""
+    from pdb_eda_amd import _native
+    if entry == "coord":
+        args = cases.coord_case("ordinary")
+        want = cases.expected_coord("ordinary")
+        call = lambda q: gpu_ctx.coord_contacts(q, *args[1:])
+    else:
+        args = cases.crystal_case("ordinary")
+        want = cases.expected_crystal("ordinary")[1:]
+        call = lambda q: gpu_ctx.crystal_contacts(q, *args[1:])[1:]
+    far = np.concatenate([[[1e308, 0.0, 0.0], [-1e308, 0.0, 0.0]], args[0][:6]])
+    assert np.all(np.isfinite(far))
+    gpu_ctx.profile_begin()
+    with pytest.raises(_native.PdbedaError) as e:
+        _within(20.0, lambda: call(far))
+    launched = gpu_ctx.profile_end()
+    print("%s: %s" % (entry, e.value))
+    assert e.value.code == ERR_ARGUMENT and "extent" in str(e.value) and "overflows" in str(e.value) and "along x" in str(e.value)
+    assert sum(calls for calls, _ in launched.values()) == 0, launched
+    assert_rows(_within(60.0, lambda: call(args[0])), want, entry + " after the refusal")
+
+
 # ---- 8. branches --------------------------------------------------------------------------------------------------------------------------------
 def test_branches_without_rows(gpu_ctx):
     query, poly, rot, ortho, cand, cutoff = cases.crystal_case("ordinary")
