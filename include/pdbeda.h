@@ -513,6 +513,56 @@ int pdbeda_model_density(pdbeda_map *like,
  * Synchronous; either output may be NULL. */
 int pdbeda_map_pair_moments(pdbeda_map *a, pdbeda_map *b, float b_floor, int64_t *n, double sums[5]);  /* Sa, Sb, Saa, Sbb, Sab */
 
+/* ---- from a map to a map through a neighbourhood: separable filters, local statistics ---- */
+/* A separable filter of a resident map (no reference counterpart; every other map-to-map call is voxel-wise).
+ * Output and domain: *out is a NEW map owned by the library on the geometry of `map` -- ownership and lifetime are those of
+ * pdbeda_map_combine's result (pdbeda_map_free).  The domain is ALL stored voxels ncrs, as for pdbeda_model_density.
+ * One axis with n = ncrs[axis] stored indices, I = crsInterval of that crs axis, radius R and 2R + 1 taps w:
+ *   y[i] = sum_{k = -R .. R} w[k + R] * x~[i + k]
+ * -- correlation form: w[0] multiplies the neighbour at i - R, taps need not be symmetric.  The sum is accumulated in fp64 from +0.0 in
+ * ascending k, one rounding for the product and one for the sum (unfused).  x~[j] is the wrap rule of getPointDensityFromCrs
+ * (cutils.pyx:125-145; what pdbeda_point_density and pdbeda_interp_density apply), on that axis alone: if j < 0 or j >= n then
+ * j -= floor(j / I) * I; afterwards an index with n <= j < I is absent and contributes 0.0, an index in [I, n) is read as stored.  So a
+ * full-cell map is filtered periodically however often R wraps round n, a cut-out sees zeros outside, a stored box larger than the cell
+ * reads its own copies.
+ * Three passes in the order c, r, s: the first reads the float32 map widened to fp64, the intermediates are fp64 and unrounded, the
+ * result is rounded ONCE to float32, to nearest.  The passes commute mathematically; the bits are defined by this order.
+ * PDBEDA_FILTER_RENORMALIZE: the fp64 result is divided by N = (W_c[c] * W_r[r]) * W_s[s] before the last rounding, W_axis[i] = sum_k
+ * w[k + R] * present(i + k) in the same order and arithmetic (the host computes the three arrays inside the call); where N > 0 is false
+ * the voxel is +0.0f.  A weighted mean then stays a mean at the faces of a cut-out.  Requires every tap >= 0.
+ * A lane owns its output: no atomic, no reduction across lanes, two calls agree to the bit.  Values of the map that are not finite are
+ * not screened; they propagate as IEEE arithmetic says (0 * inf is a NaN).
+ * PDBEDA_ERR_ARGUMENT before any launch: a radius outside 0 .. PDBEDA_FILTER_MAX_RADIUS, a NULL or non-finite tap, a negative tap
+ * under renormalisation, an unknown flag (also: an axis of 2^30 indices or more).  Synchronous; a failing call leaves the context usable
+ * and *out untouched.  Scratch: two fp64 volumes of the map's size from a self-releasing device arena, returned at the end of the call. */
+#define PDBEDA_FILTER_MAX_RADIUS 64
+#define PDBEDA_FILTER_RENORMALIZE 1u
+int pdbeda_map_filter(pdbeda_map *map,
+                      const double *taps_c, int32_t radius_c,   /* 2 * radius + 1 weights for the column axis */
+                      const double *taps_r, int32_t radius_r,
+                      const double *taps_s, int32_t radius_s,
+                      uint32_t flags, pdbeda_map **out);
+
+/* Windowed moments of one map, or of two: local mean, standard deviation and z-score of a (and b), and the local correlation of a and b.
+ * Taps as for pdbeda_map_filter, all >= 0.  F[.] is the three-pass filter above kept in fp64 WITHOUT the final rounding, applied to the
+ * channels a, a a, and with b also b, b b, a b (the products formed in fp64 from the float32 values, hence exact); N as above.  Per
+ * voxel, in unfused fp64:
+ *   Ea = F[a] / N, Eaa = F[a a] / N;  t = Eaa - Ea * Ea;  va = (t > 0) ? t : 0;  sa = sqrt(va);
+ *   d = (sa > std_floor) ? sa : std_floor;  z = (d > 0) ? ((double)a - Ea) / d : 0;      the same for b;
+ *   cov = F[a b] / N - Ea * Eb;  cc = (va > 0 && vb > 0) ? clamp(cov / sqrt(va * vb), -1, 1) : 0.
+ * Where N > 0 is false every output is 0: undefined cells are 0 and not NaN because the labelling calls refuse a map that holds a NaN
+ * and z_a exists to be labelled.  Each requested output is a NEW float32 map (rounded once) with the ownership of pdbeda_map_filter's;
+ * any output pointer may be NULL.  The maps are read once (the pass along c writes every channel).
+ * PDBEDA_ERR_ARGUMENT in addition to pdbeda_map_filter's cases: a negative tap, a negative or NaN std_floor, b of another shape or
+ * context, mean_b / std_b / cc requested without b.  Synchronous; a failing call leaves the context usable and every output pointer
+ * untouched.  Scratch: fp64 volumes of the map's size from a self-releasing device arena, returned at the end of the call -- the
+ * channels plus one: THREE for one map, SIX for a pair (the passes along r and s rotate the channels through the spare volume). */
+int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b /* may be NULL */,
+                           const double *taps_c, int32_t radius_c, const double *taps_r, int32_t radius_r,
+                           const double *taps_s, int32_t radius_s, double std_floor,
+                           pdbeda_map **mean_a, pdbeda_map **std_a, pdbeda_map **z_a,
+                           pdbeda_map **mean_b, pdbeda_map **std_b, pdbeda_map **cc);   /* any may be NULL */
+
 /* ---- aggregateCloud ------------------------------------------------------------------ */
 /* DensityAnalysis.aggregateCloud up to its statistics tail (densityAnalysis.py:571-731) as ONE call: the clouds of every
  * eligible atom (findAberrantBlobs, 603), the centroid-distance cut-off over all atoms (607), the best cloud and the pooled

@@ -124,6 +124,8 @@ _SIGS = {
     "pdbeda_atom_qscores": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_float, C.c_int32, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p]),
     "pdbeda_model_density": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, _p, C.POINTER(_p), _p]),
     "pdbeda_map_pair_moments": (C.c_int, [_p, _p, C.c_float, C.POINTER(_i64), _p]),
+    "pdbeda_map_filter": (C.c_int, [_p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_uint32, C.POINTER(_p)]),
+    "pdbeda_map_local_stats": (C.c_int, [_p, _p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_double, _p, _p, _p, _p, _p, _p]),
     "pdbeda_aggregate_cloud": (C.c_int, [_p, C.POINTER(CloudAtoms), C.c_float, C.c_double, C.POINTER(_p)]),
     "pdbeda_cloud_counts": (C.c_int, [_p, _p, _p]),
     "pdbeda_cloud_atom_rows": (C.c_int, [_p, _p, _p, _p, _p, _p]),
@@ -521,6 +523,19 @@ def radix_select(digit, bits, ranks):
     return out
 
 
+FILTER_MAX_RADIUS = 64           # PDBEDA_FILTER_MAX_RADIUS
+FILTER_RENORMALIZE = 1           # PDBEDA_FILTER_RENORMALIZE
+LOCAL_STATS_OUTPUTS = ("mean_a", "std_a", "z_a", "mean_b", "std_b", "cc")      # the output pointers of pdbeda_map_local_stats, in order
+
+
+def _filter_taps(*taps):
+    """The taps of the three axes as float64 arrays of odd length (a radius the library refuses is passed on as it is)."""
+    out = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in taps]
+    if any(len(t) % 2 == 0 for t in out):
+        raise ValueError("filter taps have an odd length, 2 * radius + 1")
+    return out
+
+
 class DeviceMap(object):
     """A density grid resident in HBM + its unit-cell basis."""
 
@@ -609,6 +624,37 @@ class DeviceMap(object):
         self._ctx.check(self._ctx._lib.pdbeda_map_pair_moments(self._h, other._h, C.c_float(-np.inf if floor is None else floor), C.byref(n), _ptr(sums)),
                         "pdbeda_map_pair_moments")
         return int(n.value), sums
+
+    @classmethod
+    def _made(cls, like, h):
+        """A map the library made on the geometry of ``like`` (handle ``h``)."""
+        self = cls.__new__(cls)
+        self._ctx, self._geom, self._keep, self.unique_shape = like._ctx, like._geom, None, like.unique_shape
+        self._h = h
+        return self
+
+    def filter(self, taps_c, taps_r, taps_s, renormalize=False):
+        """pdbeda_map_filter: a new resident map, this one filtered along c, r and s with the given taps (odd lengths 2 R + 1, correlation
+        form, the map's wrap rule at the faces); ``renormalize`` divides by the weight of the taps that met a voxel."""
+        taps = _filter_taps(taps_c, taps_r, taps_s)
+        h = C.c_void_p()
+        self._ctx.check(self._ctx._lib.pdbeda_map_filter(self._h, _ptr(taps[0]), len(taps[0]) // 2, _ptr(taps[1]), len(taps[1]) // 2, _ptr(taps[2]), len(taps[2]) // 2,
+                                                         FILTER_RENORMALIZE if renormalize else 0, C.byref(h)), "pdbeda_map_filter")
+        return type(self)._made(self, h)
+
+    def local_stats(self, other, taps_c, taps_r, taps_s, std_floor=0.0, want=None):
+        """pdbeda_map_local_stats: a dict of new resident maps out of ``mean_a``, ``std_a``, ``z_a`` and, with ``other``, ``mean_b``, ``std_b``,
+        ``cc`` -- all that apply, or the names in ``want``."""
+        names = LOCAL_STATS_OUTPUTS if other is not None else LOCAL_STATS_OUTPUTS[:3]
+        want = names if want is None else tuple(want)
+        if any(name not in LOCAL_STATS_OUTPUTS for name in want):
+            raise ValueError("local_stats outputs are %s" % ", ".join(LOCAL_STATS_OUTPUTS))
+        taps = _filter_taps(taps_c, taps_r, taps_s)
+        handles = dict((name, C.c_void_p()) for name in want)
+        refs = [C.byref(handles[name]) if name in handles else None for name in LOCAL_STATS_OUTPUTS]
+        self._ctx.check(self._ctx._lib.pdbeda_map_local_stats(self._h, other._h if other is not None else None, _ptr(taps[0]), len(taps[0]) // 2, _ptr(taps[1]), len(taps[1]) // 2,
+                                                              _ptr(taps[2]), len(taps[2]) // 2, C.c_double(float(std_floor)), *refs), "pdbeda_map_local_stats")
+        return dict((name, type(self)._made(self, handles[name])) for name in want)
 
     def abs_order_statistics(self, other, alpha, cut_a, cut_b, which, ranks=None):
         """Exact order statistics of |a| (which = 0) or |a + alpha * other| (which = 1) over the voxels of the unique box with

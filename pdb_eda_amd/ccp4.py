@@ -157,6 +157,31 @@ def modelRadii(bEff, nSigma=MODEL_N_SIGMA):
     return (float(nSigma) * np.sqrt(np.asarray(bEff, dtype=np.float64) / (8.0 * np.pi ** 2))).astype(np.float32)
 
 
+def gaussianTaps(sigmaVoxels, truncate=4.0):
+    """The weights of a Gaussian of ``sigmaVoxels`` grid steps for ``DensityMatrix.filtered`` / ``localStats``: radius int(truncate sigma +
+    0.5), exp(-x^2 / 2 sigma^2) divided by its sum -- ``scipy.ndimage.gaussian_filter``'s own weights.  sigma = 0 gives [1.0]."""
+    sigma = float(sigmaVoxels)
+    if not (sigma >= 0.0 and math.isfinite(sigma)) or not (float(truncate) >= 0.0 and math.isfinite(float(truncate))):
+        raise ValueError("gaussianTaps: sigma and truncate must be finite and >= 0")
+    radius = int(float(truncate) * sigma + 0.5)
+    if radius == 0 or sigma == 0.0:
+        return np.ones(1, dtype=np.float64)
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    w = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return w / w.sum()
+
+
+def boxTaps(halfWidth):
+    """2 halfWidth + 1 equal weights: the moving average (``scipy.ndimage.uniform_filter`` of that size)."""
+    h = int(halfWidth)
+    if h < 0:
+        raise ValueError("boxTaps: halfWidth must be >= 0")
+    return np.full(2 * h + 1, 1.0 / (2 * h + 1), dtype=np.float64)
+
+
+FILTER_MAX_RADIUS = _native.FILTER_MAX_RADIUS      # PDBEDA_FILTER_MAX_RADIUS of include/pdbeda.h
+
+
 class DensityHeader(object):
     """CCP4 header + derived cell geometry (ref ccp4.py:130-316).
 
@@ -520,6 +545,53 @@ class DensityMatrix(object):
         scale = cov / vb if vb > 0 else nan
         return {"n": n, "cc": min(1.0, max(-1.0, cov / math.sqrt(va * vb))) if va > 0 and vb > 0 else nan, "scale": scale,
                 "offset": (sa - scale * sb) / n if vb > 0 else nan}
+
+    # -- from a map to a map through a neighbourhood (no reference counterpart) ------------
+    def _made(self, device_map):
+        return DensityMatrix.fromDeviceMap(self.header, self.origin, device_map, self.pdbid, self._ctx)
+
+    def filtered(self, tapsC, tapsR, tapsS, renormalize=False):
+        """This map filtered along its column, row and section axes with the given taps (odd lengths, correlation form), as a device-made
+        DensityMatrix (``pdbeda_map_filter`` in include/pdbeda.h has the contract): the faces follow the map's own wrap rule -- a full
+        cell is periodic, a cut-out sees zeros --, and ``renormalize`` divides by the weight of the taps that met stored voxels (taps >= 0),
+        which keeps a weighted mean a mean at the faces of a cut-out."""
+        return self._made(self._map.filter(tapsC, tapsR, tapsS, renormalize))
+
+    def _gaussianTapsPerAxis(self, sigma, truncate, voxels):
+        """gaussianTaps for the three crs axes: ``sigma`` in grid steps (``voxels``) or in Angstrom over gridLength (orthogonal cells only)."""
+        if voxels:
+            sigmas = [float(sigma)] * 3
+        else:
+            if not self.header.orthogonal:
+                raise ValueError("a separable filter along the grid axes of a skewed cell is not isotropic: pass sigma in grid steps with voxels=True")
+            sigmas = [float(sigma) / self.header.gridLength[self.header.map2crs[k]] for k in range(3)]
+        taps = [gaussianTaps(s, truncate) for s in sigmas]
+        for axis, t in zip("crs", taps):
+            if len(t) // 2 > FILTER_MAX_RADIUS:
+                raise ValueError("a Gaussian of sigma %g reaches radius %d along %s, beyond the filter's largest radius %d" % (sigma, len(t) // 2, axis, FILTER_MAX_RADIUS))
+        return taps
+
+    def gaussianFilter(self, sigma, truncate=4.0, voxels=False, renormalize=True):
+        """This map smoothed by a Gaussian of ``sigma`` Angstrom (``voxels=True``: grid steps), cut off at ``truncate`` sigmas, as a
+        device-made DensityMatrix.  Angstrom are turned into grid steps per crs axis from ``gridLength``, on orthogonal cells only: a skewed
+        cell raises ValueError unless ``voxels=True``; so does a radius beyond PDBEDA_FILTER_MAX_RADIUS."""
+        taps = self._gaussianTapsPerAxis(sigma, truncate, voxels)
+        return self.filtered(taps[0], taps[1], taps[2], renormalize)
+
+    def localStats(self, other=None, taps=None, sigma=None, truncate=4.0, voxels=False, stdFloor=0.0):
+        """Windowed statistics of this map (``pdbeda_map_local_stats``): a dict of device-made DensityMatrix objects ``mean``, ``std`` and
+        ``z`` (the voxel's distance from its local mean in local standard deviations, never below ``stdFloor``), and with ``other`` also
+        ``meanOther``, ``stdOther`` and ``cc``, the local correlation of the two maps.  The window is ``taps`` (one array for all axes, or three,
+        all >= 0) or a Gaussian of ``sigma`` as in ``gaussianFilter``.  Cells the window finds nothing for are 0, never NaN."""
+        if (taps is None) == (sigma is None):
+            raise ValueError("localStats takes either taps or sigma")
+        if taps is None:
+            taps = self._gaussianTapsPerAxis(sigma, truncate, voxels)
+        elif np.ndim(taps[0]) == 0:
+            taps = [taps, taps, taps]
+        made = self._map.local_stats(None if other is None else other._map, taps[0], taps[1], taps[2], stdFloor)
+        names = {"mean_a": "mean", "std_a": "std", "z_a": "z", "mean_b": "meanOther", "std_b": "stdOther", "cc": "cc"}
+        return dict((names[key], self._made(device_map)) for key, device_map in made.items())
 
     # -- whole-map blobs ------------------------------------------------------------
     def createFullBlobList(self, cutoff):

@@ -34,6 +34,7 @@
 #include "pdbeda_partition.h"
 #include "pdbeda_qscore.h"
 #include "pdbeda_model.h"
+#include "pdbeda_filter.h"
 #include "pdbeda_blobshape.h"
 #include "pdbeda_blobnear.h"
 #include "pdbeda_basins.h"
@@ -3683,6 +3684,206 @@ extern "C" int pdbeda_map_pair_moments(pdbeda_map *a, pdbeda_map *b, float b_flo
     if (rc) return rc;
     if (n) *n = (int64_t)res[0];
     if (sums) memcpy(sums, res + 1, 40);
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// From a map to a map through a neighbourhood: the separable filter and the windowed moments (no reference counterpart; the contracts: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+struct FilterAxes {
+    FilterTaps taps[3];
+    std::vector<double> weight[3];      // W_axis[i] = sum_k w[k + R] * present(i + k), the kernels' order and arithmetic
+};
+
+// The checks both entry points share, then the taps and (want_w) the W arrays.  0, or the failure's status.
+static int filter_axes(pdbeda_ctx *ctx, const char *what, const Geom &g, const double *const taps[3], const int32_t radius[3], bool nonneg, bool want_w, FilterAxes *fa) {
+    static const char axis_name[3] = {'c', 'r', 's'};
+    for (int ax = 0; ax < 3; ++ax) {
+        const int R = radius[ax];
+        if (R < 0 || R > PDBEDA_FILTER_MAX_RADIUS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "%s: radius %d along %c is outside 0 .. %d", what, R, axis_name[ax], PDBEDA_FILTER_MAX_RADIUS);
+        if (!taps[ax]) return fail(ctx, PDBEDA_ERR_ARGUMENT, "%s: no taps along %c", what, axis_name[ax]);
+        if (!all_finite(taps[ax], 2 * R + 1)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "%s: a non-finite tap along %c", what, axis_name[ax]);
+        if (nonneg)
+            for (int k = 0; k <= 2 * R; ++k)
+                if (taps[ax][k] < 0.0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "%s: tap %d along %c is negative", what, k, axis_name[ax]);
+        if (g.ncrs[ax] <= 0 || g.ncrs[ax] >= (1 << 30) || g.crs_interval[ax] <= 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "%s: the map is empty, or an axis has 2^30 indices or more", what);
+    }
+    for (int ax = 0; ax < 3; ++ax) {
+        FilterTaps &t = fa->taps[ax];
+        memset(&t, 0, sizeof t);
+        t.radius = radius[ax];
+        memcpy(t.w, taps[ax], sizeof(double) * (size_t)(2 * radius[ax] + 1));
+        if (!want_w) continue;
+        const int n = g.ncrs[ax], I = g.crs_interval[ax], R = radius[ax];
+        fa->weight[ax].resize((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            double acc = 0.0;
+            for (int k = 0; k <= 2 * R; ++k) acc += t.w[k] * (wrap_axis(i - R + k, n, I) >= 0 ? 1.0 : 0.0);
+            fa->weight[ax][(size_t)i] = acc;
+        }
+    }
+    return 0;
+}
+
+// A pass of k_filter_line along r (axis 1) or s (axis 2).
+template <typename OUT>
+static void filter_line_launch(pdbeda_ctx *ctx, const Geom &g, int axis, const FilterTaps &t, const double *in, OUT *out, const double *w_c, const double *w_f, const double *w_o) {
+    const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
+    const int n = axis == 1 ? nr : ns, n_other = axis == 1 ? ns : nr;
+    const int64_t stride = axis == 1 ? (int64_t)nc : (int64_t)nc * nr, other_stride = axis == 1 ? (int64_t)nc * nr : (int64_t)nc;
+    const int col_tiles = (nc + FL_LANES - 1) / FL_LANES, chunks = (n + FL_CHUNK - 1) / FL_CHUNK;
+    const size_t lds = sizeof(double) * (size_t)(FL_CHUNK + 2 * t.radius) * FL_LANES;
+    PROF(ctx, axis == 1 ? "k_filter_line_r" : "k_filter_line_s");
+    hipLaunchKernelGGL(k_filter_line<OUT>, dim3((unsigned)((int64_t)col_tiles * chunks * n_other)), dim3(256), lds, ctx->stream, in, nc, n, g.crs_interval[axis], stride, n_other,
+                       other_stride, col_tiles, chunks, t, out, w_c, w_f, w_o, axis == 1 ? 1 : 0);
+}
+
+// The workgroups of the widest pass stay below 2^31.
+static bool filter_grid_fits(const Geom &g) {
+    const int64_t nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
+    const int64_t col = (nc + FL_LANES - 1) / FL_LANES, run = (nc + FC_RUN - 1) / FC_RUN;
+    const int64_t lim = 1ll << 31;
+    return run * ((nr * ns + FC_ROWS - 1) / FC_ROWS) < lim && col * ((nr + FL_CHUNK - 1) / FL_CHUNK) * ns < lim && col * ((ns + FL_CHUNK - 1) / FL_CHUNK) * nr < lim;
+}
+
+// A new map on the geometry of `like`, its voxels not yet written (the arena goes back to the pool with the map when the caller drops it).
+static int map_like(pdbeda_ctx *ctx, const char *site, const pdbeda_map *like, std::unique_ptr<pdbeda_map> *out, float **dens) {
+    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
+    m->ctx = ctx;
+    m->geom = like->geom;
+    m->n_vox = like->n_vox;
+    float *d = nullptr;
+    if (int rc = arena_carve(ctx, site, &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)m->n_vox); })) return rc;
+    *dens = d;
+    *out = std::move(m);
+    return 0;
+}
+
+// The launch graph: the W arrays (under renormalisation) in one row of scratch; k_filter_c<1> from the map into fp64 volume 0; k_filter_line<double> along r
+// into volume 1; k_filter_line<float> along s into the new map.  One wait.  Scratch: two fp64 volumes.
+extern "C" int pdbeda_map_filter(pdbeda_map *map, const double *taps_c, int32_t radius_c, const double *taps_r, int32_t radius_r, const double *taps_s, int32_t radius_s,
+                                 uint32_t flags, pdbeda_map **out) {
+    if (!map || !out) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = map->ctx;
+    if (flags & ~PDBEDA_FILTER_RENORMALIZE) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map filter: unknown flag 0x%x", flags);
+    const bool renorm = (flags & PDBEDA_FILTER_RENORMALIZE) != 0;
+    const Geom &g = map->geom;
+    const double *const taps[3] = {taps_c, taps_r, taps_s};
+    const int32_t radius[3] = {radius_c, radius_r, radius_s};
+    FilterAxes fa;
+    if (int rc = filter_axes(ctx, "map filter", g, taps, radius, renorm, renorm, &fa)) return rc;
+    if (map->n_vox <= 0 || !filter_grid_fits(g)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map filter: the map is empty or too large for one launch");
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
+    const size_t nv = (size_t)map->n_vox;
+    std::unique_ptr<pdbeda_map> m;
+    float *d_out = nullptr;
+    if (int rc = map_like(ctx, "map filter", map, &m, &d_out)) return rc;
+    double *d_vol = nullptr, *d_wc = nullptr, *d_wr = nullptr, *d_ws = nullptr;
+    const int rc = with_scratch(ctx, "map filter", [&](Carver &cv) {
+        cv.take(d_vol, 2 * nv);
+        cv.take(d_wc, renorm ? (size_t)nc : 0);
+        cv.take(d_wr, renorm ? (size_t)nr : 0);
+        cv.take(d_ws, renorm ? (size_t)ns : 0);
+    }, [&]() -> int {
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom)));
+        if (renorm) {
+            const H2DItem in[3] = {{d_wc, fa.weight[0].data(), 8 * (size_t)nc}, {d_wr, fa.weight[1].data(), 8 * (size_t)nr}, {d_ws, fa.weight[2].data(), 8 * (size_t)ns}};
+            HIP_TRY(ctx, h2d_row(ctx, in, 3));
+        }
+        const int64_t rows = (int64_t)nr * ns;
+        const int runs = (nc + FC_RUN - 1) / FC_RUN;
+        { PROF(ctx, "k_filter_c"); hipLaunchKernelGGL(k_filter_c<1>, dim3((unsigned)(runs * ((rows + FC_ROWS - 1) / FC_ROWS))), dim3(256), 0, st, map->dens, (const float *)nullptr, nc,
+                                                       g.crs_interval[0], rows, runs, fa.taps[0], d_vol, (int64_t)nv); }
+        filter_line_launch<double>(ctx, g, 1, fa.taps[1], d_vol, d_vol + nv, nullptr, nullptr, nullptr);
+        filter_line_launch<float>(ctx, g, 2, fa.taps[2], d_vol + nv, d_out, renorm ? d_wc : nullptr, renorm ? d_ws : nullptr, renorm ? d_wr : nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    });
+    if (rc) return rc;
+    m->dens = d_out;
+    m->own_dens = true;
+    ctx->live_handles++;
+    *out = m.release();
+    return PDBEDA_OK;
+}
+
+// The launch graph: the W arrays in one row of scratch; k_filter_c<2 or 5> reads a (and b) ONCE and writes every channel; per channel a pass along r and one
+// along s, through ONE spare volume -- channel k goes from volume k to volume k - 1 along r (channel 0 to the spare one, in ascending k) and back to volume k
+// along s (in descending k); k_local_finish writes the requested maps.  One wait.  Scratch: channels + 1 fp64 volumes, 3 for one map and 6 for a pair.
+extern "C" int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b, const double *taps_c, int32_t radius_c, const double *taps_r, int32_t radius_r, const double *taps_s,
+                                      int32_t radius_s, double std_floor, pdbeda_map **mean_a, pdbeda_map **std_a, pdbeda_map **z_a, pdbeda_map **mean_b, pdbeda_map **std_b,
+                                      pdbeda_map **cc) {
+    if (!a) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = a->ctx;
+    if (b) {
+        if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts");
+        if (a->n_vox != b->n_vox || memcmp(a->geom.ncrs, b->geom.ncrs, sizeof a->geom.ncrs) != 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different shapes");
+    } else if (mean_b || std_b || cc) {
+        return fail(ctx, PDBEDA_ERR_ARGUMENT, "local stats: an output of the second map is requested without a second map");
+    }
+    if (!(std_floor >= 0.0)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "local stats: std_floor is negative or NaN");
+    const Geom &g = a->geom;
+    const double *const taps[3] = {taps_c, taps_r, taps_s};
+    const int32_t radius[3] = {radius_c, radius_r, radius_s};
+    FilterAxes fa;
+    if (int rc = filter_axes(ctx, "local stats", g, taps, radius, true, true, &fa)) return rc;
+    if (a->n_vox <= 0 || !filter_grid_fits(g)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "local stats: the map is empty or too large for one launch");
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
+    const size_t nv = (size_t)a->n_vox;
+    const int n_ch = b ? 5 : 2;
+    pdbeda_map **const want[6] = {mean_a, std_a, z_a, mean_b, std_b, cc};
+    std::unique_ptr<pdbeda_map> made[6];
+    float *d_made[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 6; ++k)
+        if (want[k])
+            if (int rc = map_like(ctx, "local stats", a, &made[k], &d_made[k])) return rc;
+    double *d_vol = nullptr, *d_wc = nullptr, *d_wr = nullptr, *d_ws = nullptr;
+    const int rc = with_scratch(ctx, "local stats", [&](Carver &cv) {
+        cv.take(d_vol, (size_t)(n_ch + 1) * nv);
+        cv.take(d_wc, (size_t)nc);
+        cv.take(d_wr, (size_t)nr);
+        cv.take(d_ws, (size_t)ns);
+    }, [&]() -> int {
+        hipStream_t st = ctx->stream;
+        for (int k = 0; k < 6; ++k)
+            if (made[k]) HIP_TRY(ctx, h2d_one(ctx, made[k]->geom_dev, &made[k]->geom, sizeof(Geom)));
+        const H2DItem in[3] = {{d_wc, fa.weight[0].data(), 8 * (size_t)nc}, {d_wr, fa.weight[1].data(), 8 * (size_t)nr}, {d_ws, fa.weight[2].data(), 8 * (size_t)ns}};
+        HIP_TRY(ctx, h2d_row(ctx, in, 3));
+        const int64_t rows = (int64_t)nr * ns;
+        const int runs = (nc + FC_RUN - 1) / FC_RUN;
+        const dim3 grid_c((unsigned)(runs * ((rows + FC_ROWS - 1) / FC_ROWS)));
+        {
+            PROF(ctx, "k_filter_c");
+            if (b) hipLaunchKernelGGL(k_filter_c<5>, grid_c, dim3(256), 0, st, a->dens, b->dens, nc, g.crs_interval[0], rows, runs, fa.taps[0], d_vol, (int64_t)nv);
+            else hipLaunchKernelGGL(k_filter_c<2>, grid_c, dim3(256), 0, st, a->dens, (const float *)nullptr, nc, g.crs_interval[0], rows, runs, fa.taps[0], d_vol, (int64_t)nv);
+        }
+        auto vol = [&](int slot) { return d_vol + (size_t)(slot < 0 ? n_ch : slot) * nv; };
+        for (int k = 0; k < n_ch; ++k) filter_line_launch<double>(ctx, g, 1, fa.taps[1], vol(k), vol(k - 1), nullptr, nullptr, nullptr);
+        for (int k = n_ch - 1; k >= 0; --k) filter_line_launch<double>(ctx, g, 2, fa.taps[2], vol(k - 1), vol(k), nullptr, nullptr, nullptr);
+        LocalFinishArgs p;
+        p.a = a->dens; p.b = b ? b->dens : nullptr;
+        p.ch = d_vol; p.vol_stride = (int64_t)nv; p.n_vox = a->n_vox;
+        p.nc = nc; p.nr = nr;
+        p.w_c = d_wc; p.w_r = d_wr; p.w_s = d_ws;
+        p.std_floor = std_floor;
+        p.mean_a = d_made[0]; p.std_a = d_made[1]; p.z_a = d_made[2]; p.mean_b = d_made[3]; p.std_b = d_made[4]; p.cc = d_made[5];
+        { PROF(ctx, "k_local_finish"); hipLaunchKernelGGL(k_local_finish, dim3(grid_for(a->n_vox, 256, 8192)), dim3(256), 0, st, p); }
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    });
+    if (rc) return rc;
+    for (int k = 0; k < 6; ++k) {
+        if (!made[k]) continue;
+        made[k]->dens = d_made[k];
+        made[k]->own_dens = true;
+        ctx->live_handles++;
+        *want[k] = made[k].release();
+    }
     return PDBEDA_OK;
 }
 

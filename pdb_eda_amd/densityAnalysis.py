@@ -39,6 +39,12 @@ pdbfolder = './pdb_data/'
 modelBlur = 0.0
 modelSigmas = ccp4.MODEL_N_SIGMA
 
+# the local statistics of a map: the Gaussian window's standard deviation (A) and cut-off (standard deviations), and the floor under a local
+# standard deviation as a fraction of the whole map's stdDensity (a flat solvent region must not turn rounding noise into z-scores)
+localWindowSigma = 3.0
+localWindowTruncate = 3.0
+localStdFloorFraction = 0.25
+
 
 def setGlobals(params):
     """ref densityAnalysis.py:48-68."""
@@ -422,6 +428,8 @@ class DensityAnalysis(object):
     residueQScoreHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'mean_q_score', 'min_q_score', 'num_atoms_scored']
     atomModelCorrelationHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'rscc_model', 'rsr_model']
     residueModelCorrelationHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'rscc_model', 'rsr_model']
+    atomLocalHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'local_cc', 'local_z_diff', 'local_std_diff']
+    residueLocalHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'mean_local_cc', 'min_local_cc', 'extreme_local_z_diff']
 
     def __init__(self, pdbid, densityObj=None, diffDensityObj=None, biopdbObj=None, pdbObj=None):
         self.pdbid = pdbid
@@ -440,6 +448,7 @@ class DensityAnalysis(object):
         self._qScores = None
         self._model = None
         self._modelDifference = None
+        self._local = {}
         self._redBlobList = None
         self._blueBlobList = None
         self._greenPeakList = None
@@ -1609,3 +1618,98 @@ class DensityAnalysis(object):
         total = model.pairMoments(model)[1]
         return {"cc": fit["cc"], "scale": fit["scale"], "offset": fit["offset"], "n": fit["n"], "electrons_placed": self._model[1],
                 "electrons_found": total * self.densityObj.header.unitVolume}
+
+    # ---- local statistics: significance against the surroundings, local map-model correlation (no reference counterpart) ----
+    def _localTaps(self, densityObj):
+        """The Gaussian window of ``localWindowSigma`` A, cut off at ``localWindowTruncate`` standard deviations, as taps per crs axis: the
+        sigma in grid steps of an axis is sigma / gridLength of the cell axis it runs along.  On an orthogonal cell this is
+        ``DensityMatrix.gaussianFilter``'s window; on a skewed cell the window is a Gaussian along the cell axes, which is what a separable
+        filter can do there."""
+        header = densityObj.header
+        taps = [ccp4.gaussianTaps(localWindowSigma / header.gridLength[header.map2crs[k]], localWindowTruncate) for k in range(3)]
+        for axis, t in zip("crs", taps):
+            if len(t) // 2 > ccp4.FILTER_MAX_RADIUS:
+                raise ValueError("the local window reaches radius %d along %s, beyond the filter's largest radius %d" % (len(t) // 2, axis, ccp4.FILTER_MAX_RADIUS))
+        return taps
+
+    @property
+    def localDiffStats(self):
+        """``diffDensityObj.localStats`` under the module's window: ``mean``, ``std`` and ``z`` of the Fo-Fc map as device-made maps, the
+        local standard deviation never taken below ``localStdFloorFraction`` of the map's own."""
+        if "diff" not in self._local:
+            diff = self.diffDensityObj
+            self._local["diff"] = diff.localStats(taps=self._localTaps(diff), stdFloor=localStdFloorFraction * diff.stdDensity)
+        return self._local["diff"]
+
+    @property
+    def localZDiffObj(self):
+        """The Fo-Fc map in local standard deviations from its local mean: what a blob search cuts at +-3 to find density that is
+        significant against ITS surroundings, bulk solvent or protein core."""
+        return self.localDiffStats["z"]
+
+    def _localGreenRed(self):
+        if "blobs" not in self._local:
+            self._local["blobs"] = self.localZDiffObj.createFullBlobLists(3.0)
+        return self._local["blobs"]
+
+    @property
+    def localGreenBlobList(self):
+        """``createFullBlobList(3)`` on ``localZDiffObj``: the green blobs that stand out of their surroundings (totalDensity is in z units)."""
+        return self._localGreenRed()[0]
+
+    @property
+    def localRedBlobList(self):
+        """``createFullBlobList(-3)`` on ``localZDiffObj``."""
+        return self._localGreenRed()[1]
+
+    @property
+    def localModelCorrelationObj(self):
+        """The correlation of the 2Fo-Fc map with ``modelDensityObj`` inside the window around every voxel, as a device-made map in
+        [-1, 1] (0 where either map is locally flat): where on the grid the model explains the density, which the one number of
+        ``modelCorrelation()`` cannot say."""
+        if "cc" not in self._local:
+            dens = self.densityObj
+            made = dens._map.local_stats(self.modelDensityObj._map, *self._localTaps(dens), std_floor=0.0, want=("cc",))
+            self._local["cc"] = dens._made(made["cc"])
+        return self._local["cc"]
+
+    def _atomLocalValues(self, coord):
+        """(local_cc, local_z_diff, local_std_diff) at the coordinates, read by trilinear interpolation."""
+        xyz = np.asarray(coord, dtype=np.float64).reshape(-1, 3)
+        if len(xyz) == 0:
+            return np.zeros(0), np.zeros(0), np.zeros(0)
+        stats = self.localDiffStats
+        return (np.asarray(self.localModelCorrelationObj.getInterpolatedDensityFromXyz(xyz), dtype=np.float64),
+                np.asarray(stats["z"].getInterpolatedDensityFromXyz(xyz), dtype=np.float64), np.asarray(stats["std"].getInterpolatedDensityFromXyz(xyz), dtype=np.float64))
+
+    def calculateAtomLocalCorrelations(self):
+        """One row per atom (``atomLocalHeader``; the atoms and leading columns of ``calculateAtomModelCorrelations``): the local map-model
+        correlation, the local z-score of the Fo-Fc map and its local standard deviation, each read at the atom's position with
+        ``getInterpolatedDensityFromXyz``."""
+        cols, pick, lead = self._atomPick("")
+        cc, z, std = self._atomLocalValues(cols.coord[pick])
+        return self._rows(*lead, cols.bfactor[pick], cc, z, std)
+
+    def calculateResidueLocalCorrelations(self):
+        """One row per residue (``residueLocalHeader``): the mean and the minimum ``local_cc`` of its atoms and the ``local_z_diff`` of largest
+        magnitude among them, with its sign (None for a residue without atoms)."""
+        cols, lead, atom_rows, off = self._residuePick("", None, False)
+        cc, z, _ = self._atomLocalValues(cols.coord[atom_rows])
+        mean, low, extreme = [], [], []
+        for k in range(len(off) - 1):
+            mine, zs = cc[off[k]:off[k + 1]], z[off[k]:off[k + 1]]
+            mean.append(float(mine.mean()) if len(mine) else None)
+            low.append(float(mine.min()) if len(mine) else None)
+            extreme.append(float(zs[int(np.argmax(np.abs(zs)))]) if len(zs) else None)
+        return self._rows(*lead, mean, low, extreme)
+
+    def localSummary(self):
+        """The window (``window_sigma`` in A, ``window_truncate``, ``radius_c`` / ``radius_r`` / ``radius_s`` in grid steps), the numbers of
+        green and red blobs that are significant locally and globally, and the median and minimum ``local_cc`` over the atoms."""
+        radii = [len(t) // 2 for t in self._localTaps(self.diffDensityObj)]
+        cols, pick, _ = self._atomPick("")
+        cc = self._atomLocalValues(cols.coord[pick])[0]
+        return {"window_sigma": localWindowSigma, "window_truncate": localWindowTruncate, "radius_c": radii[0], "radius_r": radii[1], "radius_s": radii[2],
+                "num_local_green_blobs": len(self.localGreenBlobList), "num_local_red_blobs": len(self.localRedBlobList),
+                "num_green_blobs": len(self.greenBlobList), "num_red_blobs": len(self.redBlobList),
+                "median_atom_local_cc": float(np.median(cc)) if len(cc) else None, "min_atom_local_cc": float(cc.min()) if len(cc) else None}

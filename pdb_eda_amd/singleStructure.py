@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore", "model")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore", "model", "local")
 
 
 def numpyConverter(obj):
@@ -132,6 +132,13 @@ def _modelSummaryTable(analyzer, o):
     return [[summary[name] for name in _MODEL_SUMMARY]]
 
 
+def _localSummaryTable(analyzer, o):
+    summary = analyzer.localSummary()
+    return [[summary[name] for name in _LOCAL_SUMMARY]]
+
+
+_LOCAL_SUMMARY = ["window_sigma", "window_truncate", "radius_c", "radius_r", "radius_s", "num_local_green_blobs", "num_local_red_blobs", "num_green_blobs", "num_red_blobs",
+                  "median_atom_local_cc", "min_atom_local_cc"]
 _MODEL_SUMMARY = ["cc", "scale", "offset", "n", "electrons_placed", "electrons_found"]
 _QSCORE_SUMMARY = [cls + "_" + what for cls in ("all", "backbone", "side_chain", "water") for what in ("mean_q_score", "median_q_score", "num_atoms")]
 _PARTITION_SUMMARY = ["max_distance", "num_sd", "box_voxels", "asymmetric_unit_voxels", "symmetry_voxels", "unowned_voxels", "unowned_fraction", "unowned_mean",
@@ -187,6 +194,10 @@ TABLES = {
     ("model", "atom"): (lambda an: _DA.atomModelCorrelationHeader, lambda an, o: an.calculateAtomModelCorrelations(o["radius"] if o["radiusGiven"] else None)),
     ("model", "residue"): (lambda an: _DA.residueModelCorrelationHeader, lambda an, o: an.calculateResidueModelCorrelations(o["radius"] if o["radiusGiven"] else None)),
     ("model", "summary"): (lambda an: list(_MODEL_SUMMARY), _modelSummaryTable),
+    # (no reference counterpart: the Fo-Fc map against its LOCAL noise level, the 2Fo-Fc map against the model inside a window; no option applies)
+    ("local", "atom"): (lambda an: _DA.atomLocalHeader, lambda an, o: an.calculateAtomLocalCorrelations()),
+    ("local", "residue"): (lambda an: _DA.residueLocalHeader, lambda an, o: an.calculateResidueLocalCorrelations()),
+    ("local", "summary"): (lambda an: list(_LOCAL_SUMMARY), _localSummaryTable),
     ("statistics", "residue"): (lambda an: an.residueMetricsHeaderList, lambda an, o: an.residueMetrics()),
     ("statistics", "atom"): (lambda an: an.atomMetricsHeaderList, lambda an, o: _plainColumns(an.atomMetrics(), **_SYM)),
 }
@@ -196,9 +207,9 @@ def rows(analyzer, mode, level="atom", radius=None, numSD=None, type="", atomMas
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore | model;  level: atom | residue | domain | symmetry-atom
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore | model | local;  level: atom | residue | domain | symmetry-atom
     (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak, basin, shape and dipole) | atom-type (profile) | summary | blob
-    (partition) | summary (qscore: atom | residue | summary, no other option applies; model: atom | residue | summary, ``radius`` is the sphere's, by default the one of the statistics mode);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
+    (partition) | summary (qscore: atom | residue | summary, no other option applies; model: atom | residue | summary, ``radius`` is the sphere's, by default the one of the statistics mode; local: atom | residue | summary under the module's window, no other option applies);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
     (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
     maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default);  dipole: always the fused green
     and red lists (numSD default 3.0), ``radius`` is the largest gap between the two blobs when given (else 2.5 A);  radius default 3.5 elsewhere."""
