@@ -563,6 +563,48 @@ int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b /* may be NULL */,
                            pdbeda_map **mean_a, pdbeda_map **std_a, pdbeda_map **z_a,
                            pdbeda_map **mean_b, pdbeda_map **std_b, pdbeda_map **cc);   /* any may be NULL */
 
+/* ---- from a map to a map on ANOTHER grid: resampling under coordinate operators ---- */
+/* A resident map carried to the grid of `dst_geom` through one or more affine operators (no reference counterpart; every other call stays
+ * on the grid the map came with): two entries on one grid, the density under symmetry mates, an average over NCS copies, a finer box.
+ * Output and domain: *out is a NEW map on `dst_geom` -- ownership and lifetime are those of pdbeda_map_combine's result
+ * (pdbeda_map_free); the domain is ALL stored voxels of `dst_geom`.  `ops` holds n_ops rows of 12 doubles [R | t] in orthogonal Angstrom, laid
+ * out as for pdbeda_symmetry_atoms; an operator maps DESTINATION coordinates to SOURCE coordinates (a pull-back).
+ * The library is built with -ffp-contract=off and the contract fixes bits.  For every destination voxel v:
+ *  1. p = crs2xyz(dst, v) (DensityHeader.crs2xyzCoord's arithmetic, as pdbeda_crs2xyz).
+ *  2. for operator k in index order: x[i] = ((R[i][0] * p[0] + R[i][1] * p[1]) + R[i][2] * p[2]) + t[i], unfused (pdbeda_symmetry_atoms' arithmetic).
+ *  3. f = the fractional grid position of x in `src`, in crs order, as pdbeda_interp_density computes it.
+ *  4. the snap: per axis r = rint(f[j]); if |f[j] - r| <= 2^-26 then f[j] = r.  2^-26 of a grid step is far above the rounding of steps 1 to 3
+ *     at any realistic position and far below what a float32 result can show; a grid-compatible operator then lands ON voxels.
+ *  5. the sample and its validity:
+ *     order 0: the voxel at rint(f) (half to even) under the wrap rule of pdbeda_point_density; valid iff that voxel is stored.
+ *     order 1: b = floor(f), t = f - b; on an axis with t == 0 only index b is used and the fold along it is skipped, otherwise b and b + 1;
+ *              lerp(a, b, t) = a + t * (b - a) along c, then r, then s (pdbeda_interp_density's fold).
+ *     order 3: taps b - 1 .. b + 2 with the Catmull-Rom weights
+ *                w0 = ((-0.5 t + 1.0) t - 0.5) t,  w1 = ((1.5 t - 2.5) t) t + 1.0,  w2 = ((-1.5 t + 2.0) t + 0.5) t,  w3 = ((0.5 t - 0.5) t) t,
+ *              per axis y = ((w0 v0 + w1 v1) + w2 v2) + w3 v3, products and sums unfused, along c, then r, then s; with t == 0 only b is used.
+ *     orders 1 and 3 are valid iff every voxel the sample USES is stored (testValidCrs); a voxel of a skipped axis is neither read nor
+ *     required -- which differs from the `valid` output of pdbeda_interp_density.  Voxels that are not finite propagate.
+ *  6. by default the value is that of the FIRST valid operator and the count is 1 (0: no operator is valid); under PDBEDA_RESAMPLE_MEAN the
+ *     value is the fp64 sum over the valid operators, from +0.0 in index order, divided by their count.
+ *  7. count 0: the voxel is `fill`, its bits kept (a NaN is allowed), whatever `base` is.  Otherwise float32(value), or with `base`
+ *     float32((double)base[v] + alpha * value) -- two fp64 roundings, as pdbeda_map_combine.  *coverage, if asked for, is a NEW map of
+ *     float32(count).
+ * A lane owns its voxel: no atomic on a value, no reduction across lanes, two calls agree to the bit.  Whether a tap comes from a box staged
+ * in LDS or from a direct load changes no bit (PDBEDA_RESAMPLE_STAGE=0 in the environment turns staging off; A/B).
+ * counters (may be NULL): voxels with count > 0, voxels with count 0, (tile, operator) pairs served from LDS, pairs served by direct loads.
+ * PDBEDA_ERR_ARGUMENT before any launch: n_ops outside 1 .. PDBEDA_RESAMPLE_MAX_OPS; an order other than 0, 1, 3; an unknown flag; a
+ * non-finite entry of `ops` or a non-finite alpha; a `base` of another shape or context than the destination; a destination axis below 1 or of
+ * 2^30 indices or more; a source grid position of 2^29 steps or more -- evaluated on the host at the eight corners of the destination index
+ * box grown by one voxel, under every operator (the map is affine: the extreme sits at a corner).  Synchronous, one launch, one wait; a
+ * failing call leaves the context usable and every output pointer untouched. */
+#define PDBEDA_RESAMPLE_MAX_OPS 192
+#define PDBEDA_RESAMPLE_MEAN 1u        /* default: the first valid operator */
+int pdbeda_map_resample(pdbeda_map *src, const pdbeda_geometry *dst_geom,
+                        const double *ops /* n_ops x 12: rows of [R | t], orthogonal A, as pdbeda_symmetry_atoms */, int32_t n_ops,
+                        int32_t order /* 0 nearest, 1 trilinear, 3 tricubic (Catmull-Rom) */, uint32_t flags, float fill,
+                        pdbeda_map *base /* may be NULL; on dst_geom's shape */, double alpha,
+                        pdbeda_map **out, pdbeda_map **coverage /* may be NULL */, int64_t counters[4] /* may be NULL */);
+
 /* ---- aggregateCloud ------------------------------------------------------------------ */
 /* DensityAnalysis.aggregateCloud up to its statistics tail (densityAnalysis.py:571-731) as ONE call: the clouds of every
  * eligible atom (findAberrantBlobs, 603), the centroid-distance cut-off over all atoms (607), the best cloud and the pooled

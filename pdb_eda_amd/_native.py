@@ -126,6 +126,7 @@ _SIGS = {
     "pdbeda_map_pair_moments": (C.c_int, [_p, _p, C.c_float, C.POINTER(_i64), _p]),
     "pdbeda_map_filter": (C.c_int, [_p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_uint32, C.POINTER(_p)]),
     "pdbeda_map_local_stats": (C.c_int, [_p, _p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_double, _p, _p, _p, _p, _p, _p]),
+    "pdbeda_map_resample": (C.c_int, [_p, C.POINTER(Geometry), _p, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _p, C.c_double, C.POINTER(_p), C.POINTER(_p), _p]),
     "pdbeda_aggregate_cloud": (C.c_int, [_p, C.POINTER(CloudAtoms), C.c_float, C.c_double, C.POINTER(_p)]),
     "pdbeda_cloud_counts": (C.c_int, [_p, _p, _p]),
     "pdbeda_cloud_atom_rows": (C.c_int, [_p, _p, _p, _p, _p, _p]),
@@ -536,6 +537,11 @@ def _filter_taps(*taps):
     return out
 
 
+RESAMPLE_MAX_OPS = 192           # PDBEDA_RESAMPLE_MAX_OPS
+RESAMPLE_MEAN = 1                # PDBEDA_RESAMPLE_MEAN
+RESAMPLE_COUNTERS = ("covered", "uncovered", "stagedPairs", "directPairs")      # the counters of pdbeda_map_resample, in order
+
+
 class DeviceMap(object):
     """A density grid resident in HBM + its unit-cell basis."""
 
@@ -655,6 +661,27 @@ class DeviceMap(object):
         self._ctx.check(self._ctx._lib.pdbeda_map_local_stats(self._h, other._h if other is not None else None, _ptr(taps[0]), len(taps[0]) // 2, _ptr(taps[1]), len(taps[1]) // 2,
                                                               _ptr(taps[2]), len(taps[2]) // 2, C.c_double(float(std_floor)), *refs), "pdbeda_map_local_stats")
         return dict((name, type(self)._made(self, handles[name])) for name in want)
+
+    def resample(self, geometry, ops, order=1, mean=False, fill=0.0, base=None, alpha=1.0, coverage=False):
+        """pdbeda_map_resample: a new resident map on ``geometry`` -- every voxel of it pulled back into this map through the operators
+        ``ops`` (n x 12 rows of [R | t], destination to source coordinates) and read at ``order`` 0, 1 or 3: the first valid operator, or
+        with ``mean`` the average over the valid ones; ``fill`` where none is; with ``base`` (on ``geometry``) base + alpha * value.
+        Returns (map, coverage map or None); the map carries ``resample_counters``.  ``fill`` is passed as a float32 with its bits kept."""
+        ops = np.ascontiguousarray(ops, dtype=np.float64).reshape(-1, 12)
+        fill32 = C.c_float.from_buffer_copy(np.asarray(fill, dtype=np.float32).tobytes())
+        h, hc = C.c_void_p(), C.c_void_p()
+        ctr = np.zeros(4, dtype=np.int64)
+        self._ctx.check(self._ctx._lib.pdbeda_map_resample(self._h, C.byref(geometry), _ptr(ops) if len(ops) else None, len(ops), int(order), RESAMPLE_MEAN if mean else 0, fill32,
+                                                           base._h if base is not None else None, C.c_double(float(alpha)), C.byref(h), C.byref(hc) if coverage else None, _ptr(ctr)),
+                        "pdbeda_map_resample")
+        made = []
+        for handle in (h, hc) if coverage else (h,):
+            m = type(self).__new__(type(self))
+            m._ctx, m._geom, m._keep, m._h = self._ctx, geometry, None, handle
+            m.unique_shape = tuple(min(geometry.ncrs[k], geometry.xyz_interval[geometry.map2crs[k]]) for k in (2, 1, 0))
+            made.append(m)
+        made[0].resample_counters = dict(zip(RESAMPLE_COUNTERS, (int(v) for v in ctr)))
+        return made[0], (made[1] if coverage else None)
 
     def abs_order_statistics(self, other, alpha, cut_a, cut_b, which, ranks=None):
         """Exact order statistics of |a| (which = 0) or |a + alpha * other| (which = 1) over the voxels of the unique box with

@@ -182,6 +182,94 @@ def boxTaps(halfWidth):
 FILTER_MAX_RADIUS = _native.FILTER_MAX_RADIUS      # PDBEDA_FILTER_MAX_RADIUS of include/pdbeda.h
 
 
+# -- coordinate operators and destination headers for ``DensityMatrix.resampled`` (host numpy; no reference counterpart) --
+RESAMPLE_MAX_OPS = _native.RESAMPLE_MAX_OPS      # PDBEDA_RESAMPLE_MAX_OPS of include/pdbeda.h
+
+
+def _operator(op):
+    """An operator as a (3, 4) float64 array [R | t] (a 3 x 4 array, 12 numbers, or a row of ``PDBHeader.rotationMats``)."""
+    return np.array(op, dtype=np.float64).reshape(3, 4)
+
+
+def identityOperator():
+    """[I | 0]: x -> x."""
+    return np.hstack([np.eye(3), np.zeros((3, 1))])
+
+
+def invertOperator(op):
+    """The operator that undoes ``op``: x -> R^-1 (x - t)."""
+    op = _operator(op)
+    inv = np.linalg.inv(op[:, :3])
+    return np.hstack([inv, -inv.dot(op[:, 3:])])
+
+
+def composeOperators(a, b):
+    """``a`` after ``b``: x -> a(b(x))."""
+    a, b = _operator(a), _operator(b)
+    return np.hstack([a[:, :3].dot(b[:, :3]), a[:, :3].dot(b[:, 3:]) + a[:, 3:]])
+
+
+def applyOperator(op, xyz):
+    """``op`` on an (n, 3) array of coordinates."""
+    op = _operator(op)
+    return np.asarray(xyz, dtype=np.float64).reshape(-1, 3).dot(op[:, :3].T) + op[:, 3]
+
+
+def kabschOperator(fromXyz, toXyz, weights=None):
+    """(op, rmsd): the PROPER rotation and the shift with op(fromXyz) ~ toXyz in the (weighted) least-squares sense (Kabsch 1976), and
+    the root-mean-square distance that is left.  Where the SVD's best orthogonal matrix is a reflection, the sign of the smallest
+    singular direction is flipped: the result is always a rotation (det = +1)."""
+    p, q = np.asarray(fromXyz, dtype=np.float64).reshape(-1, 3), np.asarray(toXyz, dtype=np.float64).reshape(-1, 3)
+    if len(p) != len(q) or len(p) < 3:
+        raise ValueError("kabschOperator takes two lists of the same three or more points")
+    w = np.ones(len(p)) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != len(p) or not (w >= 0).all() or not w.sum() > 0:
+        raise ValueError("kabschOperator: one weight >= 0 per point, not all zero")
+    w = w / w.sum()
+    cp, cq = w.dot(p), w.dot(q)
+    u, _, vt = np.linalg.svd(((p - cp) * w[:, None]).T.dot(q - cq))
+    d = np.sign(np.linalg.det(vt.T.dot(u.T)))
+    rot = vt.T.dot(np.diag([1.0, 1.0, d if d != 0 else 1.0])).dot(u.T)
+    op = np.hstack([rot, (cq - rot.dot(cp)).reshape(3, 1)])
+    return op, float(np.sqrt(w.dot(((applyOperator(op, p) - q) ** 2).sum(axis=1))))
+
+
+def _headerFromFields(ncrs, crsStart, xyzInterval, xyzLength, angles, axes, spaceGroup=1):
+    """A mode-2 DensityHeader without file, symmetry records or statistics, through the constructor."""
+    t = tuple(int(v) for v in ncrs) + (2,) + tuple(int(v) for v in crsStart) + tuple(int(v) for v in xyzInterval) + tuple(float(v) for v in xyzLength) + \
+        tuple(float(v) for v in angles) + tuple(int(v) for v in axes) + (0.0, 0.0, 0.0, int(spaceGroup), 0, 0) + (0.0,) * 27 + (b"M", b"A", b"P", b" ") + (0, 0.0, 0)
+    return DensityHeader(t, b"", "<" if sys.byteorder == "little" else ">")
+
+
+def cellHeader(header):
+    """``header``'s cell and sampling with crsStart 0 and ncrs = crsInterval: the WHOLE unit cell, the destination of a symmetry expansion."""
+    return _headerFromFields(header.crsInterval, (0, 0, 0), header.xyzInterval, header.xyzLength, (header.alpha, header.beta, header.gamma),
+                             (header.col2xyz, header.row2xyz, header.sec2xyz), header.spaceGroup)
+
+
+def boxHeader(centre, halfWidth, spacing):
+    """An orthogonal P1 header (columns along x) whose stored box covers ``centre`` +- ``halfWidth`` (A; a number or one per axis) on a grid
+    of ``spacing`` A: crsStart lies on the grid through the coordinate origin, the cell is twice the box along every axis (nothing of
+    it wraps onto itself), and the cell lengths are float32 numbers -- they survive a CCP4 header --, so that the grid step is the
+    spacing to within 2^-24 of it."""
+    centre = np.asarray(centre, dtype=np.float64).reshape(3)
+    half = np.broadcast_to(np.asarray(halfWidth, dtype=np.float64), (3,))
+    step = np.broadcast_to(np.asarray(spacing, dtype=np.float64), (3,))
+    if not (np.isfinite(centre).all() and (half >= 0).all() and np.isfinite(half).all() and (step > 0).all() and np.isfinite(step).all()):
+        raise ValueError("boxHeader: a finite centre, halfWidth >= 0 and spacing > 0")
+    start, ncrs, interval, length = [], [], [], []
+    for k in range(3):
+        n = int(math.ceil(2.0 * half[k] / step[k])) + 4      # (enough for any placement of the box on the grid)
+        cell = float(np.float32(2 * n * step[k]))
+        g = cell / (2 * n)
+        pad = 1e-9 * (abs(centre[k]) + half[k] + 1.0)         # (above the rounding of the header's own origin and crs2xyzCoord)
+        first, last = int(math.floor((centre[k] - half[k] - pad) / g)), int(math.ceil((centre[k] + half[k] + pad) / g))
+        if last - first + 1 > n:
+            raise ValueError("boxHeader: the box does not fit the grid it was sized for")
+        start.append(first); ncrs.append(last - first + 1); interval.append(2 * n); length.append(cell)
+    return _headerFromFields(ncrs, start, interval, length, (90.0, 90.0, 90.0), (1, 2, 3))
+
+
 class DensityHeader(object):
     """CCP4 header + derived cell geometry (ref ccp4.py:130-316).
 
@@ -592,6 +680,29 @@ class DensityMatrix(object):
         made = self._map.local_stats(None if other is None else other._map, taps[0], taps[1], taps[2], stdFloor)
         names = {"mean_a": "mean", "std_a": "std", "z_a": "z", "mean_b": "meanOther", "std_b": "stdOther", "cc": "cc"}
         return dict((names[key], self._made(device_map)) for key, device_map in made.items())
+
+    # -- from a map to a map on ANOTHER grid: resampling under coordinate operators (no reference counterpart) --------
+    def resampled(self, header, ops=None, order=1, mean=False, fill=0.0, base=None, alpha=1.0, coverage=False):
+        """This map on the grid of ``header`` (a DensityHeader: another entry's, ``cellHeader`` / ``boxHeader``), as a device-made
+        DensityMatrix (``pdbeda_map_resample`` in include/pdbeda.h has the contract): every voxel of the destination is carried by the
+        operators ``ops`` ([R | t] rows from DESTINATION to SOURCE coordinates; None: the identity) into this map and read there at ``order``
+        0 (nearest), 1 (trilinear) or 3 (Catmull-Rom).  The first operator that finds stored voxels gives the value, or with ``mean`` all
+        that do are averaged; ``fill`` where none does.  With ``base`` (a DensityMatrix on ``header``) the result is base + alpha * value.
+        ``coverage=True`` returns (map, map of the number of operators that served each voxel).  ``resampleCounters`` of the result:
+        covered and uncovered voxels, (tile, operator) pairs read from staged boxes and directly."""
+        ops = identityOperator().reshape(1, 12) if ops is None else np.asarray(ops, dtype=np.float64).reshape(-1, 12)
+        made, cover = self._map.resample(header.geometry(), ops, order, mean, fill, None if base is None else base._map, alpha, coverage)
+        out = DensityMatrix.fromDeviceMap(header, header.origin, made, self.pdbid, self._ctx)
+        out.resampleCounters = made.resample_counters
+        return (out, DensityMatrix.fromDeviceMap(header, header.origin, cover, self.pdbid, self._ctx)) if coverage else out
+
+    def symmetryExpanded(self, rotationMats, header=None, order=1):
+        """This map under the space group's operators ``rotationMats`` (``PDBHeader.rotationMats``) on ``header`` (default: the whole unit
+        cell, ``cellHeader(self.header)``): the identity first, then the operators as given, the first that reaches stored density
+        serves a voxel; 0 where none does.  A symmetry operator is an isometry of the crystal, so pulling back through every one of them
+        finds each copy."""
+        ops = [identityOperator()] + [_operator(m) for m in rotationMats]
+        return self.resampled(cellHeader(self.header) if header is None else header, np.array(ops).reshape(-1, 12), order=order)
 
     # -- whole-map blobs ------------------------------------------------------------
     def createFullBlobList(self, cutoff):

@@ -35,6 +35,7 @@
 #include "pdbeda_qscore.h"
 #include "pdbeda_model.h"
 #include "pdbeda_filter.h"
+#include "pdbeda_resample.h"
 #include "pdbeda_blobshape.h"
 #include "pdbeda_blobnear.h"
 #include "pdbeda_basins.h"
@@ -3746,17 +3747,20 @@ static bool filter_grid_fits(const Geom &g) {
     return run * ((nr * ns + FC_ROWS - 1) / FC_ROWS) < lim && col * ((nr + FL_CHUNK - 1) / FL_CHUNK) * ns < lim && col * ((ns + FL_CHUNK - 1) / FL_CHUNK) * nr < lim;
 }
 
-// A new map on the geometry of `like`, its voxels not yet written (the arena goes back to the pool with the map when the caller drops it).
-static int map_like(pdbeda_ctx *ctx, const char *site, const pdbeda_map *like, std::unique_ptr<pdbeda_map> *out, float **dens) {
+// A new map on a geometry (map_like: that of `like`), its voxels not yet written (the arena goes back to the pool with the map when the caller drops it).
+static int map_on(pdbeda_ctx *ctx, const char *site, const Geom &geom, int64_t n_vox, std::unique_ptr<pdbeda_map> *out, float **dens) {
     std::unique_ptr<pdbeda_map> m(new pdbeda_map());
     m->ctx = ctx;
-    m->geom = like->geom;
-    m->n_vox = like->n_vox;
+    m->geom = geom;
+    m->n_vox = n_vox;
     float *d = nullptr;
     if (int rc = arena_carve(ctx, site, &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)m->n_vox); })) return rc;
     *dens = d;
     *out = std::move(m);
     return 0;
+}
+static int map_like(pdbeda_ctx *ctx, const char *site, const pdbeda_map *like, std::unique_ptr<pdbeda_map> *out, float **dens) {
+    return map_on(ctx, site, like->geom, like->n_vox, out, dens);
 }
 
 // The launch graph: the W arrays (under renormalisation) in one row of scratch; k_filter_c<1> from the map into fp64 volume 0; k_filter_line<double> along r
@@ -3883,6 +3887,106 @@ extern "C" int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b, const double
         made[k]->own_dens = true;
         ctx->live_handles++;
         *want[k] = made[k].release();
+    }
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// From a map to a map on ANOTHER grid through coordinate operators (no reference counterpart; the contract: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// PDBEDA_RESAMPLE_STAGE (A/B switch, read at every call so that one process can compare the paths): 0 -- every tap is a direct load; 2 -- the staged
+// boxes are not grown, so that lanes at a tile's rim leave them (a test's hook); anything else -- staged boxes.  Equal results to the bit.
+static int resample_stage_mode() {
+    const char *e = getenv("PDBEDA_RESAMPLE_STAGE");
+    return (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1);
+}
+
+// The launch graph: the host's checks; the arenas of the new maps; the operators, the two geometries and the zeroed counters in one row of scratch;
+// k_map_resample<order>, a workgroup per destination tile; the rows of counters, which the host adds up.  One wait.  *out and *coverage are written last.
+extern "C" int pdbeda_map_resample(pdbeda_map *src, const pdbeda_geometry *dst_geom, const double *ops, int32_t n_ops, int32_t order, uint32_t flags, float fill,
+                                   pdbeda_map *base, double alpha, pdbeda_map **out, pdbeda_map **coverage, int64_t counters[4]) {
+    if (!src || !dst_geom || !out || !ops) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = src->ctx;
+    if (n_ops < 1 || n_ops > PDBEDA_RESAMPLE_MAX_OPS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: n_ops must be 1 .. %d", PDBEDA_RESAMPLE_MAX_OPS);
+    if (order != 0 && order != 1 && order != 3) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: order %d is not 0, 1 or 3", order);
+    if (flags & ~PDBEDA_RESAMPLE_MEAN) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: unknown flag 0x%x", flags);
+    if (!all_finite(ops, 12 * (int64_t)n_ops)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: a non-finite operator entry");
+    if (!std::isfinite(alpha)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: alpha is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (dst_geom->ncrs[k] < 1 || dst_geom->ncrs[k] >= (1 << 30)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: destination axis %d has %d indices (1 .. 2^30 - 1)", k, dst_geom->ncrs[k]);
+    Geom gd;
+    if (int rc = fill_geom(ctx, dst_geom, &gd)) return rc;
+    const int64_t n_vox = (int64_t)gd.ncrs[0] * gd.ncrs[1] * gd.ncrs[2];
+    const int tiles_c = (gd.ncrs[0] + RS_C - 1) / RS_C, tiles_r = (gd.ncrs[1] + RS_R - 1) / RS_R, tiles_s = (gd.ncrs[2] + RS_S - 1) / RS_S;
+    const int64_t n_tiles = (int64_t)tiles_c * tiles_r * tiles_s;
+    if (n_vox >= (1ll << 32) || n_tiles >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: a destination of 2^32 voxels or 2^31 tiles or more");
+    if (base) {
+        if (base->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts");
+        if (base->n_vox != n_vox || memcmp(base->geom.ncrs, gd.ncrs, sizeof gd.ncrs) != 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: base is not of the destination's shape");
+    }
+    // every source grid position the kernel will cast: the map is affine, so its extreme over the destination box (grown by a voxel) sits at a corner
+    const Geom &gs = src->geom;
+    for (int k = 0; k < n_ops; ++k)
+        for (int j = 0; j < 8; ++j) {
+            double p[3], x[3], f[3];
+            crs2xyz(gd, (j & 1) ? gd.ncrs[0] : -1, (j & 2) ? gd.ncrs[1] : -1, (j & 4) ? gd.ncrs[2] : -1, p);
+            resample_apply(ops + 12 * k, p, x);
+            bool ok = std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]);
+            if (ok) {
+                xyz2frac(gs, x, f);
+                for (int q = 0; q < 3; ++q) ok = ok && std::fabs(f[q]) < (double)(1ll << 29);
+            }
+            if (!ok) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: operator %d carries the destination 2^29 grid steps or more from the source map's origin", k);
+        }
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<pdbeda_map> m, cov;
+    float *d_out = nullptr, *d_cov = nullptr;
+    if (int rc = map_on(ctx, "map resample", gd, n_vox, &m, &d_out)) return rc;
+    if (coverage)
+        if (int rc = map_on(ctx, "map resample", gd, n_vox, &cov, &d_cov)) return rc;
+    double *d_ops = nullptr;
+    unsigned long long *d_ctr = nullptr;
+    std::vector<unsigned long long> seen(4 * (size_t)RS_CTR_SLOTS, 0ull);
+    const int stage = resample_stage_mode();
+    const int rc = with_scratch(ctx, "map resample", [&](Carver &cv) { cv.take(d_ops, 12 * (size_t)n_ops); cv.take(d_ctr, 4 * (size_t)RS_CTR_SLOTS); }, [&]() -> int {
+        hipStream_t st = ctx->stream;
+        HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, 32 * (size_t)RS_CTR_SLOTS, st));
+        HIP_TRY(ctx, h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom)));
+        if (cov) HIP_TRY(ctx, h2d_one(ctx, cov->geom_dev, &cov->geom, sizeof(Geom)));
+        HIP_TRY(ctx, h2d_one(ctx, d_ops, ops, 96 * (size_t)n_ops));
+        ResampleArgs a;
+        a.src_geom = src->geom_dev; a.src = src->dens; a.dst_geom = m->geom_dev;
+        a.tiles_c = tiles_c; a.tiles_r = tiles_r;
+        a.ops = d_ops; a.n_ops = n_ops;
+        a.mean = (flags & PDBEDA_RESAMPLE_MEAN) ? 1 : 0; a.stage = stage;
+        a.fill = fill; a.base = base ? base->dens : nullptr; a.alpha = alpha;
+        a.out = d_out; a.coverage = d_cov; a.counters = d_ctr;
+        {
+            PROF(ctx, "k_map_resample");
+            if (order == 0) hipLaunchKernelGGL(k_map_resample<0>, dim3((unsigned)n_tiles), dim3(256), 0, st, a);
+            else if (order == 1) hipLaunchKernelGGL(k_map_resample<1>, dim3((unsigned)n_tiles), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(k_map_resample<3>, dim3((unsigned)n_tiles), dim3(256), 0, st, a);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        if (counters) HIP_TRY(ctx, d2h(ctx, seen.data(), d_ctr, 32 * (size_t)RS_CTR_SLOTS));
+        return 0;
+    });
+    if (rc) return rc;
+    if (counters)
+        for (int k = 0; k < 4; ++k) {
+            counters[k] = 0;
+            for (int slot = 0; slot < RS_CTR_SLOTS; ++slot) counters[k] += (int64_t)seen[4 * (size_t)slot + k];
+        }
+    m->dens = d_out;
+    m->own_dens = true;
+    ctx->live_handles++;
+    *out = m.release();
+    if (cov) {
+        cov->dens = d_cov;
+        cov->own_dens = true;
+        ctx->live_handles++;
+        *coverage = cov.release();
     }
     return PDBEDA_OK;
 }

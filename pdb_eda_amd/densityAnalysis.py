@@ -1713,3 +1713,73 @@ class DensityAnalysis(object):
                 "num_local_green_blobs": len(self.localGreenBlobList), "num_local_red_blobs": len(self.localRedBlobList),
                 "num_green_blobs": len(self.greenBlobList), "num_red_blobs": len(self.redBlobList),
                 "median_atom_local_cc": float(np.median(cc)) if len(cc) else None, "min_atom_local_cc": float(cc.min()) if len(cc) else None}
+
+    # ---- two entries on one grid, and the whole unit cell: maps resampled under coordinate operators (no reference counterpart) ----
+    def operatorTo(self, other, atomName="CA"):
+        """(op, rmsd, n): the proper rigid motion that carries THIS entry's coordinates onto ``other``'s -- ``ccp4.kabschOperator`` over the
+        atoms named ``atomName`` (all names when empty) that both entries have under the same chain, residue number and atom name -- the
+        root-mean-square distance it leaves, and the number of matched atoms.  It is the pull-back that ``compareMaps`` needs: a voxel of
+        this entry's grid is carried to the place in ``other`` that holds the same part of the molecule.  Fewer than three matches raise."""
+        def keyed(analyzer):
+            cols, pick, lead = analyzer._atomPick(atomName)
+            found = {}
+            for row, chain, number, name in zip(pick.tolist(), lead[1], lead[2], lead[4]):
+                found.setdefault((chain, number, name), row)      # (the first of alternate locations)
+            return cols, found
+        mine, here = keyed(self)
+        theirs, there = keyed(other)
+        shared = [key for key in here if key in there]
+        if len(shared) < 3:
+            raise ValueError("operatorTo: %d atoms named %r match by chain, residue number and name; three are needed" % (len(shared), atomName))
+        op, rmsd = ccp4.kabschOperator(np.asarray(mine.coord, dtype=np.float64)[[here[k] for k in shared]], np.asarray(theirs.coord, dtype=np.float64)[[there[k] for k in shared]])
+        return op, rmsd, len(shared)
+
+    def _operatorFor(self, other, operator):
+        if operator is None:
+            op, rmsd, _ = self.operatorTo(other)
+            return op, rmsd
+        return ccp4._operator(operator), None
+
+    def _otherOnMyGrid(self, other, operator, order):
+        """``other``'s 2Fo-Fc map on this entry's grid, NaN where it has nothing, with the operator and its rmsd."""
+        op, rmsd = self._operatorFor(other, operator)
+        return other.densityObj.resampled(self.densityObj.header, op.reshape(1, 12), order=order, fill=float("nan")), op, rmsd
+
+    def compareMaps(self, other, operator=None, order=1):
+        """``other``'s 2Fo-Fc map against this entry's, on THIS entry's grid: ``other``'s map is resampled under ``operator`` (this entry's
+        coordinates to ``other``'s; default: ``operatorTo(other)``) with a NaN fill and correlated with this one over the voxels it covers
+        (``DensityMatrix.correlate`` skips what is not finite).  A dict: ``n``, ``cc``, ``scale`` and ``offset`` of mine ~ scale * other +
+        offset, ``coveredFraction`` of this entry's stored voxels, ``rmsd`` of the operator (None for a given one) and ``operator``."""
+        moved, op, rmsd = self._otherOnMyGrid(other, operator, order)
+        fit = self.densityObj.correlate(moved)
+        counters = moved.resampleCounters
+        fit.update({"coveredFraction": counters["covered"] / float(counters["covered"] + counters["uncovered"]), "rmsd": rmsd, "operator": op})
+        return fit
+
+    def isomorphousDifferenceObj(self, other, operator=None, order=1):
+        """This entry's 2Fo-Fc map minus ``scale`` times ``other``'s, on this entry's grid, as a device-made DensityMatrix: ``scale`` from
+        ``compareMaps``, the subtraction inside ONE resample call (``base`` = this map, ``alpha`` = -scale); 0 where ``other`` has nothing.
+        ``createFullBlobList``, ``findPeaks`` and the basins take it as it is: what one entry has and the other lacks -- a ligand, a
+        moved loop."""
+        fit = self.compareMaps(other, operator, order)
+        if fit["scale"] != fit["scale"]:
+            raise RuntimeError("the other entry's map is constant where it covers this one: there is no scale to subtract it with")
+        return other.densityObj.resampled(self.densityObj.header, fit["operator"].reshape(1, 12), order=order, fill=0.0, base=self.densityObj, alpha=-fit["scale"])
+
+    def _expanded(self, densityObj, order):
+        return densityObj.symmetryExpanded([np.asarray(m, dtype=np.float64) for m in self.pdbObj.header.rotationMats], order=order)
+
+    @property
+    def expandedDensityObj(self):
+        """The 2Fo-Fc map over the WHOLE unit cell (``DensityMatrix.symmetryExpanded`` with the header's ``rotationMats``): PDBe maps are
+        cut-outs around the model, this is the density under every symmetry mate too."""
+        if "expanded" not in self._local:
+            self._local["expanded"] = self._expanded(self.densityObj, 1)
+        return self._local["expanded"]
+
+    @property
+    def expandedDiffDensityObj(self):
+        """The Fo-Fc map over the whole unit cell."""
+        if "expandedDiff" not in self._local:
+            self._local["expandedDiff"] = self._expanded(self.diffDensityObj, 1)
+        return self._local["expandedDiff"]
