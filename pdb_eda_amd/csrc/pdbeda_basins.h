@@ -22,7 +22,8 @@
 // Every accumulator is an integer (counts, fixed-point sums, offset sums, a 64-bit maximum), so the order the atomics land in
 // cannot change a bit.  No kernel here waits for another workgroup.
 #pragma once
-#include "pdbeda_peaks.h"
+#include "pdbeda_kernels.h"
+#include "pdbeda_wave.h"
 
 namespace pdbeda {
 
@@ -44,8 +45,8 @@ struct BasinArgs {
     double fix_mul;
 };
 
-// Stage a tile of 64 x 8 x 8 voxels and its one-voxel halo: a wave per (s, r) row, 64 lanes along c and two lanes more for the far
-// halo columns; five rows in flight per wave.  Outside the box: `outside`.
+// halo_stage (pdbeda_wave.h) once more, as a function of this header with one caller per instantiation: on the shared, force-inlined one
+// k_basin_parent took 26 VGPRs for 20 and ran 0.9 % slower, k_basin_sums 2.5 % slower.  Keep the two bodies alike.
 template <typename T>
 __device__ inline void basin_stage(T (*tile)[PK_HR][PK_HC], const T *__restrict__ src, int64_t pitch_c, int64_t pitch_r, int c0, int r0, int s0,
                                    int uc, int ur, int us, T outside) {
@@ -143,11 +144,12 @@ __global__ __launch_bounds__(256) void k_basin_resolve(int32_t *up, int64_t n, u
         up[v] = res;
     }
     if (__ballot(lost != 0u) == 0ull) return;             // (every map without a NaN)
-    for (int off = 32; off > 0; off >>= 1) lost += __shfl_xor(lost, off, 64);
+    lost = wave_fold<SegAdd>(lost);
     if ((threadIdx.x & 63) == 0) atomicAdd(orphans, (unsigned long long)lost);
 }
 
-// Inclusive sum over the lanes of a run: `head` is the first lane of this lane's run.
+// Inclusive sum over the lanes of a run: `head` is the first lane of this lane's run.  (seg_scan of pdbeda_wave.h names a run by an id and asks
+// with a shuffle per distance; on a form of it that took this predicate k_basin_sums ran 2.5 % slower.)
 template <typename T>
 __device__ inline T basin_seg_sum(T v, int lane, int head) {
 #pragma unroll

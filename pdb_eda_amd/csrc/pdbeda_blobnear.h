@@ -18,7 +18,10 @@
 //                       depend on the order it is folded in, so pruning cannot change it.
 //   k_blobnear_finish   one thread per blob: key -> t, voxel, partner voxel, and the partner's index out of b's labels.
 #pragma once
-#include "pdbeda_blobshape.h"
+#include <climits>
+
+#include "pdbeda_device.h"
+#include "pdbeda_wave.h"
 
 namespace pdbeda {
 
@@ -31,8 +34,6 @@ static constexpr int BN_MAX_OFFSETS = 16384, BN_MAX_COMPONENT = 127;
 static constexpr int BN_POS_BITS = 40;                                       // key = t << 40 | c-major position (below 2^31: whole_map_enqueue)
 static constexpr unsigned long long BN_NONE = ~0ull;                         // no pair: what the records start as
 static constexpr int BN_REFRESH = 64;                                        // table entries between two looks at the blob's best so far
-
-struct SegMin { template <typename T> __device__ static T op(T a, T b) { return a < b ? a : b; } };
 
 struct BlobNearArgs {
     const int32_t *crs;             // a's job: the voxel lists
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(256) k_blobnear_scan(BlobNearArgs a) {
     if (chunk_lo >= nv) return;      // (block-uniform)
     const int n_here = (int)min((int64_t)chunk, nv - chunk_lo);
     // every blob has a voxel, so the chunk covers at most n_here blobs
-    const int64_t b_first = blobshape_blob_at(a.off, a.cnt, chunk_lo), b_last = blobshape_blob_at(a.off, a.cnt, chunk_lo + n_here - 1);
+    const int64_t b_first = offsets_segment_at(a.off, a.cnt, chunk_lo), b_last = offsets_segment_at(a.off, a.cnt, chunk_lo + n_here - 1);
     const int nb_here = (int)(b_last - b_first + 1), n_slots = min(nb_here, BN_SLOTS);
     for (int i = tid; i <= nb_here; i += 256) {
         const int64_t rel = a.off[b_first + i] - v_lo - chunk_lo;      // (the first blob may start before the chunk, the last one end behind it)

@@ -24,6 +24,7 @@
 // maximum: no result depends on the order of the voxel list or of the atomics.
 #pragma once
 #include "pdbeda_kernels.h"
+#include "pdbeda_wave.h"
 
 namespace pdbeda {
 
@@ -48,34 +49,6 @@ struct BlobShapeArgs {
     double fix_mul;
 };
 
-struct SegMax { template <typename T> __device__ static T op(T a, T b) { return a > b ? a : b; } };
-struct SegAdd { template <typename T> __device__ static T op(T a, T b) { return a + b; } };
-
-// Inclusive segmented scan over the lanes of a wave: afterwards the LAST lane of a run of equal `seg` holds the run's fold.
-template <int N, typename T, typename Op> __device__ inline void seg_scan(T (&v)[N], int seg, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const bool take = __shfl_up(seg, d, 64) == seg && lane >= d;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const T o = __shfl_up(v[i], d, 64);
-            if (take) v[i] = Op::op(v[i], o);
-        }
-    }
-}
-__device__ inline bool seg_last(int seg, int lane) { return __shfl_down(seg, 1, 64) != seg || lane == 63; }
-
-// The blob (index in the list) of list position p: the last one whose offset is <= p.
-__device__ inline int64_t blobshape_blob_at(const int64_t *__restrict__ off, int64_t cnt, int64_t p) {
-    const int64_t v_lo = off[0];
-    int64_t lo = 0, hi = cnt - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (off[mid] - v_lo <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(256) k_blobshape_box(BlobShapeArgs a) {
     __shared__ int s_off[BS_CHUNK + 1];
     __shared__ int s_box[BS_SLOTS * BS_BOX];
@@ -85,7 +58,7 @@ __global__ void __launch_bounds__(256) k_blobshape_box(BlobShapeArgs a) {
     if (chunk_lo >= nv) return;      // (block-uniform)
     const int n_here = (int)min((int64_t)BS_CHUNK, nv - chunk_lo);
     // every blob has a voxel, so the chunk covers at most n_here blobs
-    const int64_t b_first = blobshape_blob_at(a.off, a.cnt, chunk_lo), b_last = blobshape_blob_at(a.off, a.cnt, chunk_lo + n_here - 1);
+    const int64_t b_first = offsets_segment_at(a.off, a.cnt, chunk_lo), b_last = offsets_segment_at(a.off, a.cnt, chunk_lo + n_here - 1);
     const int nb_here = (int)(b_last - b_first + 1), n_slots = min(nb_here, BS_SLOTS);
     for (int i = tid; i <= nb_here; i += 256) {
         const int64_t rel = a.off[b_first + i] - v_lo - chunk_lo;      // (the first blob may start before the chunk, the last one end behind it)
@@ -133,7 +106,7 @@ __global__ void __launch_bounds__(256) k_blobshape_widths(const int32_t *__restr
         const int32_t *x = box + b * BS_BOX;
         for (int q = 0; q < 3; ++q) w = max(w, (unsigned long long)((long long)x[3 + q] - (long long)~x[q] + 1));
     }
-    for (int d = 32; d > 0; d >>= 1) w = max(w, (unsigned long long)__shfl_xor((long long)w, d, 64));
+    w = wave_fold<SegMax>(w);
     if ((threadIdx.x & 63) == 0 && w > 0) atomicMax(widest, w);
 }
 

@@ -56,6 +56,7 @@ __global__ void __launch_bounds__(256) k_grid_scatter_indexed(const double *__re
 }
 
 // Inclusive scan of one value per lane across a 1024-lane block; `total` gets the block's sum.
+// (its wave scan is wave_incl_scan's loop, kept here: on the shared one k_contact_compact measured 0.4 % slower)
 __device__ inline unsigned block_scan_1024(unsigned x, unsigned *s_wave, unsigned &total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int off = 1; off < 64; off <<= 1) {

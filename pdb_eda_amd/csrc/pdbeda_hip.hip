@@ -28,17 +28,18 @@
 #include "pdbeda_kernels.h"
 #include "pdbeda_tile.h"
 #include "pdbeda_upload.h"
+// the feature headers, in alphabetical order: each one includes what it uses
+#include "pdbeda_basins.h"
+#include "pdbeda_blobnear.h"
+#include "pdbeda_blobshape.h"
 #include "pdbeda_contacts.h"
+#include "pdbeda_filter.h"
+#include "pdbeda_model.h"
+#include "pdbeda_partition.h"
 #include "pdbeda_peaks.h"
 #include "pdbeda_profiles.h"
-#include "pdbeda_partition.h"
 #include "pdbeda_qscore.h"
-#include "pdbeda_model.h"
-#include "pdbeda_filter.h"
 #include "pdbeda_resample.h"
-#include "pdbeda_blobshape.h"
-#include "pdbeda_blobnear.h"
-#include "pdbeda_basins.h"
 
 using namespace pdbeda;
 

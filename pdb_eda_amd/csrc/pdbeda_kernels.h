@@ -13,6 +13,7 @@
 // non-periodic, cutils.pyx:44-70).
 #pragma once
 #include "pdbeda_spherebox.h"
+#include "pdbeda_wave.h"
 
 namespace pdbeda {
 
@@ -212,15 +213,6 @@ __device__ inline int find_vol_by_key(const VolDesc *vols, int n, int64_t key) {
 }
 
 
-__device__ inline double wave_incl_scan(double x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        double y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
 // One wave, one non-empty mask word `mw` (lane = voxel): wrapped density fetch
 // (getPointDensityFromCrs), two wave prefix sums (rho, rho*lane), run sums by difference at the
 // run's first lane; writes one record per run at index rec0 + (run number inside the word).
@@ -384,12 +376,7 @@ __global__ void __launch_bounds__(256) k_run_index(Job job, const float *__restr
     const uint64_t m = mine ? job.mask[w] : 0ull;
     const uint32_t cnt = (uint32_t)popc64(run_starts(m));
     // block exclusive scan of cnt
-    uint32_t x = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
+    const uint32_t x = wave_incl_scan(cnt, lane);
     if (lane == 63) s_wsum[wv] = x;
     if (tid < WPB) s_mask[tid] = m;
     __syncthreads();
@@ -1188,12 +1175,7 @@ __global__ void __launch_bounds__(1024) k_blob_offsets(Job job, int64_t *__restr
     for (int base = 0; base < nb; base += 1024) {
         const int i = base + tid;
         long long v = i < nb ? job.b_n[i] : 0;
-        long long x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            long long y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
+        const long long x = wave_incl_scan(v, lane);
         if (lane == 63) s_w[wv] = x;
         __syncthreads();
         long long pre = s_carry;
@@ -1404,7 +1386,7 @@ __global__ void __launch_bounds__(1024) k_make_vols(const int32_t *__restrict__ 
         VolDesc vd;
         int64_t words = 0, keys = 0;
         if (i < n_groups) (void)vol_from_bounds(g_lo + 3 * i, g_hi + 3 * i, i, 0, 0, &vd, &words, &keys);      // (the bases: below, from the scan)
-        long long xw = words, xk = keys;
+        long long xw = words, xk = keys;      // (two sums in one pass of shuffles: not wave_incl_scan twice)
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             long long yw = __shfl_up(xw, d), yk = __shfl_up(xk, d);
@@ -1634,12 +1616,7 @@ __global__ void __launch_bounds__(256) k_atom_engine(Job job, const Geom *__rest
     for (int w0 = 0; w0 < W; w0 += 256) {   // (block-uniform trip count)
         const int w = w0 + tid;
         const uint32_t cnt = w < W ? (uint32_t)popc64(run_starts(s_m[w])) : 0u;
-        uint32_t x = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
+        const uint32_t x = wave_incl_scan(cnt, lane);
         if (lane == 63) s_wsum[wv] = x;
         __syncthreads();
         uint32_t pre = s_carry;
@@ -1872,7 +1849,7 @@ __global__ void __launch_bounds__(256) k_region_reduce(const Geom *__restrict__ 
         }
         const unsigned long long any_bad = __ballot(bad);
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
+        for (int off = 32; off > 0; off >>= 1) {      // (three sums in one pass of shuffles: not wave_fold_down three times)
             p += __shfl_down(p, off);
             q += __shfl_down(q, off);
             n += __shfl_down(n, off);
@@ -1941,7 +1918,7 @@ __global__ void __launch_bounds__(256) k_atom_region(const Geom *__restrict__ gp
         }
         const unsigned long long any_bad = __ballot(bad);
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
+        for (int off = 32; off > 0; off >>= 1) {      // (three sums in one pass of shuffles: not wave_fold_down three times)
             p += __shfl_down(p, off);
             q += __shfl_down(q, off);
             n += __shfl_down(n, off);
@@ -2095,8 +2072,7 @@ __global__ void __launch_bounds__(256) k_map_combine(const float *__restrict__ a
 // ------------------------------------------------------------------------------------
 __device__ inline double block_sum(double v, double *s_part) {
     const int lane = lane_id(), wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    wave_fold_down<SegAdd>(v);
     if (lane == 0) s_part[wv] = v;
     __syncthreads();
     double t = 0.0;
@@ -2148,8 +2124,7 @@ __global__ void __launch_bounds__(256) k_range_partials(const float *__restrict_
         take(v.x); take(v.y); take(v.z); take(v.w);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) take(x[(n4 << 2) + threadIdx.x]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const float o = __shfl_down(mx, off); mx = o > mx ? o : mx; }
+    wave_fold_down<SegMaxMine>(mx);
     if (lane_id() == 0) s_max[threadIdx.x >> 6] = mx;
     const double t = block_sum(acc, s_part);   // (its barrier also publishes s_max)
     if (threadIdx.x == 0) {
@@ -2162,8 +2137,7 @@ __global__ void __launch_bounds__(256) k_range_final(const double *__restrict__ 
     __shared__ double s_max[4];
     double acc = 0.0, mx = 0.0;
     for (int i = threadIdx.x; i < n_part; i += blockDim.x) { acc += part_sum[i]; mx = part_max[i] > mx ? part_max[i] : mx; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(mx, off); mx = o > mx ? o : mx; }
+    wave_fold_down<SegMaxMine>(mx);
     if (lane_id() == 0) s_max[threadIdx.x >> 6] = mx;
     const double t = block_sum(acc, s_part);
     if (threadIdx.x == 0) { out[0] = t; out[1] = fmax(fmax(s_max[0], s_max[1]), fmax(s_max[2], s_max[3])); }
@@ -2341,8 +2315,7 @@ __global__ void __launch_bounds__(256) k_np_final(const float *__restrict__ x, i
         for (int i = tid; i < rem; i += 256) { const float a = fabsf(s_tail[i]); if (a < INFINITY) { acc += (double)a; mx = (double)a > mx ? (double)a : mx; } else mx = INFINITY; }
         if (range_max)
             for (int64_t k = tid; k < n_full; k += 256) { const double q = range_max[k]; mx = q > mx ? q : mx; }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(mx, off); mx = o > mx ? o : mx; }
+        wave_fold_down<SegMaxMine>(mx);
         if ((tid & 63) == 0) s_rmax[tid >> 6] = mx;
         const double tail_sum = block_sum(acc, s_rpart);   // (its barrier also publishes s_rmax)
         if (tid == 0) {

@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(256) k_pair_moments(const float *__restrict__ 
         v[0] += 1.0; v[1] += x; v[2] += y; v[3] += x * x; v[4] += y * y; v[5] += x * y;
     }
     for (int k = 0; k < 6; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);      // (wave_fold's order; rolled: the kernel is slower with six unrolled folds)
     if ((threadIdx.x & 63) == 0)
         for (int k = 0; k < 6; ++k) s_part[threadIdx.x >> 6][k] = v[k];
     __syncthreads();

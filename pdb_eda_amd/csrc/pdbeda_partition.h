@@ -20,6 +20,7 @@
 // same way for every (voxel, atom) whichever tile or buffer run meets the pair, so owners do not depend on the tiling.
 #pragma once
 #include "pdbeda_contacts.h"
+#include "pdbeda_wave.h"
 
 namespace pdbeda {
 
@@ -54,13 +55,8 @@ __global__ void __launch_bounds__(256) k_partition_range(const float *__restrict
         const double v = fabs((double)dens[(s * n1 + r) * n0 + c]);
         if (isfinite(v) && v > best) best = v;
     }
-    for (int off = 32; off > 0; off >>= 1) best = fmax(best, __shfl_xor(best, off, 64));
+    best = wave_fold<SegFmax>(best);
     if ((threadIdx.x & 63) == 0 && best > 0.0) atomicMax(out, (unsigned long long)__double_as_longlong(best));
-}
-
-__device__ inline long long wave_sum_ll(long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 __global__ void __launch_bounds__(256) k_partition_tile(PartitionArgs a) {
@@ -135,8 +131,8 @@ __global__ void __launch_bounds__(256) k_partition_tile(PartitionArgs a) {
         }
     }
     // the unowned voxels of the workgroup: integers in any order, the squares in a fixed tree (lanes, then waves 0..3)
-    for (int k = 0; k < 6; ++k) un[k] = wave_sum_ll(un[k]);
-    for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
+    for (int k = 0; k < 6; ++k) un[k] = wave_fold<SegAdd>(un[k]);
+    sq = wave_fold<SegAdd>(sq);
     if (lane == 0) {
         for (int k = 0; k < 6; ++k) s_un[wv][k] = un[k];
         s_sq[wv] = sq;

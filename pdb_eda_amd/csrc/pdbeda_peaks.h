@@ -15,12 +15,9 @@
 // position: the order of the list.  Keys are unique, so the list does not depend on the order the atomics landed in.
 #pragma once
 #include "pdbeda_device.h"
+#include "pdbeda_wave.h"
 
 namespace pdbeda {
-
-static constexpr int PK_C = 64, PK_R = 8, PK_S = 8;          // voxels of a tile: a wave reads one row of 64 along c (256 B)
-static constexpr int PK_HC = PK_C + 2, PK_HR = PK_R + 2, PK_HS = PK_S + 2;
-static constexpr int PK_THREADS = 256;
 
 static constexpr int PK_SCAN_THREADS = 1024;
 
@@ -101,35 +98,11 @@ __global__ __launch_bounds__(PK_THREADS) void k_peak_stencil(PeakJobArgs a, cons
     const unsigned tile_id = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     const float no_voxel = __uint_as_float(0x7fc00000u);   // outside the box: never read by a comparison (the bounds tests above), NaN all the same
     if (threadIdx.x < 2) { s_count[threadIdx.x] = 0u; s_tested[threadIdx.x] = 0u; }
-    // stage the tile and its halo: a wave per (s, r) row, 64 lanes along c (coalesced) and two lanes more for the far halo
-    // columns; five rows in flight per wave (the loads of a batch are issued before the first LDS store)
-    constexpr int WAVES = PK_THREADS / 64, ROWS_PER_WAVE = PK_HS * PK_HR / WAVES, BATCH = 5;
-    static_assert(PK_HS * PK_HR % WAVES == 0 && ROWS_PER_WAVE % BATCH == 0, "the halo rows divide among the waves in whole batches");
-    for (int b = 0; b < ROWS_PER_WAVE; b += BATCH) {
-        float v[BATCH], w[BATCH];
-#pragma unroll
-        for (int k = 0; k < BATCH; ++k) {
-            const int row = wave + WAVES * (b + k);
-            const int hs = row / PK_HR, hr = row - hs * PK_HR;
-            const int s = s0 - 1 + hs, r = r0 - 1 + hr;
-            const bool row_in = (unsigned)s < (unsigned)us && (unsigned)r < (unsigned)ur;   // wave-uniform
-            const float *src = dens + ((int64_t)(row_in ? s : 0) * a.nr + (row_in ? r : 0)) * a.nc;
-            const int c = c0 - 1 + lane, c2 = c0 + 63 + lane;
-            v[k] = (row_in && (unsigned)c < (unsigned)uc) ? src[c] : no_voxel;
-            w[k] = (lane < 2 && row_in && c2 < uc) ? src[c2] : no_voxel;
-        }
-#pragma unroll
-        for (int k = 0; k < BATCH; ++k) {
-            const int row = wave + WAVES * (b + k);
-            const int hs = row / PK_HR, hr = row - hs * PK_HR;
-            tile[hs][hr][lane] = v[k];
-            if (lane < 2) tile[hs][hr][64 + lane] = w[k];
-        }
-    }
+    halo_stage<float>(tile, dens, a.nc, a.nr, c0, r0, s0, uc, ur, us, no_voxel);
     __syncthreads();
     const int c = c0 + lane;
     unsigned tested[2] = {0u, 0u};
-    for (int q = wave; q < PK_R * PK_S; q += WAVES) {
+    for (int q = wave; q < PK_R * PK_S; q += PK_THREADS / 64) {
         const int ss = q / PK_R, rr = q - ss * PK_R;
         const int r = r0 + rr, s = s0 + ss;
         if (r >= ur || s >= us) continue;                 // wave-uniform

@@ -19,6 +19,7 @@
 // sample (the atom's own position, which every atom keeps) and by ref[0]: the one-pass variances then lose nothing to cancellation.
 #pragma once
 #include "pdbeda_partition.h"
+#include "pdbeda_wave.h"
 
 namespace pdbeda {
 
@@ -83,19 +84,6 @@ struct QScoreArgs {
 __device__ inline double qs_d2(const double p[3], double x, double y, double z) {
     const double dx = p[0] - x, dy = p[1] - y, dz = p[2] - z;
     return (dx * dx + dy * dy) + dz * dz;
-}
-
-__device__ inline double wave_sum_d(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ inline double wave_min_d(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ inline double wave_max_d(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
 }
 
 __global__ void __launch_bounds__(256) k_atom_qscores(QScoreArgs a) {
@@ -188,8 +176,8 @@ __global__ void __launch_bounds__(256) k_atom_qscores(QScoreArgs a) {
             v = interp_trilinear(g, a.dens, f, &ok);
         }
         const double d = mine ? v - shift : 0.0;
-        const double s_v = wave_sum_d(mine ? v : 0.0), s_d = wave_sum_d(d), s_dd = wave_sum_d(d * d);
-        const double mn = wave_min_d(mine ? v : INFINITY), mx = wave_max_d(mine ? v : -INFINITY);
+        const double s_v = wave_fold<SegAdd>(mine ? v : 0.0), s_d = wave_fold<SegAdd>(d), s_dd = wave_fold<SegAdd>(d * d);
+        const double mn = wave_fold<SegFmin>(mine ? v : INFINITY), mx = wave_fold<SegFmax>(mine ? v : -INFINITY);
         all_valid = all_valid && __ballot(mine && !ok) == 0ull;
         all_finite = all_finite && __ballot(mine && !isfinite(v)) == 0ull;
         if (n_k > 0) {
