@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "pdbeda_kernels.h"
+#include "pdbeda_stage.h"
 #include "pdbeda_tile.h"
 #include "pdbeda_upload.h"
 // the feature headers, in alphabetical order: each one includes what it uses
@@ -80,10 +81,7 @@ struct pdbeda_ctx {
     // device -> host results are staged through pinned memory: the copies are truly asynchronous (a copy into pageable
     // memory blocks inside the runtime, where no watchdog can see it) and land in the caller's buffers when ctx_sync()
     // has seen the stream drain
-    char *pinned = nullptr;
-    size_t pinned_cap = 0, pinned_used = 0;
-    struct Pending { void *dst; size_t off, bytes; };
-    std::vector<Pending> pending;
+    PinnedBlock pinned;
     // file -> device uploads (pdbeda_map_upload_file): the chunks of a map go through the process's upload engine (reader threads
     // with pinned chunks and copy streams of their own); what a context keeps is one event per reader, recorded
     // behind the reader's copies of the map and waited for by the context's stream
@@ -132,7 +130,7 @@ static void ctx_release_device(pdbeda_ctx *ctx, bool lent_too) {
     }
     if (ctx->partials) (void)hipFree(ctx->partials);
     if (ctx->dev_stage) (void)hipFree(ctx->dev_stage);
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    if (ctx->pinned.base) (void)hipHostFree(ctx->pinned.base);
     for (int k = 0; k < pdbeda_ctx::MAX_READERS; ++k)
         if (ctx->reader_ev[k]) (void)hipEventDestroy(ctx->reader_ev[k]);
     for (auto &r : ctx->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -260,7 +258,7 @@ static int fail(pdbeda_ctx *ctx, int code, const char *fmt, ...) {
     va_end(ap);
     // results of a failed call are never delivered.  The staging regions are NOT handed out again here: copies queued by an
     // earlier call (a sphere batch's staged inputs) may still read them -- only ctx_sync(), which has drained the stream, rewinds
-    if (ctx) ctx->pending.clear();
+    if (ctx) ctx->pinned.drop_deliveries();
     if (ctx && ctx->timed_out) return PDBEDA_ERR_TIMEOUT;   // (the watchdog's message stays)
     if (ctx) ctx->err = buf;
     return code;
@@ -312,36 +310,17 @@ static hipError_t copy_by_kernel(pdbeda_ctx *ctx, void *dst, const void *src, si
 
 static hipError_t ctx_sync(pdbeda_ctx *ctx) {
     const hipError_t e = ctx_wait(ctx);
-    if (e == hipSuccess)
-        for (const auto &p : ctx->pending) memcpy(p.dst, ctx->pinned + p.off, p.bytes);
-    ctx->pending.clear();
-    ctx->pinned_used = 0;
+    if (e == hipSuccess) ctx->pinned.rewind_delivering(); else ctx->pinned.rewind();
     ctx->dev_stage_used = 0;
     return e;
 }
 
-// The pinned block's ONE allocator: everything staged in it -- inputs the host writes, results kernels write -- is a take, handed out until the next
-// ctx_sync() rewinds the block.  A take occupies whole 64-byte lines ((bytes + 63) & ~63: an EMPTY take occupies none and shares its address with the
-// next one; a caller whose kernel wants a place of its own for an empty item takes a byte), so the room left is always a multiple of 64 and "N bytes
-// fit" is plainly N <= pinned_room().
-static inline size_t pinned_span(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
-static inline size_t pinned_room(const pdbeda_ctx *ctx) { return ctx->pinned_cap - ctx->pinned_used; }      // (0 without a block)
-// The next ctx_sync() delivers `bytes` at `from` (inside a take) to `dst`.
-static inline void pinned_deliver(pdbeda_ctx *ctx, const char *from, void *dst, size_t bytes) { ctx->pending.push_back({dst, (size_t)(from - ctx->pinned), bytes}); }
-// nullptr: no block, or no room.  deliver_to: where the next ctx_sync() copies the take's bytes (nothing for an empty take).
-static char *pinned_take(pdbeda_ctx *ctx, size_t bytes, void *deliver_to = nullptr) {
-    if (!ctx->pinned || pinned_span(bytes) > pinned_room(ctx)) return nullptr;
-    char *p = ctx->pinned + ctx->pinned_used;
-    if (deliver_to && bytes) pinned_deliver(ctx, p, deliver_to, bytes);
-    ctx->pinned_used += pinned_span(bytes);
-    return p;
-}
-// A caller whose launch failed (or that found it cannot use what it took) hands back `first` and every take after it, deliveries included: the block
-// and the pending list are as they were before `first` was taken -- a failed call delivers nothing.
-static void pinned_untake(pdbeda_ctx *ctx, const char *first) {
-    ctx->pinned_used = (size_t)(first - ctx->pinned);
-    while (!ctx->pending.empty() && ctx->pending.back().off >= ctx->pinned_used) ctx->pending.pop_back();
-}
+// The pinned block's allocator is PinnedBlock (pdbeda_stage.h); these forward to the context's block.
+static inline size_t pinned_span(size_t bytes) { return PinnedBlock::span(bytes); }
+static inline size_t pinned_room(const pdbeda_ctx *ctx) { return ctx->pinned.room(); }
+static inline void pinned_deliver(pdbeda_ctx *ctx, const char *from, void *dst, size_t bytes) { ctx->pinned.deliver(from, dst, bytes); }
+static inline char *pinned_take(pdbeda_ctx *ctx, size_t bytes, void *deliver_to = nullptr) { return ctx->pinned.take(bytes, deliver_to); }
+static inline void pinned_untake(pdbeda_ctx *ctx, const char *first) { ctx->pinned.untake(first); }
 // The copy between a take and device memory (by kernel, or PDBEDA_COPY_KERNELS=0: by the runtime); a take whose copy could not be launched is handed back.
 static hipError_t stage_copy(pdbeda_ctx *ctx, char *stage, void *dev, size_t bytes, bool to_device) {
     void *dst = to_device ? dev : stage, *src = to_device ? stage : dev;
@@ -359,8 +338,6 @@ static hipError_t d2h(pdbeda_ctx *ctx, void *dst, const void *src, size_t bytes)
     if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
     return e;
 }
-
-static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 static int arena_get_raw(pdbeda_ctx *ctx, size_t bytes, Arena *out);
 
@@ -426,20 +403,6 @@ void Arena::put() {
     }
 }
 
-// The rule: an arena's layout and its size come from ONE carve -- a callable that takes a Carver & and names every piece.  arena_carve() (or
-// with_scratch() on top of it) runs the carve on a null base for the size and again on the arena's base; never size an arena by hand.
-struct Carver {
-    char *base;
-    size_t off = 0;
-    explicit Carver(char *b) : base(b) {}
-    template <typename T> T *take(size_t n) {
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += align_up(n * sizeof(T));
-        return p;
-    }
-    template <typename T> void take(T *&p, size_t n) { p = take<T>(n); }      // (T from the pointer it fills)
-};
-
 // An arena sized by `carve` and laid out by the same carve, moved into *out (what *out held goes back to the pool first).  A failure -- a second pass
 // that does not end where the first did: the carve read something that changed in between -- leaves *out as it was and nothing behind.
 // The ownership rule: an Arena is released by its owner going away.  An explicit put() stands only where the TIME of the release is the point, with a
@@ -468,7 +431,7 @@ static inline unsigned grid_for(int64_t n, int block, int64_t cap = 1 << 20) {
 // staging block as on the device; one by one from the caller's memory when the block has no room (the caller waits before it
 // returns either way).
 struct H2DItem { void *dst; const void *src; size_t bytes; };
-static hipError_t h2d_row(pdbeda_ctx *ctx, const H2DItem *items, int n, size_t max_span = 256u << 10) {
+static hipError_t h2d_row(pdbeda_ctx *ctx, const H2DItem *items, int n, size_t max_span = H2D_ROW_SPAN) {
     char *lo = nullptr, *hi = nullptr;
     for (int k = 0; k < n; ++k) {
         if (items[k].bytes == 0) continue;
@@ -479,8 +442,8 @@ static hipError_t h2d_row(pdbeda_ctx *ctx, const H2DItem *items, int n, size_t m
     if (!lo) return hipSuccess;
     const size_t span = (size_t)(hi - lo);
     if (char *stage = span <= max_span ? pinned_take(ctx, span) : nullptr) {
-        for (int k = 0; k < n; ++k)
-            if (items[k].bytes) memcpy(stage + ((char *)items[k].dst - lo), items[k].src, items[k].bytes);
+        const StagedRow row{stage, lo, span};
+        for (int k = 0; k < n; ++k) row.put(items[k].dst, items[k].src, items[k].bytes);
         return stage_copy(ctx, stage, lo, span, true);
     }
     for (int k = 0; k < n; ++k) {
@@ -499,10 +462,16 @@ static hipError_t h2d_one(pdbeda_ctx *ctx, void *dst, const void *src, size_t by
 // Several results of one call, complete after the next ctx_sync(): packed on the device (k_pack) and brought over in ONE copy
 // when they fit the staging blocks, else one by one (d2h).  Items with a null destination or no bytes are skipped.
 struct D2HItem { void *dst; const void *src; size_t bytes; };
+static hipError_t d2h_each(pdbeda_ctx *ctx, const D2HItem *items, int n) {      // (one by one)
+    for (int k = 0; k < n; ++k)
+        if (items[k].dst && items[k].bytes)
+            if (const hipError_t e = d2h(ctx, items[k].dst, items[k].src, items[k].bytes)) return e;
+    return hipSuccess;
+}
 static hipError_t d2h_many(pdbeda_ctx *ctx, const D2HItem *items, int n_items) {
     int live[8], n = 0;
     size_t total = 0;
-    bool packable = (ctx->dev_stage != nullptr || copy_kernels()) && ctx->pinned != nullptr;
+    bool packable = (ctx->dev_stage != nullptr || copy_kernels()) && ctx->pinned.base != nullptr;
     for (int k = 0; k < n_items; ++k) {
         if (!items[k].dst || items[k].bytes == 0) continue;
         if (n == 8 || (items[k].bytes & 3u) || ((uintptr_t)items[k].src & 3u)) { packable = false; break; }
@@ -533,12 +502,7 @@ static hipError_t d2h_many(pdbeda_ctx *ctx, const D2HItem *items, int n_items) {
         if (via_dev_stage) ctx->dev_stage_used += total;
         return hipSuccess;
     }
-    for (int k = 0; k < n_items; ++k) {
-        if (!items[k].dst || items[k].bytes == 0) continue;
-        const hipError_t e = d2h(ctx, items[k].dst, items[k].src, items[k].bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return d2h_each(ctx, items, n_items);
 }
 
 // ------------------------------------------------------------------------------------
@@ -562,6 +526,32 @@ static const T *pinned_in(pdbeda_ctx *ctx, const T *src, size_t count) {
     if (p) memcpy(p, src, bytes);
     return reinterpret_cast<const T *>(p);
 }
+// A result slot {host, count[, dev]}: `count` items for the caller's `host` array, and a device piece -- carve()d with the call's scratch, or given -- for
+// when the block has no room.  at(): where the kernel writes -- the pinned take if pinned_out grants one, else the device piece; nullptr when the caller
+// passed no array (the kernel skips that result).  finish(): the copy, queued only when the device piece was used.  Call at() in the order of the takes.
+template <typename T>
+struct Result {
+    T *host;
+    size_t count;
+    T *dev = nullptr, *pin = nullptr;
+    void carve(Carver &cv) { cv.take(dev, count); }
+    T *at(pdbeda_ctx *ctx) { return !host ? nullptr : (pin = pinned_out(ctx, host, count)) ? pin : dev; }
+    hipError_t finish(pdbeda_ctx *ctx) const { return host && !pin ? d2h(ctx, host, dev, sizeof(T) * count) : hipSuccess; }
+};
+// An input slot, the same way: send() stages the caller's array in the block when pinned_in grants a take, else copies it into the device piece; the kernel reads at `at`.
+template <typename T>
+struct Input {
+    const T *host;
+    size_t count;
+    T *dev = nullptr;
+    const T *at = nullptr;
+    void carve(Carver &cv) { cv.take(dev, count); }
+    hipError_t send(pdbeda_ctx *ctx) {
+        if ((at = pinned_in(ctx, host, count)) != nullptr) return hipSuccess;
+        at = dev;
+        return h2d_one(ctx, dev, host, sizeof(T) * count);
+    }
+};
 
 // Scratch for one call, laid out by `carve` (see Carver), which fills the caller's pointers; `fn` uses them; the stream is drained before the arena goes back.
 template <typename Carve, typename Fn>
@@ -623,9 +613,9 @@ extern "C" int pdbeda_ctx_create_on_stream(int device_id, void *hip_stream, pdbe
     }
     // (coherent + mapped, explicitly: with PDBEDA_COPY_KERNELS the staged results are WRITTEN BY KERNELS into this block and read by the host after the
     //  stream wait -- or after a hipStreamQuery poll under the watchdog --, which is only right for coherent host memory)
-    if (hipHostMalloc((void **)&ctx->pinned, 4 << 20, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) ctx->pinned_cap = 4 << 20;   // (without it results are copied directly)
+    if (hipHostMalloc((void **)&ctx->pinned.base, PINNED_BLOCK_BYTES, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) ctx->pinned.cap = PINNED_BLOCK_BYTES;   // (without it results are copied directly)
     else (void)hipGetLastError();
-    if (ctx->pinned_cap && hipMalloc((void **)&ctx->dev_stage, 2 << 20) == hipSuccess) ctx->dev_stage_cap = 2 << 20; else { ctx->dev_stage = nullptr; (void)hipGetLastError(); }
+    if (ctx->pinned.cap && hipMalloc((void **)&ctx->dev_stage, DEV_STAGE_BYTES) == hipSuccess) ctx->dev_stage_cap = DEV_STAGE_BYTES; else { ctx->dev_stage = nullptr; (void)hipGetLastError(); }
     ctx->debug_poison = env_set("PDBEDA_DEBUG_POISON");
     ctx->debug_shrink_totals = env_set("PDBEDA_DEBUG_SHRINK_TOTALS");
     if (const char *v = getenv("PDBEDA_DEBUG_EDGE_CAP")) ctx->debug_edge_cap = atoll(v);
@@ -752,52 +742,78 @@ static int stats_carve(pdbeda_map *m, Arena *out, double *&chunk_sums) {
 static bool stats_carries_geom(const pdbeda_map *m) { return m->n_vox / NP_CHUNK > 0; }      // (the chain's first launch exists: it brings the geometry along when asked to)
 static void range_apply(pdbeda_map *m, const double range[2]);
 
+// A map the library makes, until it is the caller's: the record on a geometry and ONE arena that holds the device's copy of the geometry and (voxels)
+// the grid, which the call then writes; make() sets dens and own_dens of a map with voxels (a borrowing maker sets dens itself).  geometry_up() queues
+// the geometry's copy (it reads the record: a wait comes before the call returns); publish() counts the handle and writes *out, when nothing can fail
+// any more.  A map that is never published goes back to the pool with its arena when the MadeMap goes away.
+struct MadeMap {
+    std::unique_ptr<pdbeda_map> m;
+    float *dens = nullptr;
+    double stats[2] = {0.0, 0.0}, range[2] = {0.0, 0.0};      // an uploaded map's mean / std and range, from the wait that completes the upload
+    Arena stats_scratch;
+    int make(pdbeda_ctx *ctx, const char *site, const Geom &geom, int64_t n_vox, bool voxels = true) {
+        m.reset(new pdbeda_map());
+        m->ctx = ctx;
+        m->geom = geom;
+        m->n_vox = n_vox;
+        const int rc = arena_carve(ctx, site, &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); if (voxels) cv.take(dens, (size_t)n_vox); });
+        if (rc == 0 && voxels) { m->dens = dens; m->own_dens = true; }
+        return rc;
+    }
+    int make_like(const char *site, const pdbeda_map *like) { return make(like->ctx, site, like->geom, like->n_vox); }
+    hipError_t geometry_up() { return h2d_one(m->ctx, m->geom_dev, &m->geom, sizeof(Geom)); }
+    hipError_t stats_up(bool with_geom) {      // (queued behind the upload; filled by the next wait)
+        double *chunk_sums = nullptr;
+        if (stats_carve(m.get(), &stats_scratch, chunk_sums) != 0) return hipErrorOutOfMemory;
+        return stats_enqueue(m.get(), chunk_sums, stats, range, true, with_geom) != 0 ? hipErrorUnknown : hipSuccess;
+    }
+    void stats_out(double *mean, double *std) { range_apply(m.get(), range); if (mean) *mean = stats[0]; if (std) *std = stats[1]; }
+    void publish(pdbeda_map **out) { m->ctx->live_handles++; *out = m.release(); }
+};
+
+// A second map beside a grid (a first map's, or the one a call is about to make): of the call's context, and of the grid's shape (units: the unique
+// boxes count too).  0, or the refusal; `what` words the refusal of the shape.
+static int same_grid(pdbeda_ctx *ctx, const Geom &g, int64_t n_vox, const pdbeda_map *b, const char *what = "maps of different shapes", bool units = false) {
+    if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts");
+    if (b->n_vox != n_vox || memcmp(g.ncrs, b->geom.ncrs, sizeof g.ncrs) != 0 || (units && memcmp(g.unique_ncrs, b->geom.unique_ncrs, sizeof g.unique_ncrs) != 0))
+        return fail(ctx, PDBEDA_ERR_ARGUMENT, "%s", what);
+    return 0;
+}
+
 static int map_create(pdbeda_ctx *ctx, const float *host, const float *dev, const pdbeda_geometry *geom, pdbeda_map **out, double *mean = nullptr, double *std = nullptr) {
     if (!ctx || !geom || !out || (!host && !dev)) return PDBEDA_ERR_ARGUMENT;
     *out = nullptr;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
-    m->ctx = ctx;
-    int rc = fill_geom(ctx, geom, &m->geom);
+    Geom g;
+    int rc = fill_geom(ctx, geom, &g);
     if (rc) return rc;
-    m->n_vox = (int64_t)geom->ncrs[0] * geom->ncrs[1] * geom->ncrs[2];
-    if (m->n_vox >= (1ll << 32)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grids of 2^32 voxels or more are not supported");
+    const int64_t n_vox = (int64_t)geom->ncrs[0] * geom->ncrs[1] * geom->ncrs[2];
+    if (n_vox >= (1ll << 32)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grids of 2^32 voxels or more are not supported");
     if (dev && ((uintptr_t)dev & 15u) != 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "device density pointer must be 16-byte aligned");
-    float *d = nullptr;
-    rc = arena_carve(ctx, "map_create", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); if (host) cv.take(d, (size_t)m->n_vox); });
+    MadeMap made;
+    rc = made.make(ctx, "map_create", g, n_vox, host != nullptr);
     if (rc) return rc;
+    pdbeda_map *m = made.m.get();
     hipError_t e = hipSuccess;
     if (host) {
-        m->dens = d;
-        m->own_dens = true;
         // (measured, round 5: the same grid through the upload engine -- readers memcpy chunks into their pinned slots -- takes twice as long as the runtime's
         //  own copy from pageable memory, which pins the caller's pages and lets the engine read them in place: 0.6 against 0.3 ms for 8 MB)
-        e = hipMemcpyAsync(d, host, sizeof(float) * (size_t)m->n_vox, hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(made.dens, host, sizeof(float) * (size_t)n_vox, hipMemcpyHostToDevice, ctx->stream);
     } else {
-        m->dens = dev;
+        m->dens = dev;      // (borrowed: the map owns its geometry alone)
     }
     // (an uploaded map with its statistics from the same wait: see upload_file_impl; the geometry rides in the statistics' first launch then)
     const bool with_stats = (mean || std) && host && e == hipSuccess;
-    const bool geom_in_stats = with_stats && stats_carries_geom(m.get());
-    if (e == hipSuccess && !geom_in_stats) e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
-    double st_host[2] = {0.0, 0.0}, range[2] = {0.0, 0.0}, *chunk_sums = nullptr;
-    Arena scratch;
-    if (with_stats) {
-        if (stats_carve(m.get(), &scratch, chunk_sums) != 0) e = hipErrorOutOfMemory;
-        else if (stats_enqueue(m.get(), chunk_sums, st_host, range, true, geom_in_stats) != 0) e = hipErrorUnknown;
-    }
+    const bool geom_in_stats = with_stats && stats_carries_geom(m);
+    if (e == hipSuccess && !geom_in_stats) e = made.geometry_up();
+    if (with_stats && e == hipSuccess) e = made.stats_up(geom_in_stats);      // (a failed geometry copy stays the call's error)
     {
         const hipError_t e2 = ctx_sync(ctx);  // host buffers may be released on return
         if (e == hipSuccess) e = e2;
     }
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "map upload: %s", hipGetErrorString(e));
-    if (with_stats) {
-        range_apply(m.get(), range);
-        if (mean) *mean = st_host[0];
-        if (std) *std = st_host[1];
-    }
-    ctx->live_handles++;
-    *out = m.release();
+    if (with_stats) made.stats_out(mean, std);
+    made.publish(out);
     return PDBEDA_OK;
 }
 
@@ -935,19 +951,17 @@ static int upload_file_impl(pdbeda_ctx *ctx, const char *path, int64_t offset, i
     UploadEngine *engine = upload_engine(ctx->device);
     if (engine->n_readers < 1) { close(fd); return fail(ctx, PDBEDA_ERR_MEMORY, "no reader (pinned chunks, copy stream, thread) for the file upload"); }
     if (!ensure_reader_events(ctx, engine)) { close(fd); return fail(ctx, PDBEDA_ERR_MEMORY, "no event for the file upload"); }
-    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
-    m->ctx = ctx;
-    int rc = fill_geom(ctx, geom, &m->geom);
-    float *d = nullptr;
-    if (rc == 0) rc = arena_carve(ctx, "map upload from file", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)n_vox); });
+    Geom g;
+    MadeMap made;
+    int rc = fill_geom(ctx, geom, &g);
+    if (rc == 0) rc = made.make(ctx, "map upload from file", g, n_vox);
     if (rc) { close(fd); return rc; }
-    m->n_vox = n_vox;
-    m->dens = d;
-    m->own_dens = true;
+    pdbeda_map *m = made.m.get();
+    float *d = made.dens;
     const char *why = nullptr;
     hipError_t e = engine_copy(ctx, engine, fd, offset, nullptr, (char *)d, need, &why);   // (first: the stream is idle, its query says so at once)
-    const bool geom_in_stats = (mean || std) && stats_carries_geom(m.get());      // (the statistics' first launch brings the geometry along: a copy launch less)
-    if (e == hipSuccess && !geom_in_stats) e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
+    const bool geom_in_stats = (mean || std) && stats_carries_geom(m);      // (the statistics' first launch brings the geometry along: a copy launch less)
+    if (e == hipSuccess && !geom_in_stats) e = made.geometry_up();
     close(fd);
     if (e == hipSuccess && !why && byteswap) {
         PROF(ctx, "k_byteswap32");
@@ -957,24 +971,14 @@ static int upload_file_impl(pdbeda_ctx *ctx, const char *path, int64_t offset, i
     // mean / std (and the range of the blob sums' quantum) queued behind the copies: ONE wait for the map and its statistics -- every
     // caller asks for them next (cutoffs are mean + k std), and a wait of their own was one of a pool entry's host round trips
     const bool with_stats = (mean || std) && e == hipSuccess && !why;
-    double host[2] = {0.0, 0.0}, range[2] = {0.0, 0.0}, *chunk_sums = nullptr;
-    Arena scratch;
-    if (with_stats) {
-        if (stats_carve(m.get(), &scratch, chunk_sums) != 0) e = hipErrorOutOfMemory;
-        else if (stats_enqueue(m.get(), chunk_sums, host, range, true, geom_in_stats) != 0) e = hipErrorUnknown;
-    }
+    if (with_stats) e = made.stats_up(geom_in_stats);
     const double t_s0 = now_s();
     const hipError_t e2 = ctx_sync(ctx);      // (&m->geom is free again)
     if (upload_trace()) fprintf(stderr, "upload: final wait %.3f ms\n", 1e3 * (now_s() - t_s0));
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess || why) return why ? fail(ctx, PDBEDA_ERR_ARGUMENT, "reading %s: %s", path, why) : fail(ctx, PDBEDA_ERR_DEVICE, "map upload from file: %s", hipGetErrorString(e));
-    if (with_stats) {
-        range_apply(m.get(), range);
-        if (mean) *mean = host[0];
-        if (std) *std = host[1];
-    }
-    ctx->live_handles++;
-    *out = m.release();
+    if (with_stats) made.stats_out(mean, std);
+    made.publish(out);
     return PDBEDA_OK;
 }
 
@@ -990,29 +994,19 @@ extern "C" int pdbeda_map_combine(pdbeda_map *a, pdbeda_map *b, double alpha, pd
     if (!a || !b || !out) return PDBEDA_ERR_ARGUMENT;
     *out = nullptr;
     pdbeda_ctx *ctx = a->ctx;
-    if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts");
-    if (a->n_vox != b->n_vox || memcmp(a->geom.ncrs, b->geom.ncrs, sizeof a->geom.ncrs) != 0)
-        return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different shapes");
+    if (int rc = same_grid(ctx, a->geom, a->n_vox, b)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
-    m->ctx = ctx;
-    m->geom = a->geom;
-    m->n_vox = a->n_vox;
-    float *d = nullptr;
-    int rc = arena_carve(ctx, "map combine", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)m->n_vox); });
-    if (rc) return rc;
-    hipError_t e = h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom));
+    MadeMap made;
+    if (int rc = made.make_like("map combine", a)) return rc;
+    hipError_t e = made.geometry_up();
     if (e == hipSuccess) {
         PROF(ctx, "k_map_combine");
-        hipLaunchKernelGGL(k_map_combine, dim3(grid_for(m->n_vox / 4 + 1, 256, 4096)), dim3(256), 0, ctx->stream, a->dens, b->dens, alpha, m->n_vox, d);
+        hipLaunchKernelGGL(k_map_combine, dim3(grid_for(a->n_vox / 4 + 1, 256, 4096)), dim3(256), 0, ctx->stream, a->dens, b->dens, alpha, a->n_vox, made.dens);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = ctx_sync(ctx);   // (&m->geom is read by the copy above)
+    if (e == hipSuccess) e = ctx_sync(ctx);   // (the new map's geometry record is read by the copy above)
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "map combine: %s", hipGetErrorString(e));
-    m->dens = d;
-    m->own_dens = true;
-    ctx->live_handles++;
-    *out = m.release();
+    made.publish(out);
     return PDBEDA_OK;
 }
 
@@ -1182,8 +1176,8 @@ extern "C" int pdbeda_abs_select_hist(pdbeda_map *a, pdbeda_map *b, double alpha
                                       unsigned long long prefix, unsigned long long prefix_mask, uint32_t *hist) {
     if (!a || !hist || shift < 0 || shift > 48 || (which != 0 && which != 1) || (which == 1 && !b)) return PDBEDA_ERR_ARGUMENT;
     pdbeda_ctx *ctx = a->ctx;
-    if (b && (b->ctx != ctx || b->n_vox != a->n_vox || memcmp(a->geom.ncrs, b->geom.ncrs, sizeof a->geom.ncrs) != 0))
-        return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts or shapes");
+    if (b)
+        if (int rc = same_grid(ctx, a->geom, a->n_vox, b)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t n = (int64_t)a->geom.unique_ncrs[0] * a->geom.unique_ncrs[1] * a->geom.unique_ncrs[2];
     return with_scratch(ctx, 65536 * sizeof(uint32_t), [&](char *base) -> int {
@@ -1198,53 +1192,37 @@ extern "C" int pdbeda_abs_select_hist(pdbeda_map *a, pdbeda_map *b, double alpha
     });
 }
 
-extern "C" int pdbeda_point_density(pdbeda_map *m, const int32_t *crs, int64_t n, double *out) {
-    if (!m || (n > 0 && (!crs || !out)) || n < 0) return PDBEDA_ERR_ARGUMENT;
+// k_point_density writes the one of its two results that is asked for (the other has no array, and an empty piece of scratch).
+static int point_lookup(pdbeda_map *m, const char *site, const int32_t *crs, int64_t n, double *out, uint8_t *valid) {
+    if (!m || (n > 0 && (!crs || (!out && !valid))) || n < 0) return PDBEDA_ERR_ARGUMENT;
     if (n == 0) return PDBEDA_OK;
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int32_t *d_crs = nullptr;
-    double *d_out = nullptr;
-    return with_scratch(ctx, "point density", [&](Carver &cv) { cv.take(d_crs, 3 * n); cv.take(d_out, n); }, [&]() -> int {
-        const int32_t *in = pinned_in(ctx, crs, (size_t)(3 * n));
-        if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_crs, crs, (size_t)(12 * n))); in = d_crs; }
-        double *res = pinned_out(ctx, out, (size_t)n);
-        hipLaunchKernelGGL(k_point_density, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, m->geom_dev, m->dens, in, n, res ? res : d_out, (uint8_t *)nullptr);
-        if (!res) HIP_TRY(ctx, d2h(ctx, out, d_out, 8 * n));
+    Input<int32_t> in{crs, (size_t)(3 * n)};
+    Result<double> r_out{out, out ? (size_t)n : 0};
+    Result<uint8_t> r_valid{valid, valid ? (size_t)n : 0};
+    return with_scratch(ctx, site, [&](Carver &cv) { in.carve(cv); r_out.carve(cv); r_valid.carve(cv); }, [&]() -> int {
+        HIP_TRY(ctx, in.send(ctx));
+        hipLaunchKernelGGL(k_point_density, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, m->geom_dev, m->dens, in.at, n, r_out.at(ctx), r_valid.at(ctx));      // (one of the two takes)
+        HIP_TRY(ctx, r_out.finish(ctx));
+        HIP_TRY(ctx, r_valid.finish(ctx));
         return 0;
     });
 }
-
-extern "C" int pdbeda_valid_crs(pdbeda_map *m, const int32_t *crs, int64_t n, uint8_t *out) {
-    if (!m || (n > 0 && (!crs || !out)) || n < 0) return PDBEDA_ERR_ARGUMENT;
-    if (n == 0) return PDBEDA_OK;
-    pdbeda_ctx *ctx = m->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int32_t *d_crs = nullptr;
-    uint8_t *d_out = nullptr;
-    return with_scratch(ctx, "valid crs", [&](Carver &cv) { cv.take(d_crs, 3 * n); cv.take(d_out, n); }, [&]() -> int {
-        const int32_t *in = pinned_in(ctx, crs, (size_t)(3 * n));
-        if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_crs, crs, (size_t)(12 * n))); in = d_crs; }
-        uint8_t *res = pinned_out(ctx, out, (size_t)n);
-        hipLaunchKernelGGL(k_point_density, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, m->geom_dev, m->dens, in, n, (double *)nullptr, res ? res : d_out);
-        if (!res) HIP_TRY(ctx, d2h(ctx, out, d_out, n));
-        return 0;
-    });
-}
+extern "C" int pdbeda_point_density(pdbeda_map *m, const int32_t *crs, int64_t n, double *out) { return point_lookup(m, "point density", crs, n, out, nullptr); }
+extern "C" int pdbeda_valid_crs(pdbeda_map *m, const int32_t *crs, int64_t n, uint8_t *out) { return point_lookup(m, "valid crs", crs, n, nullptr, out); }
 
 extern "C" int pdbeda_crs2xyz(pdbeda_map *m, const int32_t *crs, int64_t n, double *xyz) {
     if (!m || (n > 0 && (!crs || !xyz)) || n < 0) return PDBEDA_ERR_ARGUMENT;
     if (n == 0) return PDBEDA_OK;
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int32_t *d_crs = nullptr;
-    double *d_xyz = nullptr;
-    return with_scratch(ctx, "crs2xyz", [&](Carver &cv) { cv.take(d_crs, 3 * n); cv.take(d_xyz, 3 * n); }, [&]() -> int {
-        const int32_t *in = pinned_in(ctx, crs, (size_t)(3 * n));
-        if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_crs, crs, (size_t)(12 * n))); in = d_crs; }
-        double *res = pinned_out(ctx, xyz, (size_t)(3 * n));
-        hipLaunchKernelGGL(k_crs2xyz, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, m->geom_dev, in, n, res ? res : d_xyz);
-        if (!res) HIP_TRY(ctx, d2h(ctx, xyz, d_xyz, 24 * n));
+    Input<int32_t> in{crs, (size_t)(3 * n)};
+    Result<double> res{xyz, (size_t)(3 * n)};
+    return with_scratch(ctx, "crs2xyz", [&](Carver &cv) { in.carve(cv); res.carve(cv); }, [&]() -> int {
+        HIP_TRY(ctx, in.send(ctx));
+        hipLaunchKernelGGL(k_crs2xyz, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, m->geom_dev, in.at, n, res.at(ctx));
+        HIP_TRY(ctx, res.finish(ctx));
         return 0;
     });
 }
@@ -1254,14 +1232,12 @@ extern "C" int pdbeda_xyz2crs(pdbeda_map *m, const double *xyz, int64_t n, int32
     if (n == 0) return PDBEDA_OK;
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    double *d_xyz = nullptr;
-    int32_t *d_crs = nullptr;
-    return with_scratch(ctx, "xyz2crs", [&](Carver &cv) { cv.take(d_xyz, 3 * n); cv.take(d_crs, 3 * n); }, [&]() -> int {
-        const double *in = pinned_in(ctx, xyz, (size_t)(3 * n));
-        if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, (size_t)(24 * n))); in = d_xyz; }
-        int32_t *res = pinned_out(ctx, crs, (size_t)(3 * n));
-        hipLaunchKernelGGL(k_xyz2crs, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, m->geom_dev, in, n, res ? res : d_crs);
-        if (!res) HIP_TRY(ctx, d2h(ctx, crs, d_crs, 12 * n));
+    Input<double> in{xyz, (size_t)(3 * n)};
+    Result<int32_t> res{crs, (size_t)(3 * n)};
+    return with_scratch(ctx, "xyz2crs", [&](Carver &cv) { in.carve(cv); res.carve(cv); }, [&]() -> int {
+        HIP_TRY(ctx, in.send(ctx));
+        hipLaunchKernelGGL(k_xyz2crs, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, m->geom_dev, in.at, n, res.at(ctx));
+        HIP_TRY(ctx, res.finish(ctx));
         return 0;
     });
 }
@@ -1412,6 +1388,14 @@ template <bool FUSED>
 static void launch_labels(pdbeda_ctx *ctx, const Job &job, const TileDims &td, int32_t *labels_dev, const Geom *geom_dev) {
     if (FUSED && job.fine_shift == 4) launch_labels_cw<FUSED, FUSED>(ctx, job, td, labels_dev, geom_dev);
     else launch_labels_cw<FUSED, false>(ctx, job, td, labels_dev, geom_dev);
+}
+// A whole-map job's signed label volume: its own if it kept one (PDBEDA_FLAG_LABELS), else written into `scratch` now (a caller carves the scratch only
+// when !job_keeps_labels).
+static bool job_keeps_labels(const LabelJob *lj) { return lj->labels_dev && lj->labels_done; }
+static const int32_t *job_signed_labels(const LabelJob *lj, int32_t *scratch) {
+    if (job_keeps_labels(lj)) return lj->labels_dev;
+    launch_labels<false>(lj->ctx, lj->job, lj->td, scratch, lj->map->geom_dev);
+    return scratch;
 }
 
 // Enqueue a whole-map job.  tier 0 carves the arena for what maps need in practice -- unit-tile run / component ids for a quarter of
@@ -1721,7 +1705,7 @@ static int list_stats_one_trip(pdbeda_bloblist *bl, int64_t guess, std::vector<i
         }
         extra = nullptr;      // (the guess was too small for the table; the caller's extra result has arrived with this first wait all the same)
     }
-    if (extra && extra->dst && extra->bytes) HIP_TRY(ctx, d2h(ctx, extra->dst, extra->src, extra->bytes));      // (delivered by the waits below)
+    if (extra) HIP_TRY(ctx, d2h_each(ctx, extra, 1));      // (delivered by the waits below)
     const int64_t nb = pdbeda_bloblist_count(bl);
     if (nb < 0) return (int)nb;
     n.resize((size_t)nb); tot.resize((size_t)nb); cen.resize(3 * (size_t)nb); grp.resize((size_t)nb);
@@ -1901,16 +1885,11 @@ extern "C" int pdbeda_bloblist_labels(pdbeda_bloblist *bl, int32_t *labels_host)
     const int uc = g.unique_ncrs[0], ur = g.unique_ncrs[1], us = g.unique_ncrs[2];
     const int64_t nvox = (int64_t)uc * ur * us;
     // scratch: [signed volume if it was not requested at labelling time] + decoded volume
-    const bool have = lj->labels_dev && lj->labels_done;
     Arena a;
     int32_t *decoded = nullptr, *tmp = nullptr;
-    int rc = arena_carve(ctx, "labels", &a, [&](Carver &cv) { cv.take(decoded, nvox); if (!have) cv.take(tmp, nvox); });
+    int rc = arena_carve(ctx, "labels", &a, [&](Carver &cv) { cv.take(decoded, nvox); if (!job_keeps_labels(lj)) cv.take(tmp, nvox); });
     if (rc) return rc;
-    const int32_t *signed_vol = lj->labels_dev;
-    if (!have) {
-        launch_labels<false>(ctx, lj->job, lj->td, tmp, lj->map->geom_dev);
-        signed_vol = tmp;
-    }
+    const int32_t *signed_vol = job_signed_labels(lj, tmp);
     hipLaunchKernelGGL(k_labels_decode, dim3(grid_for(nvox, 256, 4096)), dim3(256), 0, ctx->stream, signed_vol, nvox, bl->sign, decoded);
     hipError_t e = d2h(ctx, labels_host, decoded, 4 * nvox);
     if (e == hipSuccess) e = ctx_sync(ctx);
@@ -1967,7 +1946,6 @@ extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, c
     if (cnt >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "nearest blobs: a list of 2^31 blobs or more");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t nvox = (int64_t)g.unique_ncrs[0] * g.unique_ncrs[1] * g.unique_ncrs[2];
-    const bool have = jb->labels_dev && jb->labels_done;
     const size_t nb = (size_t)cnt;
     BlobNearArgs args;
     uint32_t *d_table = nullptr;
@@ -1977,7 +1955,7 @@ extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, c
         cv.take(args.best, nb);
         cv.take(d_table, (size_t)n_offsets);
         cv.take(d_rows, 8 * nb);
-        if (!have) cv.take(tmp, (size_t)nvox);
+        if (!job_keeps_labels(jb)) cv.take(tmp, (size_t)nvox);
     });
     if (rc_arena) return rc_arena;
     std::vector<int32_t> rows(8 * nb);
@@ -1985,13 +1963,8 @@ extern "C" int pdbeda_bloblist_nearest(pdbeda_bloblist *a, pdbeda_bloblist *b, c
         hipStream_t st = ctx->stream;
         HIP_TRY(ctx, h2d_one(ctx, d_table, packed.data(), sizeof(uint32_t) * (size_t)n_offsets));
         HIP_TRY(ctx, hipMemsetAsync(args.best, 0xFF, sizeof(unsigned long long) * nb, st));
-        const int32_t *signed_vol = jb->labels_dev;
-        if (!have) {
-            launch_labels<false>(ctx, jb->job, jb->td, tmp, jb->map->geom_dev);
-            signed_vol = tmp;
-        }
         args.crs = ja->crs_dev; args.off = ja->offsets_dev + ra.lo; args.cnt = cnt;
-        args.labels = signed_vol; args.sign = b->sign;
+        args.labels = job_signed_labels(jb, tmp); args.sign = b->sign;
         args.uc = g.unique_ncrs[0]; args.ur = g.unique_ncrs[1]; args.us = g.unique_ncrs[2];
         args.table = d_table; args.n_off = (int32_t)n_offsets;
         // positions per thread: one while that gives fewer than BN_MIN_GROUPS workgroups (a walk is a chain of read latencies: a short list
@@ -2085,7 +2058,7 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
     for (int p = 0; p < a.n_planes; ++p) {
         pdbeda_bloblist *bl = pj->blobs[p];
         if (!bl) continue;
-        if (bl->job->labels_dev && bl->job->labels_done) have[p] = bl->job->labels_dev;
+        if (job_keeps_labels(bl->job)) have[p] = bl->job->labels_dev;
         else need_own[p] = true;
     }
     // (the two lists of ONE fused labelling job: one signed volume serves both planes)
@@ -2120,7 +2093,7 @@ static int peaks_enqueue(PeakJob *pj, const int64_t cap[2], const int64_t seg[2]
     hipError_t e = hipSuccess;
     {   // (nothing to clear: the stencil stores every tile's counts, the scan every counter)
         for (int p = 0; p < a.n_planes; ++p)
-            if (need_own[p]) launch_labels<false>(ctx, pj->blobs[p]->job->job, pj->blobs[p]->job->td, const_cast<int32_t *>(a.plane[p].labels), m->geom_dev);
+            if (need_own[p]) (void)job_signed_labels(pj->blobs[p]->job, const_cast<int32_t *>(a.plane[p].labels));      // (written into the piece carved above: the list's job is one of this map)
         const dim3 grid((unsigned)((a.uc + PK_C - 1) / PK_C), (unsigned)((a.ur + PK_R - 1) / PK_R), (unsigned)((a.us + PK_S - 1) / PK_S));
         { PROF(ctx, "k_peak_stencil"); hipLaunchKernelGGL(k_peak_stencil, grid, dim3(PK_THREADS), 0, ctx->stream, a, m->dens); }
         { PROF(ctx, "k_peak_scan"); hipLaunchKernelGGL(k_peak_scan, dim3(1), dim3(PK_SCAN_THREADS), 0, ctx->stream, a); }
@@ -2507,16 +2480,12 @@ struct GroupSetup {
     int64_t largest_box = 0;    // a batch the host planned: voxels of its largest volume
     bool atom_engine = false;   // per-atom spheres whose boxes the host made, every box one mask word a row and at most ATOM_WORDS rows: ONE launch labels the batch (k_atom_engine)
     // staged inputs whose copy into the device scratch has not been launched yet: grouped_job's k_job_init does it (one launch less), flush_pending for everybody else
-    const char *pend_src = nullptr;
-    char *pend_dst = nullptr;
-    size_t pend_bytes = 0;
+    PendingCopy pend;
 };
 
 static hipError_t flush_pending(pdbeda_ctx *ctx, GroupSetup *gs) {
-    if (!gs->pend_bytes) return hipSuccess;
-    const hipError_t e = copy_by_kernel(ctx, gs->pend_dst, gs->pend_src, gs->pend_bytes);
-    gs->pend_bytes = 0;
-    return e;
+    const PendingCopy p = gs->pend.take();
+    return p.bytes ? copy_by_kernel(ctx, p.dst, p.src, p.bytes) : hipSuccess;
 }
 
 static int expand_groups(const int64_t *group_offsets, int64_t n_groups, int64_t n_items, std::vector<int32_t> &item_group) {
@@ -2611,49 +2580,47 @@ static int group_setup(pdbeda_map *m, const double *xyz, const float *radii, con
     bool per_atom = spheres && n_items > 0 && n_groups == n_items;
     for (int64_t g = 0; g <= n_groups && per_atom; ++g) per_atom = group_offsets[g] == g;
     const bool grouped = spheres && n_items > 0 && n_groups > 0 && n_groups < n_items;
-    // (a staged block mirrors the head of the scratch arena, where group_alloc carves the inputs first: `staged` is the block's twin of a device pointer)
+    // (a staged block mirrors the head of the scratch arena, where group_alloc carves the inputs first: a StagedRow over it)
     char *const base = gs->in_arena.base;
     const size_t inputs = (size_t)((char *)(gs->d_item_group + n_items) - base), row = (size_t)((char *)(gs->d_ctr + 1) - base);
-    auto staged = [&](char *stage, const void *dev) { return stage + ((const char *)dev - base); };
     // ---- decide: each plan is sized once, by the planner ----
     enum { ROW_TO_JOB, ROW_NOW, INPUTS_ONLY, DEVICE_SIZED } ship = DEVICE_SIZED;
-    char *stage = nullptr;
+    StagedRow sr;
     SpherePlan plan;
-    const bool row_allowed = (per_atom || (grouped && copy_kernels())) && host_boxes_on && !ctx->debug_shrink_totals && row <= ((size_t)1 << 20);
-    if (row_allowed && (stage = pinned_take(ctx, row)) != nullptr) {      // (boxes and volumes straight into the staged row)
-        plan = plan_spheres(m->geom, xyz, radii, per_atom ? nullptr : item_group.data(), n_items, n_groups, reinterpret_cast<AtomBox *>(staged(stage, gs->d_boxes)),
-                            reinterpret_cast<VolDesc *>(staged(stage, gs->d_vols)), ATOM_WORDS);
+    const bool row_allowed = (per_atom || (grouped && copy_kernels())) && host_boxes_on && !ctx->debug_shrink_totals && row <= STAGED_ROW_LIMIT;
+    if (row_allowed && (sr = StagedRow{pinned_take(ctx, row), base, row}).stage) {      // (boxes and volumes straight into the staged row)
+        plan = plan_spheres(m->geom, xyz, radii, per_atom ? nullptr : item_group.data(), n_items, n_groups, sr.twin(gs->d_boxes), sr.twin(gs->d_vols), ATOM_WORDS);
         if (plan.fits) ship = copy_kernels() ? ROW_TO_JOB : ROW_NOW;
-        else { pinned_untake(ctx, stage); stage = nullptr; }
+        else { pinned_untake(ctx, sr.stage); sr = StagedRow(); }
     }
     if (ship == DEVICE_SIZED && per_atom && plan.plannable) {      // (a coordinate the host may not cast: the device's boxes are its own business, and so are its totals)
         plan = plan_radii_totals(m->geom, radii, n_items, ATOM_WORDS);
-        if (plan.fits && (stage = pinned_take(ctx, inputs)) != nullptr) ship = INPUTS_ONLY;
+        if (plan.fits && (sr = StagedRow{pinned_take(ctx, inputs), base, inputs}).stage) ship = INPUTS_ONLY;
     }
     // ---- ship ----
     if (ship != DEVICE_SIZED) {      // coordinates, radii and groups at their arena offsets
-        memcpy(staged(stage, gs->d_xyz), xyz, 24 * (size_t)n_items);
-        memcpy(staged(stage, gs->d_radii), radii, 4 * (size_t)n_items);
-        memcpy(staged(stage, gs->d_item_group), item_group.data(), 4 * (size_t)n_items);
+        sr.put(gs->d_xyz, xyz, 24 * (size_t)n_items);
+        sr.put(gs->d_radii, radii, 4 * (size_t)n_items);
+        sr.put(gs->d_item_group, item_group.data(), 4 * (size_t)n_items);
     }
     if (ship == ROW_TO_JOB || ship == ROW_NOW) {
-        Counters *ctr0 = reinterpret_cast<Counters *>(staged(stage, gs->d_ctr));
+        Counters *ctr0 = sr.twin(gs->d_ctr);
         memset(ctr0, 0, sizeof *ctr0);
         ctr0->total_words = plan.words;
         ctr0->total_keys = plan.keys;
         gs->largest_box = plan.largest;
         if (per_atom) {
-            const AtomBox *boxes = reinterpret_cast<const AtomBox *>(staged(stage, gs->d_boxes));
+            const AtomBox *boxes = sr.twin(gs->d_boxes);
             gs->host_boxes.assign(boxes, boxes + n_items);
             gs->atom_engine = plan.small_boxes && atom_engine_on && n_items < (1ll << 31);
         }
-        if (ship == ROW_NOW) HIP_TRY(ctx, stage_copy(ctx, stage, base, row, true));
-        else { gs->pend_src = stage; gs->pend_dst = base; gs->pend_bytes = (row + 15) & ~(size_t)15; }   // (copied by the job's first launch; whole 16-byte units: the stage and the carve are padded)
+        if (ship == ROW_NOW) HIP_TRY(ctx, stage_copy(ctx, sr.stage, base, row, true));
+        else gs->pend = {sr.stage, base, sr.bytes16()};   // (copied by the job's first launch; whole 16-byte units: the stage and the carve are padded)
         return group_sized(ctx, gs, plan.words, plan.keys, true);
     }
     if (ship == INPUTS_ONLY) {
         const int64_t totals[2] = {plan.words / (ctx->debug_shrink_totals ? 2 : 1), plan.keys / (ctx->debug_shrink_totals ? 2 : 1)};
-        HIP_TRY(ctx, stage_copy(ctx, stage, base, inputs, true));      // (a row at the head of the scratch arena: one staged block, one copy)
+        HIP_TRY(ctx, stage_copy(ctx, sr.stage, base, inputs, true));      // (a row at the head of the scratch arena: one staged block, one copy)
         return group_bounds(m, gs, n_items, n_groups, true, totals);
     }
     if (n_items > 0) {
@@ -2679,7 +2646,7 @@ static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n
     }();
     pdbeda_ctx *ctx = m->ctx;
     const int64_t max_runs = gs.total_keys / 2 + gs.total_words + 1;
-    if (gs.pend_bytes && m->fix_mul == 0.0 && !m->fix_refused) {
+    if (gs.pend.bytes && m->fix_mul == 0.0 && !m->fix_refused) {
         // map_fix_mul is about to WAIT (a map whose range is not known yet), and a wait hands the pinned block out afresh: inputs staged there must be on
         // their way before it, not left to k_job_init behind it
         const hipError_t ep = flush_pending(ctx, &gs);
@@ -2698,16 +2665,16 @@ static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n
     {   // volume descriptors into the job + zeroes over counters, masks, first-key bitmap and both levels of rank counters (adjacent in the arena: job_carve): one launch
         static_assert(sizeof(VolDesc) % 16 == 0, "VolDesc is copied in 16-byte units");
         const size_t zero_bytes = ((size_t)((char *)(job.mid_count + (job.key_words + KEY_FINE - 1) / KEY_FINE * (KEY_FINE / 16)) - (char *)job.ctr) + 15) & ~(size_t)15;   // (into the carve's own padding)
-        const size_t vol16 = sizeof(VolDesc) * (size_t)n_groups / 16, in16 = gs.pend_bytes / 16;
+        const PendingCopy pend = gs.pend.take();      // (the staged inputs, when their copy was left to this launch)
+        const size_t vol16 = sizeof(VolDesc) * (size_t)n_groups / 16, in16 = pend.bytes / 16;
         // (volume descriptors that are part of the inputs still to be copied come straight from the staged block)
         const char *vol_src = reinterpret_cast<const char *>(gs.d_vols);
-        if (gs.pend_bytes && vol_src >= gs.pend_dst && vol_src < gs.pend_dst + gs.pend_bytes) vol_src = gs.pend_src + (vol_src - gs.pend_dst);
+        if (pend.bytes && vol_src >= pend.dst && vol_src < pend.dst + pend.bytes) vol_src = StagedRow{pend.src, pend.dst, pend.bytes}.twin(vol_src);
         hipLaunchKernelGGL(k_job_init, dim3((unsigned)std::min<size_t>((std::max(std::max(zero_bytes / 16, vol16), in16) + 255) / 256, 2048)), dim3(256), 0, st,
-                           reinterpret_cast<const uint4 *>(gs.pend_src), reinterpret_cast<uint4 *>(gs.pend_dst), (unsigned long long)in16,
+                           reinterpret_cast<const uint4 *>(pend.src), reinterpret_cast<uint4 *>(pend.dst), (unsigned long long)in16,
                            reinterpret_cast<const uint4 *>(vol_src), reinterpret_cast<uint4 *>(job.vols), (unsigned long long)vol16,
                            reinterpret_cast<uint4 *>(job.ctr), (unsigned long long)(zero_bytes / 16));
         e = hipGetLastError();
-        gs.pend_bytes = 0;
     }
     const bool fused_atoms = spheres && gs.atom_engine && n_items > 0 && n_items == n_groups;
     if (e == hipSuccess && fused_atoms) {   // a per-atom batch of small boxes: paint, run index, unions, resolve and key painting in one launch
@@ -2780,20 +2747,17 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
     {   // a group per atom whose inputs the host staged (coordinates, radii, host-made volumes in the pinned block): ONE launch, no mask (k_atom_region).
         // The kernel counts a box's voxels in 32 bits and does not ask for small boxes, so the gate does: the plan's largest box has fewer than 2^31.
         const size_t out_bytes = 3 * pinned_span(8 * (size_t)n_groups) + pinned_span(4 * (size_t)n_groups);
-        if (atom_region_on && n_groups == n_atoms && gs.pend_bytes && !gs.host_boxes.empty() && gs.largest_box < (1ll << 31) && copy_kernels() && out_bytes <= pinned_room(ctx)) {
+        if (atom_region_on && n_groups == n_atoms && gs.pend.bytes && !gs.host_boxes.empty() && gs.largest_box < (1ll << 31) && copy_kernels() && out_bytes <= pinned_room(ctx)) {
             // (n_groups > 0: no take is empty.  As before a failed launch below keeps the takes until the next wait and, through fail(), delivers nothing)
             double *o_pos = reinterpret_cast<double *>(pinned_take(ctx, 8 * (size_t)n_groups, pos));
             double *o_neg = reinterpret_cast<double *>(pinned_take(ctx, 8 * (size_t)n_groups, neg));
             unsigned long long *o_cnt = reinterpret_cast<unsigned long long *>(pinned_take(ctx, 8 * (size_t)n_groups, h_cnt.data()));
             unsigned int *o_inv = reinterpret_cast<unsigned int *>(pinned_take(ctx, 4 * (size_t)n_groups, h_inv.data()));
-            // (the staged row mirrors the scratch arena: the same offsets)
-            const char *stage = gs.pend_src;
-            const double *s_xyz = reinterpret_cast<const double *>(stage + ((char *)gs.d_xyz - gs.in_arena.base));
-            const float *s_rad = reinterpret_cast<const float *>(stage + ((char *)gs.d_radii - gs.in_arena.base));
-            const VolDesc *s_vols = reinterpret_cast<const VolDesc *>(stage + ((char *)gs.d_vols - gs.in_arena.base));
-            gs.pend_bytes = 0;
-            { PROF(ctx, "k_atom_region"); hipLaunchKernelGGL(k_atom_region, dim3((unsigned)std::min<int64_t>(n_groups, 65536)), dim3(256), 0, ctx->stream, m->geom_dev, m->dens, s_xyz, s_rad,
-                                                            s_vols, (int)n_groups, cutoff, o_pos, o_neg, o_cnt, o_inv); }
+            // (the kernel reads the staged row where it lies: its copy into the scratch arena is never launched)
+            const PendingCopy pend = gs.pend.take();
+            const StagedRow sr{pend.src, pend.dst, pend.bytes};
+            { PROF(ctx, "k_atom_region"); hipLaunchKernelGGL(k_atom_region, dim3((unsigned)std::min<int64_t>(n_groups, 65536)), dim3(256), 0, ctx->stream, m->geom_dev, m->dens, sr.twin(gs.d_xyz), sr.twin(gs.d_radii),
+                                                            sr.twin(gs.d_vols), (int)n_groups, cutoff, o_pos, o_neg, o_cnt, o_inv); }
             hipError_t e1 = hipGetLastError();
             if (e1 == hipSuccess) e1 = ctx_sync(ctx);
             if (e1 != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "region sums: %s", hipGetErrorString(e1));
@@ -2819,12 +2783,12 @@ extern "C" int pdbeda_region_sums(pdbeda_map *m, const double *xyz, const float 
     hipStream_t st = ctx->stream;
     hipError_t e;
     {   // the staged inputs into the scratch (when group_setup left their copy to us) and zeroes over masks and sums: one launch
-        const size_t in16 = gs.pend_bytes / 16, zero16 = zero_bytes / 16;
+        const PendingCopy pend = gs.pend.take();
+        const size_t in16 = pend.bytes / 16, zero16 = zero_bytes / 16;
         hipLaunchKernelGGL(k_job_init, dim3((unsigned)std::min<size_t>((std::max(zero16, in16) + 255) / 256, 2048)), dim3(256), 0, st,
-                           reinterpret_cast<const uint4 *>(gs.pend_src), reinterpret_cast<uint4 *>(gs.pend_dst), (unsigned long long)in16,
+                           reinterpret_cast<const uint4 *>(pend.src), reinterpret_cast<uint4 *>(pend.dst), (unsigned long long)in16,
                            (const uint4 *)nullptr, (uint4 *)nullptr, 0ull, reinterpret_cast<uint4 *>(a.base), (unsigned long long)zero16);
         e = hipGetLastError();
-        gs.pend_bytes = 0;
     }
     if (e == hipSuccess && n_atoms > 0) {
         { PROF(ctx, "k_sphere_paint"); hipLaunchKernelGGL(k_sphere_paint, dim3((unsigned)n_atoms), dim3(256), 0, st, m->geom_dev, m->dens, gs.d_xyz, gs.d_radii,
@@ -2889,7 +2853,7 @@ extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t 
     for (int64_t room = 1ll << 22; room < largest; room <<= 1) fix_mul *= 0.5;
     const double fix_inv = 1.0 / fix_mul;      // (powers of two: exact)
     const size_t cells = (size_t)n_shells, per_atom = 48 + 32 * cells + 1, slack = 7 * 64;
-    const bool direct = copy_kernels() && ctx->pinned && pinned_room(ctx) >= per_atom + slack;
+    const bool direct = copy_kernels() && ctx->pinned.base && pinned_room(ctx) >= per_atom + slack;
     const int64_t chunk = std::max<int64_t>(1, direct ? (int64_t)((pinned_room(ctx) - slack) / per_atom) : (int64_t)(((size_t)8 << 20) / per_atom));
     Arena scratch;
     for (int64_t a0 = 0; a0 < n_atoms; a0 += chunk) {
@@ -2899,15 +2863,12 @@ extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t 
         long long *k_n, *k_nsig;
         double *k_sum, *k_sumsig;
         uint8_t *k_valid;
-        char *first = nullptr;
+        const char *first = nullptr;
         hipError_t e = hipSuccess;
         if (direct) {      // (the chunk was sized to fit: no take fails)
-            first = pinned_take(ctx, 24 * na);
-            memcpy(first, xyz + 3 * a0, 24 * na);
-            char *b = pinned_take(ctx, sizeof(AtomBox) * na);
-            memcpy(b, &boxes[(size_t)a0], sizeof(AtomBox) * na);
-            k_xyz = reinterpret_cast<const double *>(first);
-            k_box = reinterpret_cast<const AtomBox *>(b);
+            k_xyz = pinned_in(ctx, xyz + 3 * a0, 3 * na);
+            k_box = pinned_in(ctx, &boxes[(size_t)a0], na);
+            first = reinterpret_cast<const char *>(k_xyz);
             k_n = reinterpret_cast<long long *>(pinned_take(ctx, 8 * rows, n ? n + (size_t)a0 * cells : nullptr));
             k_sum = reinterpret_cast<double *>(pinned_take(ctx, 8 * rows, sum ? sum + (size_t)a0 * cells : nullptr));
             k_nsig = reinterpret_cast<long long *>(pinned_take(ctx, 8 * rows, n_sig ? n_sig + (size_t)a0 * cells : nullptr));
@@ -2932,7 +2893,7 @@ extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t 
             k_xyz = d_xyz;
             k_box = d_box;
             const H2DItem in[2] = {{d_xyz, xyz + 3 * a0, 24 * na}, {d_box, &boxes[(size_t)a0], sizeof(AtomBox) * na}};
-            e = h2d_row(ctx, in, 2, (size_t)1 << 20);
+            e = h2d_row(ctx, in, 2, STAGED_ROW_LIMIT);
         }
         if (e == hipSuccess) {
             PROF(ctx, "k_atom_shells");
@@ -2945,8 +2906,7 @@ extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t 
             const D2HItem parts[5] = {{n ? n + (size_t)a0 * cells : nullptr, k_n, 8 * rows}, {sum ? sum + (size_t)a0 * cells : nullptr, k_sum, 8 * rows},
                                       {n_sig ? n_sig + (size_t)a0 * cells : nullptr, k_nsig, 8 * rows}, {sum_sig ? sum_sig + (size_t)a0 * cells : nullptr, k_sumsig, 8 * rows},
                                       {valid ? valid + a0 : nullptr, k_valid, na}};
-            for (int k = 0; k < 5 && e == hipSuccess; ++k)
-                if (parts[k].dst) e = d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes);
+            e = d2h_each(ctx, parts, 5);
         }
         if (e == hipSuccess) e = ctx_sync(ctx);      // (delivers the chunk's rows and rewinds the block for the next chunk)
         if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "radial profiles: %s", hipGetErrorString(e));
@@ -3023,20 +2983,20 @@ extern "C" int pdbeda_symmetry_atoms(pdbeda_ctx *ctx, const double *xyz, int64_t
             const H2DItem in[5] = {{d_xyz, xyz, (size_t)(24 * n_atoms)}, {d_rot, rot, (size_t)(96 * n_ops)}, {d_ortho, ortho, 72}, {d_lo, bbox_lo, 24}, {d_hi, bbox_hi, 24}};
             HIP_TRY(ctx, h2d_row(ctx, in, 5));      // (one copy: the five sit in a row)
         }
-        unsigned long long *r_keep = pinned_out(ctx, h_keep.data(), (size_t)n_words);
-        { PROF(ctx, "k_symmetry_keep"); hipLaunchKernelGGL(k_symmetry_keep, dim3(grid_for(total, 256)), dim3(256), 0, st, d_xyz, n_atoms, d_rot, (int)n_ops, d_ortho, d_lo, d_hi, r_keep ? r_keep : d_keep); }
-        if (!r_keep) HIP_TRY(ctx, d2h(ctx, h_keep.data(), d_keep, 8 * n_words));
+        Result<unsigned long long> keep{h_keep.data(), (size_t)n_words, d_keep};
+        { PROF(ctx, "k_symmetry_keep"); hipLaunchKernelGGL(k_symmetry_keep, dim3(grid_for(total, 256)), dim3(256), 0, st, d_xyz, n_atoms, d_rot, (int)n_ops, d_ortho, d_lo, d_hi, keep.at(ctx)); }
+        HIP_TRY(ctx, keep.finish(ctx));
         HIP_TRY(ctx, ctx_sync(ctx));
         for (int64_t w = 0; w < n_words; ++w)
             for (unsigned long long bits = h_keep[(size_t)w]; bits; bits &= bits - 1) picked.push_back(64 * w + __builtin_ctzll(bits));
         const int64_t n = (int64_t)picked.size();
         if (n == 0 || n > cap || !out_xyz) return 0;
         h_xyz.resize(3 * (size_t)n);
-        const int64_t *in_picked = pinned_in(ctx, picked.data(), (size_t)n);      // (a survivor's number is read by its own thread, once)
-        if (!in_picked) { HIP_TRY(ctx, h2d_one(ctx, d_picked, picked.data(), (size_t)(8 * n))); in_picked = d_picked; }
-        double *r_out = pinned_out(ctx, h_xyz.data(), 3 * (size_t)n);
-        { PROF(ctx, "k_symmetry_pick"); hipLaunchKernelGGL(k_symmetry_pick, dim3(grid_for(n, 256)), dim3(256), 0, st, d_xyz, n_atoms, d_rot, (int)n_ops, d_ortho, d_lo, d_hi, in_picked, n, r_out ? r_out : d_out); }
-        if (!r_out) HIP_TRY(ctx, d2h(ctx, h_xyz.data(), d_out, 24 * n));
+        Input<int64_t> in_picked{picked.data(), (size_t)n, d_picked};      // (a survivor's number is read by its own thread, once)
+        Result<double> out{h_xyz.data(), 3 * (size_t)n, d_out};
+        HIP_TRY(ctx, in_picked.send(ctx));
+        { PROF(ctx, "k_symmetry_pick"); hipLaunchKernelGGL(k_symmetry_pick, dim3(grid_for(n, 256)), dim3(256), 0, st, d_xyz, n_atoms, d_rot, (int)n_ops, d_ortho, d_lo, d_hi, in_picked.at, n, out.at(ctx)); }
+        HIP_TRY(ctx, out.finish(ctx));
         return 0;
     });
     if (rc) return rc;
@@ -3312,24 +3272,24 @@ extern "C" int pdbeda_image_coords(pdbeda_ctx *ctx, const double *poly_xyz, int6
     if (n_cand * n_poly >= (1ll << 32) - 1) return fail(ctx, PDBEDA_ERR_ARGUMENT, "more than 2^32 image atoms");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t total = n_cand * n_poly;
-    double *d_poly = nullptr, *d_rot = nullptr, *d_ortho = nullptr, *d_out = nullptr;
+    double *d_poly = nullptr, *d_rot = nullptr, *d_ortho = nullptr;
     int32_t *d_cand = nullptr;
+    Result<double> out{out_xyz, 3 * (size_t)total};
     return with_scratch(ctx, "image coords", [&](Carver &cv) {
         cv.take(d_poly, 3 * n_poly);
         cv.take(d_rot, 12 * n_ops);
         cv.take(d_ortho, 9);
         cv.take(d_cand, 4 * n_cand);
-        cv.take(d_out, 3 * total);
+        out.carve(cv);
     }, [&]() -> int {
         hipStream_t st = ctx->stream;
         {
             const H2DItem in[4] = {{d_poly, poly_xyz, (size_t)(24 * n_poly)}, {d_rot, rot, (size_t)(96 * n_ops)}, {d_ortho, ortho, 72}, {d_cand, cand, (size_t)(16 * n_cand)}};
             HIP_TRY(ctx, h2d_row(ctx, in, 4));
         }
-        double *r_out = pinned_out(ctx, out_xyz, 3 * (size_t)total);
-        { PROF(ctx, "k_image_emit"); hipLaunchKernelGGL(k_image_emit, dim3(grid_for(total, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, r_out ? r_out : d_out); }
+        { PROF(ctx, "k_image_emit"); hipLaunchKernelGGL(k_image_emit, dim3(grid_for(total, 256)), dim3(256), 0, st, d_poly, n_poly, d_rot, d_ortho, d_cand, n_cand, out.at(ctx)); }
         HIP_TRY(ctx, hipGetLastError());
-        if (!r_out) HIP_TRY(ctx, d2h(ctx, out_xyz, d_out, 24 * (size_t)total));
+        HIP_TRY(ctx, out.finish(ctx));
         return 0;
     });
 }
@@ -3416,8 +3376,7 @@ extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_
         HIP_TRY(ctx, hipGetLastError());
         const D2HItem parts[9] = {{n, d_on, 8 * na}, {n_pos, d_on + na, 8 * na}, {n_neg, d_on + 2 * na, 8 * na}, {sum, d_os, 8 * na}, {sum_pos, d_os + na, 8 * na},
                                   {sum_neg, d_os + 2 * na, 8 * na}, {unowned_n, d_un, 24}, {unowned_sum, d_us, 32}, {owner, d_owner, 4 * (size_t)nbox}};
-        for (int k = 0; k < 9; ++k)
-            if (parts[k].dst && parts[k].bytes) HIP_TRY(ctx, d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes));
+        HIP_TRY(ctx, d2h_each(ctx, parts, 9));
         return 0;
     });
 }
@@ -3446,18 +3405,17 @@ extern "C" int pdbeda_interp_density(pdbeda_map *m, const double *xyz, int64_t n
             return fail(ctx, PDBEDA_ERR_ARGUMENT, "interpolated density: point %lld is not finite or lies 2^29 grid steps or more from the map's origin", (long long)i);
     if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    double *d_xyz = nullptr, *d_out = nullptr;
-    uint8_t *d_valid = nullptr;
-    return with_scratch(ctx, "interpolated density", [&](Carver &cv) { cv.take(d_xyz, 3 * n); cv.take(d_out, n); cv.take(d_valid, n); }, [&]() -> int {
-        const double *in = pinned_in(ctx, xyz, (size_t)(3 * n));
-        if (!in) { HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, (size_t)(24 * n))); in = d_xyz; }
-        double *r_out = pinned_out(ctx, out, (size_t)n);
-        uint8_t *r_valid = pinned_out(ctx, valid, (size_t)n);
-        { PROF(ctx, "k_interp_density"); hipLaunchKernelGGL(k_interp_density, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->geom_dev, m->dens, in, n,
-                                                            out ? (r_out ? r_out : d_out) : (double *)nullptr, valid ? (r_valid ? r_valid : d_valid) : (uint8_t *)nullptr); }
+    Input<double> in{xyz, (size_t)(3 * n)};
+    Result<double> r_out{out, (size_t)n};
+    Result<uint8_t> r_valid{valid, (size_t)n};
+    return with_scratch(ctx, "interpolated density", [&](Carver &cv) { in.carve(cv); r_out.carve(cv); r_valid.carve(cv); }, [&]() -> int {
+        HIP_TRY(ctx, in.send(ctx));
+        double *k_out = r_out.at(ctx);
+        uint8_t *k_valid = r_valid.at(ctx);
+        { PROF(ctx, "k_interp_density"); hipLaunchKernelGGL(k_interp_density, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->geom_dev, m->dens, in.at, n, k_out, k_valid); }
         HIP_TRY(ctx, hipGetLastError());
-        if (out && !r_out) HIP_TRY(ctx, d2h(ctx, out, d_out, 8 * (size_t)n));
-        if (valid && !r_valid) HIP_TRY(ctx, d2h(ctx, valid, d_valid, (size_t)n));
+        HIP_TRY(ctx, r_out.finish(ctx));
+        HIP_TRY(ctx, r_valid.finish(ctx));
         return 0;
     });
 }
@@ -3544,8 +3502,7 @@ extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_a
         { PROF(ctx, "k_atom_qscores"); hipLaunchKernelGGL(k_atom_qscores, dim3((unsigned)((n_scored + 3) / 4)), dim3(256), 0, st, a); }
         HIP_TRY(ctx, hipGetLastError());
         const D2HItem parts[6] = {{q, d_q, 8 * ns}, {n_points, d_np, 4 * ns}, {shell_n, d_sn, 4 * rows}, {shell_mean, d_mean, 8 * rows}, {valid, d_valid, ns}, {counters, d_ctr, 16}};
-        for (int k = 0; k < 6; ++k)
-            if (parts[k].dst && parts[k].bytes) HIP_TRY(ctx, d2h(ctx, parts[k].dst, parts[k].src, parts[k].bytes));
+        HIP_TRY(ctx, d2h_each(ctx, parts, 6));
         return 0;
     });
 }
@@ -3610,13 +3567,8 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t cells = grid.n_cells;
     const size_t na = (size_t)n_atoms, np = (size_t)n_pairs;
-
-    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
-    m->ctx = ctx;
-    m->geom = like->geom;
-    m->n_vox = like->n_vox;
-    float *d_out = nullptr;
-    if (int rc = arena_carve(ctx, "model density", &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d_out, (size_t)m->n_vox); })) return rc;
+    MadeMap made;
+    if (int rc = made.make_like("model density", like)) return rc;
     double *d_xyz = nullptr, *d_amp = nullptr, *d_expo = nullptr;
     float *d_radii = nullptr;
     GridBuild gb;
@@ -3633,18 +3585,18 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
         hipStream_t st = ctx->stream;
         HIP_TRY(ctx, hipMemsetAsync(gb.count, 0, 4 * (size_t)cells, st));
         HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, 16, st));
-        HIP_TRY(ctx, h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom)));
+        HIP_TRY(ctx, made.geometry_up());
         if (n_atoms > 0) {
             const H2DItem in[4] = {{d_xyz, xyz, 24 * na}, {d_amp, amp, 8 * np}, {d_expo, expo, 8 * np}, {d_radii, radii, 4 * na}};
             HIP_TRY(ctx, h2d_row(ctx, in, 4));
         }
         gb.sort_points(ctx, grid, d_xyz, n_atoms);
         ModelArgs a;
-        a.geom = m->geom_dev; a.tiles_c = tiles_c; a.tiles_r = tiles_r;
+        a.geom = made.m->geom_dev; a.tiles_c = tiles_c; a.tiles_r = tiles_r;
         a.grid = grid; a.sorted = gb.sorted; a.sorted_index = gb.sorted_index; a.start = gb.start;
         a.amp = d_amp; a.expo = d_expo; a.radii = d_radii; a.n_terms = n_terms;
         a.r_max = r_max; a.fix_mul = ldexp(1.0, S); a.fix_inv = ldexp(1.0, -S);
-        a.out = d_out; a.counters = d_ctr;
+        a.out = made.dens; a.counters = d_ctr;
         { PROF(ctx, "k_model_tile"); hipLaunchKernelGGL(k_model_tile, dim3((unsigned)n_tiles), dim3(256), 0, st, a); }
         HIP_TRY(ctx, hipGetLastError());
         if (counters) HIP_TRY(ctx, d2h(ctx, seen, d_ctr, 16));
@@ -3652,10 +3604,7 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
     });
     if (rc) return rc;
     if (counters) { counters[0] = S; counters[1] = seen[0]; counters[2] = seen[1]; }
-    m->dens = d_out;
-    m->own_dens = true;
-    ctx->live_handles++;
-    *out = m.release();
+    made.publish(out);
     return PDBEDA_OK;
 }
 
@@ -3663,9 +3612,7 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
 extern "C" int pdbeda_map_pair_moments(pdbeda_map *a, pdbeda_map *b, float b_floor, int64_t *n, double sums[5]) {
     if (!a || !b) return PDBEDA_ERR_ARGUMENT;
     pdbeda_ctx *ctx = a->ctx;
-    if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts");
-    if (a->n_vox != b->n_vox || memcmp(a->geom.ncrs, b->geom.ncrs, sizeof a->geom.ncrs) != 0 || memcmp(a->geom.unique_ncrs, b->geom.unique_ncrs, sizeof a->geom.unique_ncrs) != 0)
-        return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different shapes");
+    if (int rc = same_grid(ctx, a->geom, a->n_vox, b, "maps of different shapes", true)) return rc;
     if (std::isnan(b_floor)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "pair moments: the floor is NaN");
     if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     const Geom &g = a->geom;
@@ -3748,22 +3695,6 @@ static bool filter_grid_fits(const Geom &g) {
     return run * ((nr * ns + FC_ROWS - 1) / FC_ROWS) < lim && col * ((nr + FL_CHUNK - 1) / FL_CHUNK) * ns < lim && col * ((ns + FL_CHUNK - 1) / FL_CHUNK) * nr < lim;
 }
 
-// A new map on a geometry (map_like: that of `like`), its voxels not yet written (the arena goes back to the pool with the map when the caller drops it).
-static int map_on(pdbeda_ctx *ctx, const char *site, const Geom &geom, int64_t n_vox, std::unique_ptr<pdbeda_map> *out, float **dens) {
-    std::unique_ptr<pdbeda_map> m(new pdbeda_map());
-    m->ctx = ctx;
-    m->geom = geom;
-    m->n_vox = n_vox;
-    float *d = nullptr;
-    if (int rc = arena_carve(ctx, site, &m->arena, [&](Carver &cv) { cv.take(m->geom_dev, 1); cv.take(d, (size_t)m->n_vox); })) return rc;
-    *dens = d;
-    *out = std::move(m);
-    return 0;
-}
-static int map_like(pdbeda_ctx *ctx, const char *site, const pdbeda_map *like, std::unique_ptr<pdbeda_map> *out, float **dens) {
-    return map_on(ctx, site, like->geom, like->n_vox, out, dens);
-}
-
 // The launch graph: the W arrays (under renormalisation) in one row of scratch; k_filter_c<1> from the map into fp64 volume 0; k_filter_line<double> along r
 // into volume 1; k_filter_line<float> along s into the new map.  One wait.  Scratch: two fp64 volumes.
 extern "C" int pdbeda_map_filter(pdbeda_map *map, const double *taps_c, int32_t radius_c, const double *taps_r, int32_t radius_r, const double *taps_s, int32_t radius_s,
@@ -3782,9 +3713,8 @@ extern "C" int pdbeda_map_filter(pdbeda_map *map, const double *taps_c, int32_t 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
     const size_t nv = (size_t)map->n_vox;
-    std::unique_ptr<pdbeda_map> m;
-    float *d_out = nullptr;
-    if (int rc = map_like(ctx, "map filter", map, &m, &d_out)) return rc;
+    MadeMap made;
+    if (int rc = made.make_like("map filter", map)) return rc;
     double *d_vol = nullptr, *d_wc = nullptr, *d_wr = nullptr, *d_ws = nullptr;
     const int rc = with_scratch(ctx, "map filter", [&](Carver &cv) {
         cv.take(d_vol, 2 * nv);
@@ -3793,7 +3723,7 @@ extern "C" int pdbeda_map_filter(pdbeda_map *map, const double *taps_c, int32_t 
         cv.take(d_ws, renorm ? (size_t)ns : 0);
     }, [&]() -> int {
         hipStream_t st = ctx->stream;
-        HIP_TRY(ctx, h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom)));
+        HIP_TRY(ctx, made.geometry_up());
         if (renorm) {
             const H2DItem in[3] = {{d_wc, fa.weight[0].data(), 8 * (size_t)nc}, {d_wr, fa.weight[1].data(), 8 * (size_t)nr}, {d_ws, fa.weight[2].data(), 8 * (size_t)ns}};
             HIP_TRY(ctx, h2d_row(ctx, in, 3));
@@ -3803,15 +3733,12 @@ extern "C" int pdbeda_map_filter(pdbeda_map *map, const double *taps_c, int32_t 
         { PROF(ctx, "k_filter_c"); hipLaunchKernelGGL(k_filter_c<1>, dim3((unsigned)(runs * ((rows + FC_ROWS - 1) / FC_ROWS))), dim3(256), 0, st, map->dens, (const float *)nullptr, nc,
                                                        g.crs_interval[0], rows, runs, fa.taps[0], d_vol, (int64_t)nv); }
         filter_line_launch<double>(ctx, g, 1, fa.taps[1], d_vol, d_vol + nv, nullptr, nullptr, nullptr);
-        filter_line_launch<float>(ctx, g, 2, fa.taps[2], d_vol + nv, d_out, renorm ? d_wc : nullptr, renorm ? d_ws : nullptr, renorm ? d_wr : nullptr);
+        filter_line_launch<float>(ctx, g, 2, fa.taps[2], d_vol + nv, made.dens, renorm ? d_wc : nullptr, renorm ? d_ws : nullptr, renorm ? d_wr : nullptr);
         HIP_TRY(ctx, hipGetLastError());
         return 0;
     });
     if (rc) return rc;
-    m->dens = d_out;
-    m->own_dens = true;
-    ctx->live_handles++;
-    *out = m.release();
+    made.publish(out);
     return PDBEDA_OK;
 }
 
@@ -3824,8 +3751,7 @@ extern "C" int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b, const double
     if (!a) return PDBEDA_ERR_ARGUMENT;
     pdbeda_ctx *ctx = a->ctx;
     if (b) {
-        if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts");
-        if (a->n_vox != b->n_vox || memcmp(a->geom.ncrs, b->geom.ncrs, sizeof a->geom.ncrs) != 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different shapes");
+        if (int rc = same_grid(ctx, a->geom, a->n_vox, b)) return rc;
     } else if (mean_b || std_b || cc) {
         return fail(ctx, PDBEDA_ERR_ARGUMENT, "local stats: an output of the second map is requested without a second map");
     }
@@ -3842,11 +3768,10 @@ extern "C" int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b, const double
     const size_t nv = (size_t)a->n_vox;
     const int n_ch = b ? 5 : 2;
     pdbeda_map **const want[6] = {mean_a, std_a, z_a, mean_b, std_b, cc};
-    std::unique_ptr<pdbeda_map> made[6];
-    float *d_made[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    MadeMap made[6];
     for (int k = 0; k < 6; ++k)
         if (want[k])
-            if (int rc = map_like(ctx, "local stats", a, &made[k], &d_made[k])) return rc;
+            if (int rc = made[k].make_like("local stats", a)) return rc;
     double *d_vol = nullptr, *d_wc = nullptr, *d_wr = nullptr, *d_ws = nullptr;
     const int rc = with_scratch(ctx, "local stats", [&](Carver &cv) {
         cv.take(d_vol, (size_t)(n_ch + 1) * nv);
@@ -3856,7 +3781,7 @@ extern "C" int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b, const double
     }, [&]() -> int {
         hipStream_t st = ctx->stream;
         for (int k = 0; k < 6; ++k)
-            if (made[k]) HIP_TRY(ctx, h2d_one(ctx, made[k]->geom_dev, &made[k]->geom, sizeof(Geom)));
+            if (made[k].m) HIP_TRY(ctx, made[k].geometry_up());
         const H2DItem in[3] = {{d_wc, fa.weight[0].data(), 8 * (size_t)nc}, {d_wr, fa.weight[1].data(), 8 * (size_t)nr}, {d_ws, fa.weight[2].data(), 8 * (size_t)ns}};
         HIP_TRY(ctx, h2d_row(ctx, in, 3));
         const int64_t rows = (int64_t)nr * ns;
@@ -3876,19 +3801,14 @@ extern "C" int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b, const double
         p.nc = nc; p.nr = nr;
         p.w_c = d_wc; p.w_r = d_wr; p.w_s = d_ws;
         p.std_floor = std_floor;
-        p.mean_a = d_made[0]; p.std_a = d_made[1]; p.z_a = d_made[2]; p.mean_b = d_made[3]; p.std_b = d_made[4]; p.cc = d_made[5];
+        p.mean_a = made[0].dens; p.std_a = made[1].dens; p.z_a = made[2].dens; p.mean_b = made[3].dens; p.std_b = made[4].dens; p.cc = made[5].dens;
         { PROF(ctx, "k_local_finish"); hipLaunchKernelGGL(k_local_finish, dim3(grid_for(a->n_vox, 256, 8192)), dim3(256), 0, st, p); }
         HIP_TRY(ctx, hipGetLastError());
         return 0;
     });
     if (rc) return rc;
-    for (int k = 0; k < 6; ++k) {
-        if (!made[k]) continue;
-        made[k]->dens = d_made[k];
-        made[k]->own_dens = true;
-        ctx->live_handles++;
-        *want[k] = made[k].release();
-    }
+    for (int k = 0; k < 6; ++k)
+        if (made[k].m) made[k].publish(want[k]);
     return PDBEDA_OK;
 }
 
@@ -3921,10 +3841,8 @@ extern "C" int pdbeda_map_resample(pdbeda_map *src, const pdbeda_geometry *dst_g
     const int tiles_c = (gd.ncrs[0] + RS_C - 1) / RS_C, tiles_r = (gd.ncrs[1] + RS_R - 1) / RS_R, tiles_s = (gd.ncrs[2] + RS_S - 1) / RS_S;
     const int64_t n_tiles = (int64_t)tiles_c * tiles_r * tiles_s;
     if (n_vox >= (1ll << 32) || n_tiles >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: a destination of 2^32 voxels or 2^31 tiles or more");
-    if (base) {
-        if (base->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "maps of different contexts");
-        if (base->n_vox != n_vox || memcmp(base->geom.ncrs, gd.ncrs, sizeof gd.ncrs) != 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map resample: base is not of the destination's shape");
-    }
+    if (base)
+        if (int rc = same_grid(ctx, gd, n_vox, base, "map resample: base is not of the destination's shape")) return rc;
     // every source grid position the kernel will cast: the map is affine, so its extreme over the destination box (grown by a voxel) sits at a corner
     const Geom &gs = src->geom;
     for (int k = 0; k < n_ops; ++k)
@@ -3941,11 +3859,10 @@ extern "C" int pdbeda_map_resample(pdbeda_map *src, const pdbeda_geometry *dst_g
         }
     if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<pdbeda_map> m, cov;
-    float *d_out = nullptr, *d_cov = nullptr;
-    if (int rc = map_on(ctx, "map resample", gd, n_vox, &m, &d_out)) return rc;
+    MadeMap made, cov;
+    if (int rc = made.make(ctx, "map resample", gd, n_vox)) return rc;
     if (coverage)
-        if (int rc = map_on(ctx, "map resample", gd, n_vox, &cov, &d_cov)) return rc;
+        if (int rc = cov.make(ctx, "map resample", gd, n_vox)) return rc;
     double *d_ops = nullptr;
     unsigned long long *d_ctr = nullptr;
     std::vector<unsigned long long> seen(4 * (size_t)RS_CTR_SLOTS, 0ull);
@@ -3953,16 +3870,16 @@ extern "C" int pdbeda_map_resample(pdbeda_map *src, const pdbeda_geometry *dst_g
     const int rc = with_scratch(ctx, "map resample", [&](Carver &cv) { cv.take(d_ops, 12 * (size_t)n_ops); cv.take(d_ctr, 4 * (size_t)RS_CTR_SLOTS); }, [&]() -> int {
         hipStream_t st = ctx->stream;
         HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, 32 * (size_t)RS_CTR_SLOTS, st));
-        HIP_TRY(ctx, h2d_one(ctx, m->geom_dev, &m->geom, sizeof(Geom)));
-        if (cov) HIP_TRY(ctx, h2d_one(ctx, cov->geom_dev, &cov->geom, sizeof(Geom)));
+        HIP_TRY(ctx, made.geometry_up());
+        if (cov.m) HIP_TRY(ctx, cov.geometry_up());
         HIP_TRY(ctx, h2d_one(ctx, d_ops, ops, 96 * (size_t)n_ops));
         ResampleArgs a;
-        a.src_geom = src->geom_dev; a.src = src->dens; a.dst_geom = m->geom_dev;
+        a.src_geom = src->geom_dev; a.src = src->dens; a.dst_geom = made.m->geom_dev;
         a.tiles_c = tiles_c; a.tiles_r = tiles_r;
         a.ops = d_ops; a.n_ops = n_ops;
         a.mean = (flags & PDBEDA_RESAMPLE_MEAN) ? 1 : 0; a.stage = stage;
         a.fill = fill; a.base = base ? base->dens : nullptr; a.alpha = alpha;
-        a.out = d_out; a.coverage = d_cov; a.counters = d_ctr;
+        a.out = made.dens; a.coverage = cov.dens; a.counters = d_ctr;
         {
             PROF(ctx, "k_map_resample");
             if (order == 0) hipLaunchKernelGGL(k_map_resample<0>, dim3((unsigned)n_tiles), dim3(256), 0, st, a);
@@ -3979,16 +3896,8 @@ extern "C" int pdbeda_map_resample(pdbeda_map *src, const pdbeda_geometry *dst_g
             counters[k] = 0;
             for (int slot = 0; slot < RS_CTR_SLOTS; ++slot) counters[k] += (int64_t)seen[4 * (size_t)slot + k];
         }
-    m->dens = d_out;
-    m->own_dens = true;
-    ctx->live_handles++;
-    *out = m.release();
-    if (cov) {
-        cov->dens = d_cov;
-        cov->own_dens = true;
-        ctx->live_handles++;
-        *coverage = cov.release();
-    }
+    made.publish(out);
+    if (cov.m) cov.publish(coverage);
     return PDBEDA_OK;
 }
 
@@ -4247,22 +4156,24 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     t_marks[4] = now_s();
     const bool host_sized = union_plan.fits && !ctx->debug_shrink_totals;   // (what the planner declines, or the debug hook that wants the device's own sizing: the waiting path sizes and reports)
     hipError_t e;
-    std::vector<char> block(upload_bytes, 0);      // (staged: the copy below reads a pinned block or, too large for that, has finished reading when it returns)
+    // The row is written straight into the pinned block when it fits there -- copied by the union job's first launch (k_job_init) --, else into one pageable
+    // block that h2d_row has finished reading when it returns.  What no put covers is zero: the pairs' touch flags, and the padding.
+    std::vector<char> block;
     {
-        auto put = [&](const void *dev, const void *src, size_t bytes) { if (bytes) memcpy(block.data() + ((const char *)dev - aux.base), src, bytes); };
-        put(d_pool_cloud, pool_cloud.data(), 4 * (size_t)n_pool);
-        put(d_pool_group, pool_group.data(), 4 * (size_t)n_pool);
-        put(d_pool_voff, pool_voff.data(), 8 * (size_t)(n_pool + 1));
-        put(d_set_off, set_off.data(), 8 * (size_t)(n + 1));
-        put(d_pa, pair_a.data(), 4 * (size_t)n_pairs);
-        put(d_pb, pair_b.data(), 4 * (size_t)n_pairs);
-        if (host_sized) put(d_union_vols, union_vols.data(), sizeof(VolDesc) * (size_t)n_groups);
-    }
-    {
-        const size_t span16 = (upload_bytes + 15) & ~(size_t)15;      // (upload_bytes is a carve boundary: a multiple of 256)
-        if (char *stage = copy_kernels() && span16 <= ((size_t)1 << 20) ? pinned_take(ctx, span16) : nullptr) {      // staged now, copied by the union job's first launch (k_job_init)
-            memcpy(stage, block.data(), upload_bytes);
-            gs.pend_src = stage; gs.pend_dst = aux.base; gs.pend_bytes = span16;
+        StagedRow row{nullptr, aux.base, upload_bytes};      // (upload_bytes is a carve boundary: a multiple of 256, and so is bytes16())
+        char *const stage = copy_kernels() && row.bytes16() <= STAGED_ROW_LIMIT ? pinned_take(ctx, row.bytes16()) : nullptr;
+        if (stage) memset(stage, 0, upload_bytes);
+        else block.assign(upload_bytes, 0);
+        row.stage = stage ? stage : block.data();
+        row.put(d_pool_cloud, pool_cloud.data(), 4 * (size_t)n_pool);
+        row.put(d_pool_group, pool_group.data(), 4 * (size_t)n_pool);
+        row.put(d_pool_voff, pool_voff.data(), 8 * (size_t)(n_pool + 1));
+        row.put(d_set_off, set_off.data(), 8 * (size_t)(n + 1));
+        row.put(d_pa, pair_a.data(), 4 * (size_t)n_pairs);
+        row.put(d_pb, pair_b.data(), 4 * (size_t)n_pairs);
+        if (host_sized) row.put(d_union_vols, union_vols.data(), sizeof(VolDesc) * (size_t)n_groups);
+        if (stage) {
+            gs.pend = {stage, aux.base, row.bytes16()};
             e = hipSuccess;
         } else {
             const H2DItem in[1] = {{aux.base, block.data(), upload_bytes}};

@@ -10,7 +10,7 @@ import numpy as np
 
 import contacts_checker as chk
 
-PINNED_BLOCK = 4 << 20          # pdbeda_ctx_create: hipHostMalloc(&ctx->pinned, 4 << 20): what pinned_out hands out per call
+PINNED_BLOCK = 4 << 20          # PINNED_BLOCK_BYTES (pdbeda_stage.h), the context's pinned block: what pinned_out hands out per call
 SCAN_TILE = 8 * 1024            # k_grid_scan: 1024 lanes x 8 cells per trip
 MAX_SHIFT = 1 << 20             # check_images: the largest cell shift
 

@@ -158,8 +158,8 @@ def test_checker_equals_oracle_on_golden_inputs(name):
 
 
 # ---- the large entry ---------------------------------------------------------------------------------------------------------------
-PINNED = 4 << 20          # the context's pinned block (pdbeda_hip.hip: pinned_cap)
-STAGED = 1 << 20          # the staged row of the aux block (pdbeda_hip.hip:3642)
+PINNED = 4 << 20          # the context's pinned block (pdbeda_stage.h: PINNED_BLOCK_BYTES)
+STAGED = 1 << 20          # the staged row of the aux block (pdbeda_stage.h: STAGED_ROW_LIMIT)
 
 
 def _span(b, a):
@@ -169,12 +169,12 @@ def _span(b, a):
 def switch_points(n, n_pool, n_pairs, n_groups):
     """What pdbeda_aggregate_cloud compares at its three switch points for an entry of n atoms, n_pool pooled clouds, n_pairs bonded
     pairs between pooled names and n_groups union groups (residues with a pooled cloud + 1), on an idle pinned block:
-    T1 (pdbeda_hip.hip:3466 -> list_stats_one_trip, 1690)   the clouds' table comes in one trip while 44 * (4 n + 64) + 4096 < PINNED;
-    T2 (3568-3577, 3642)   the uploaded part of the aux block is staged while it is <= STAGED: the carve's items in 256-byte steps --
+    T1 (list_stats_one_trip, for the clouds' list)   the clouds' table comes in one trip while 44 * (4 n + 64) + 4096 < PINNED;
+    T2 (the "aggregate cloud" carve up to upload_bytes, STAGED_ROW_LIMIT)   the uploaded part of the aux block is staged while it is <= STAGED: the carve's items in 256-byte steps --
                            48-byte volume descriptors, 2 x 4 n_pool, 8 (n_pool + 1), 8 (n + 1), 3 x 4 max(n_pairs, 1);
-    T3 (3680-3689)         k_union_finish delivers while fin_bytes <= PINNED: 64-byte lines of the counters (64 bytes), 8 + 8 + 24 + 4
+    T3 (fin_bytes)         k_union_finish delivers while fin_bytes <= PINNED: 64-byte lines of the counters (64 bytes), 8 + 8 + 24 + 4
                            bytes a row of u_cap = 2 n_pool + 64 rows, 4 max(n_pairs, 1) and 8 n_pool.
-    Small staged inputs (h2d_row: at most 256 KiB) may share the block at those moments: the 10 % that every size keeps from its limit
+    Small staged inputs (h2d_row: at most H2D_ROW_SPAN, 256 KiB) may share the block at those moments: the 10 % that every size keeps from its limit
     is more than that.  Returns {name: (bytes compared, limit)}; the path below the switch runs while bytes <= limit (T1: <)."""
     np1 = max(n_pairs, 1)
     t1 = 44 * (4 * n + 64) + 4096
