@@ -605,6 +605,72 @@ int pdbeda_map_resample(pdbeda_map *src, const pdbeda_geometry *dst_geom,
                         pdbeda_map *base /* may be NULL; on dst_geom's shape */, double alpha,
                         pdbeda_map **out, pdbeda_map **coverage /* may be NULL */, int64_t counters[4] /* may be NULL */);
 
+/* ---- reciprocal space: the 3-D Fourier transform of a resident map, and what works on a resident spectrum ---- */
+/* The forward transform (no reference counterpart; every other map call works in real space).  *out is a NEW spectrum owned by the library
+ * in a self-releasing device arena of the map's context (pdbeda_spectrum_free): the Hermitian half [ns][nr][nh] complex fp64, nh = nc / 2 + 1,
+ * of numpy's rfftn convention -- unnormalised,
+ *   F[k2][k1][k0] = sum_{s, r, c} x[s][r][c] * exp(-2 pi i (c k0 / nc + r k1 / nr + s k2 / ns)),   k0 = 0 .. nc / 2.
+ * The domain is ALL stored voxels ncrs: the stored box is the period, whatever the cell is (for a crystal map transform the whole cell,
+ * DensityMatrix.symmetryExpanded on ccp4.cellHeader; a cut-out is periodic in its own box).  The map is neither read for its geometry beyond
+ * ncrs nor screened: values that are not finite propagate.
+ * The bits are defined.  Lines are transformed along c, then r, then s.  A line of length n is the autosort (Stockham) mixed-radix transform of
+ * pdb_eda_amd/csrc/pdbeda_fourier_line.h: the radices of n = 2^a 3^b 5^c 7^d are 4 (a / 2 times), 2 (if a is odd), 3, 5, 7 in this order, the
+ * twiddles come from a host-made fp64 table w[k] = exp(-2 pi i k / n) with every component within 1 ulp and w[0], w[n/4], w[n/2], w[3n/4] exact,
+ * every product and sum is plain unfused IEEE fp64 in the order that header states.  A row along c is run as a complex line whose imaginary
+ * parts are zero (no half-length or two-rows-in-one trick), of which columns 0 .. nc / 2 are kept.  The same line gives the same bits wherever
+ * it lies; a lane owns its outputs, there is no atomic, two calls agree to the bit, and tests/fourier_harness.cpp gives the same bits on a CPU.
+ * PDBEDA_ERR_ARGUMENT before any launch: a NULL argument; an axis that is not plannable, i.e. not 2^a 3^b 5^c 7^d or above
+ * PDBEDA_FFT_MAX_AXIS (the message names the axis and the next plannable length).  Synchronous; a failing call leaves the context usable and
+ * *out untouched.  Scratch: none beyond the spectrum itself (the passes along r and s run in place) and, once per context and length, the table. */
+#define PDBEDA_FFT_MAX_AXIS 1024
+typedef struct pdbeda_spectrum pdbeda_spectrum;
+int pdbeda_map_fft(pdbeda_map *map, pdbeda_spectrum **out);
+/* The inverse transform: a NEW map on the geometry of `like`, with the ownership of pdbeda_map_combine's result; only the geometry of `like`
+ * is read, and its ncrs must equal the shape the spectrum was made from.  Lines along s, then r, then c, with the conjugate twiddles; the
+ * pass along c rebuilds the whole Hermitian line from the half (column k0 > nc / 2 is the conjugate of column nc - k0 OF THE SAME ROW of
+ * the half-transformed data; the imaginary parts of column 0 and, for even nc, of column nc / 2 are ignored), and the voxel is
+ * float32(re / (double)N), N = nc nr ns: one fp64 division, one rounding.  The spectrum is not changed.  PDBEDA_ERR_ARGUMENT: a NULL
+ * argument, another context, another shape.  Synchronous; failing calls leave *out untouched.  Scratch: ONE spectrum-sized volume. */
+int pdbeda_spectrum_inverse(pdbeda_spectrum *spec, pdbeda_map *like, pdbeda_map **out);
+int pdbeda_spectrum_shape(pdbeda_spectrum *spec, int32_t ncrs[3]);                 /* the shape of the MAP the spectrum was made from */
+int pdbeda_spectrum_download(pdbeda_spectrum *spec, double *out /* [ns][nr][nc/2+1][2] */);
+int pdbeda_spectrum_free(pdbeda_spectrum *spec);
+/* Single coefficients: out[i] = (re, im) of F at idx[i] = (k0, k1, k2), crs order.  Any integer index is reduced modulo its axis (floor
+ * modulo); a coefficient of the missing half, k0 > nc / 2 after reduction, is the conjugate of F[(ns - k2) % ns][(nr - k1) % nr][nc - k0].
+ * n == 0 succeeds.  PDBEDA_ERR_ARGUMENT: NULL arguments with n > 0, n < 0.  Synchronous. */
+int pdbeda_spectrum_values(pdbeda_spectrum *spec, const int32_t *idx /* n x 3, crs order */, int64_t n, double *out /* n x 2 */);
+/* The metric of the calls below is the CALLER's: six doubles {m00, m11, m22, m01, m02, m12} of the symmetric matrix M with s^2 = h^T M h
+ * = 1 / d^2 for the frequency numbers h of the stored box as the period (ccp4.reciprocalMetric: M = (B^T B)^-1, the columns of B being
+ * b_k = orthoMat[:, map2crs[k]] * ncrs[k] / crsInterval[k]).  For index j on an axis of n:  h = j if 2 j <= n, else j - n.  Then, in unfused
+ * fp64 and in this order, every m multiplied by the EXACT integer product converted to fp64,
+ *   s2 = ((m00 * (h0 h0) + m11 * (h1 h1)) + m22 * (h2 h2)) + 2 * ((m01 * (h0 h1) + m02 * (h0 h2)) + m12 * (h1 h2)).
+ *
+ * pdbeda_spectrum_scale multiplies every coefficient IN PLACE by a radial transfer function g(s2) given as a table over [0, s2_max]:
+ *   t = s2 * ((n_table - 1) / s2_max)  (the quotient formed once, in fp64);  i = floor(t);
+ *   g = table[i] + (t - i) * (table[i + 1] - table[i])  for 0 <= t < n_table - 1;  g = table[n_table - 1] at t == n_table - 1 exactly;
+ *   g = beyond for t > n_table - 1;  g = table[0] where t >= 0 is false (a metric that is not positive definite).
+ * Both components are multiplied by the real g: one rounding each.  A lane owns its coefficient.  PDBEDA_ERR_ARGUMENT before any launch: NULL
+ * arguments, n_table outside 2 .. PDBEDA_SPECTRUM_MAX_TABLE, a non-finite metric, table entry or `beyond`, s2_max not finite or not > 0.
+ * Synchronous; a failing call leaves the spectrum untouched. */
+#define PDBEDA_SPECTRUM_MAX_TABLE 4096
+int pdbeda_spectrum_scale(pdbeda_spectrum *spec, const double metric[6], const double *table, int32_t n_table, double s2_max, double beyond);
+/* Sums over resolution shells of one spectrum, or of two of one shape.  A coefficient belongs to shell j iff edges[j] <= s2 < edges[j + 1]
+ * (s2 as above); outside the edges it is dropped.  The sums run over the FULL spectrum, evaluated on the half: a coefficient of column 0 and,
+ * for even nc, of column nc / 2 has weight w = 1, every other w = 2.  Per shell: count[j] = sum w (integers), and sums[j] = { sum w |A|^2,
+ * sum w |B|^2, sum w Re(A conj B), sum w Im(A conj B) } with |A|^2 = Are Are + Aim Aim, Re = Are Bre + Aim Bim, Im = Aim Bre - Are Bim, unfused
+ * fp64, each multiplied by w; the last three are exactly 0 when b is NULL.  (Over the full spectrum of two real maps Im(A conj B) of a
+ * coefficient and of its mirror cancel; the fourth sum is that of the STORED half, columns 0 .. nc / 2, under these weights.)  The fold has a fixed order, as pdbeda_map_pair_moments folds: a
+ * number of workgroups fixed by the shape, each over a contiguous run of coefficients in index order, per-workgroup per-shell partials, and a
+ * fold of every shell's partials in an order fixed by that number (strided sums, then a binary tree); no floating-point atomic: the same
+ * spectra with the same edges give the same bits in every run.
+ * PDBEDA_ERR_ARGUMENT before any launch: NULL a, metric or edges; n_shells outside 1 .. PDBEDA_SPECTRUM_MAX_SHELLS; a non-finite metric or
+ * edge; edges that do not strictly ascend; b of another shape or context.  Synchronous; either output may be NULL; a failing call leaves
+ * the outputs untouched. */
+#define PDBEDA_SPECTRUM_MAX_SHELLS 256
+int pdbeda_spectrum_shells(pdbeda_spectrum *a, pdbeda_spectrum *b /* may be NULL */, const double metric[6],
+                           const double *edges /* n_shells + 1, strictly ascending */, int32_t n_shells,
+                           int64_t *count /* n_shells */, double *sums /* n_shells x 4 */);
+
 /* ---- aggregateCloud ------------------------------------------------------------------ */
 /* DensityAnalysis.aggregateCloud up to its statistics tail (densityAnalysis.py:571-731) as ONE call: the clouds of every
  * eligible atom (findAberrantBlobs, 603), the centroid-distance cut-off over all atoms (607), the best cloud and the pooled

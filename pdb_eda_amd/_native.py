@@ -127,6 +127,14 @@ _SIGS = {
     "pdbeda_map_filter": (C.c_int, [_p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_uint32, C.POINTER(_p)]),
     "pdbeda_map_local_stats": (C.c_int, [_p, _p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_double, _p, _p, _p, _p, _p, _p]),
     "pdbeda_map_resample": (C.c_int, [_p, C.POINTER(Geometry), _p, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _p, C.c_double, C.POINTER(_p), C.POINTER(_p), _p]),
+    "pdbeda_map_fft": (C.c_int, [_p, C.POINTER(_p)]),
+    "pdbeda_spectrum_inverse": (C.c_int, [_p, _p, C.POINTER(_p)]),
+    "pdbeda_spectrum_shape": (C.c_int, [_p, _p]),
+    "pdbeda_spectrum_download": (C.c_int, [_p, _p]),
+    "pdbeda_spectrum_free": (C.c_int, [_p]),
+    "pdbeda_spectrum_values": (C.c_int, [_p, _p, _i64, _p]),
+    "pdbeda_spectrum_scale": (C.c_int, [_p, _p, _p, C.c_int32, C.c_double, C.c_double]),
+    "pdbeda_spectrum_shells": (C.c_int, [_p, _p, _p, _p, C.c_int32, _p, _p]),
     "pdbeda_aggregate_cloud": (C.c_int, [_p, C.POINTER(CloudAtoms), C.c_float, C.c_double, C.POINTER(_p)]),
     "pdbeda_cloud_counts": (C.c_int, [_p, _p, _p]),
     "pdbeda_cloud_atom_rows": (C.c_int, [_p, _p, _p, _p, _p, _p]),
@@ -542,6 +550,69 @@ RESAMPLE_MEAN = 1                # PDBEDA_RESAMPLE_MEAN
 RESAMPLE_COUNTERS = ("covered", "uncovered", "stagedPairs", "directPairs")      # the counters of pdbeda_map_resample, in order
 
 
+FFT_MAX_AXIS = 1024              # PDBEDA_FFT_MAX_AXIS
+SPECTRUM_MAX_TABLE = 4096        # PDBEDA_SPECTRUM_MAX_TABLE
+SPECTRUM_MAX_SHELLS = 256        # PDBEDA_SPECTRUM_MAX_SHELLS
+
+
+class DeviceSpectrum(object):
+    """The Hermitian half spectrum of a map, resident in HBM (pdbeda_map_fft): complex fp64 [ns][nr][nc / 2 + 1], numpy's rfftn."""
+
+    def __init__(self, ctx, handle):
+        self._ctx, self._h = ctx, handle
+        ncrs = np.zeros(3, dtype=np.int32)
+        ctx.check(ctx._lib.pdbeda_spectrum_shape(handle, _ptr(ncrs)), "pdbeda_spectrum_shape")
+        self.ncrs = tuple(int(v) for v in ncrs)
+        self.shape = (self.ncrs[2], self.ncrs[1], self.ncrs[0] // 2 + 1)
+
+    def download(self):
+        """The coefficients as a complex128 array [ns][nr][nc / 2 + 1]."""
+        out = np.empty(self.shape, dtype=np.complex128)
+        self._ctx.check(self._ctx._lib.pdbeda_spectrum_download(self._h, _ptr(out)), "pdbeda_spectrum_download")
+        return out
+
+    def values(self, idx):
+        """pdbeda_spectrum_values: the coefficients at the (n, 3) integer indices ``idx`` (crs order; any integer, either half)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros(len(idx), dtype=np.complex128)
+        self._ctx.check(self._ctx._lib.pdbeda_spectrum_values(self._h, _ptr(idx) if len(idx) else None, len(idx), _ptr(out) if len(idx) else None), "pdbeda_spectrum_values")
+        return out
+
+    def scale(self, metric, table, s2_max, beyond=0.0):
+        """pdbeda_spectrum_scale: every coefficient times the table's g(s^2), IN PLACE."""
+        metric = np.ascontiguousarray(metric, dtype=np.float64).reshape(6)
+        table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+        self._ctx.check(self._ctx._lib.pdbeda_spectrum_scale(self._h, _ptr(metric), _ptr(table), len(table), C.c_double(float(s2_max)), C.c_double(float(beyond))),
+                        "pdbeda_spectrum_scale")
+
+    def shells(self, other, metric, edges):
+        """pdbeda_spectrum_shells: (count int64 [n], sums float64 [n][4]) over the shells between the ``edges`` of s^2."""
+        metric = np.ascontiguousarray(metric, dtype=np.float64).reshape(6)
+        edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        n = len(edges) - 1
+        count, sums = np.zeros(max(n, 0), dtype=np.int64), np.zeros((max(n, 0), 4), dtype=np.float64)
+        self._ctx.check(self._ctx._lib.pdbeda_spectrum_shells(self._h, other._h if other is not None else None, _ptr(metric), _ptr(edges), n, _ptr(count), _ptr(sums)),
+                        "pdbeda_spectrum_shells")
+        return count, sums
+
+    def inverse(self, like):
+        """pdbeda_spectrum_inverse: a new resident map on the geometry of the DeviceMap ``like``."""
+        h = C.c_void_p()
+        self._ctx.check(self._ctx._lib.pdbeda_spectrum_inverse(self._h, like._h, C.byref(h)), "pdbeda_spectrum_inverse")
+        return DeviceMap._made(like, h)
+
+    def free(self):
+        if getattr(self, "_h", None) is not None and self._ctx._h:
+            self._ctx._lib.pdbeda_spectrum_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class DeviceMap(object):
     """A density grid resident in HBM + its unit-cell basis."""
 
@@ -699,6 +770,12 @@ class DeviceMap(object):
             return int(digit(bits - 16, 0, 0).sum())
         keys = radix_select(digit, bits, ranks)
         return [np.array([k], dtype=np.uint64).view(np.float64)[0] if which else float(np.array([k], dtype=np.uint32).view(np.float32)[0]) for k in keys]
+
+    def fft(self):
+        """pdbeda_map_fft: the Hermitian half spectrum of this map as a DeviceSpectrum."""
+        h = C.c_void_p()
+        self._ctx.check(self._ctx._lib.pdbeda_map_fft(self._h, C.byref(h)), "pdbeda_map_fft")
+        return DeviceSpectrum(self._ctx, h)
 
     def download(self):
         """The float32 grid [ns][nr][nc] copied back to the host."""

@@ -270,6 +270,120 @@ def boxHeader(centre, halfWidth, spacing):
     return _headerFromFields(ncrs, start, interval, length, (90.0, 90.0, 90.0), (1, 2, 3))
 
 
+# -- reciprocal space: plannable sizes, the metric, shells and radial tables for ``DensityMatrix.fourier`` (host numpy; no reference counterpart) --
+FFT_MAX_AXIS = _native.FFT_MAX_AXIS                  # PDBEDA_FFT_MAX_AXIS of include/pdbeda.h
+SPECTRUM_MAX_TABLE = _native.SPECTRUM_MAX_TABLE      # PDBEDA_SPECTRUM_MAX_TABLE
+SPECTRUM_MAX_SHELLS = _native.SPECTRUM_MAX_SHELLS    # PDBEDA_SPECTRUM_MAX_SHELLS
+
+
+def isFourierSize(n):
+    """Whether an axis of ``n`` indices can be transformed: n = 2^a 3^b 5^c 7^d, 1 <= n <= FFT_MAX_AXIS (pdbeda_fft_plan)."""
+    n = int(n)
+    if n < 1 or n > FFT_MAX_AXIS:
+        return False
+    for p in (2, 3, 5, 7):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
+def fourierSize(n):
+    """The next plannable length at or above ``n``; ValueError beyond FFT_MAX_AXIS."""
+    k = max(int(n), 1)
+    while k <= FFT_MAX_AXIS:
+        if isFourierSize(k):
+            return k
+        k += 1
+    raise ValueError("no plannable Fourier length at or above %d (the longest line is %d)" % (int(n), FFT_MAX_AXIS))
+
+
+def fourierHeader(header):
+    """The WHOLE unit cell of ``header`` sampled at the next plannable intervals (``fourierSize`` of every xyzInterval), crsStart 0: the
+    destination of a tricubic ``resampled`` / ``symmetryExpanded`` when the cell's own sampling cannot be transformed.  A cell whose sampling
+    is plannable gives ``cellHeader``'s grid."""
+    interval = [fourierSize(v) for v in header.xyzInterval]
+    return _headerFromFields([interval[a] for a in header.map2crs], (0, 0, 0), interval, header.xyzLength, (header.alpha, header.beta, header.gamma),
+                             (header.col2xyz, header.row2xyz, header.sec2xyz), header.spaceGroup)
+
+
+def reciprocalMetric(header):
+    """The six numbers {m00, m11, m22, m01, m02, m12} of M = (B^T B)^-1 for the STORED BOX of ``header`` as the period: the columns of B are
+    b_k = orthoMat[:, map2crs[k]] * ncrs[k] / crsInterval[k], k in crs order, and s^2 = h^T M h = 1 / d^2 for the frequency numbers h of a
+    coefficient (what ``pdbeda_spectrum_scale`` / ``pdbeda_spectrum_shells`` take).  For a whole-cell map h are the Miller indices in crs order."""
+    ortho = np.asarray(header.orthoMat, dtype=np.float64)
+    b = np.stack([ortho[:, header.map2crs[k]] * (float(header.ncrs[k]) / float(header.crsInterval[k])) for k in range(3)], axis=1)
+    m = np.linalg.inv(b.T.dot(b))
+    return np.array([m[0, 0], m[1, 1], m[2, 2], 0.5 * (m[0, 1] + m[1, 0]), 0.5 * (m[0, 2] + m[2, 0]), 0.5 * (m[1, 2] + m[2, 1])], dtype=np.float64)
+
+
+def _nyquist(header, metric):
+    """The smallest |s| of the three axis Nyquist points (h = n / 2 along one axis): the resolution every direction of the box supports."""
+    return min(0.5 * header.ncrs[k] * math.sqrt(metric[k]) for k in range(3))
+
+
+def maxS2(header):
+    """An upper bound of s^2 over the coefficients of the stored box: the largest over the eight corners h = +- n / 2, times 1 + 2^-20."""
+    m = reciprocalMetric(header)
+    best = 0.0
+    for sr in (-1.0, 1.0):
+        for ss in (-1.0, 1.0):
+            h = (0.5 * header.ncrs[0], sr * 0.5 * header.ncrs[1], ss * 0.5 * header.ncrs[2])
+            best = max(best, m[0] * h[0] * h[0] + m[1] * h[1] * h[1] + m[2] * h[2] * h[2] + 2.0 * (m[3] * h[0] * h[1] + m[4] * h[0] * h[2] + m[5] * h[1] * h[2]))
+    return best * (1.0 + 2.0 ** -20)
+
+
+def shellEdges(header, nShells, dMin=None, dMax=None):
+    """nShells + 1 ascending edges of s^2 = 1 / d^2 in equal steps of s^3, i.e. shells of equal reciprocal volume, from 1 / dMax to 1 / dMin.
+    dMin defaults to the Nyquist limit of the coarsest axis (the edge lies 2^-20 above it, so that the Nyquist coefficient is in the last
+    shell whatever the rounding); dMax defaults to twice the longest axis period of the box, so the first edge is above 0 and F(000) is
+    in no shell."""
+    n = int(nShells)
+    if n < 1 or n > SPECTRUM_MAX_SHELLS:
+        raise ValueError("shellEdges: 1 .. %d shells" % SPECTRUM_MAX_SHELLS)
+    m = reciprocalMetric(header)
+    hi = _nyquist(header, m) * (1.0 + 2.0 ** -20) if dMin is None else 1.0 / float(dMin)
+    lo = 0.5 * min(math.sqrt(m[k]) for k in range(3)) if dMax is None else 1.0 / float(dMax)
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo < hi):
+        raise ValueError("shellEdges: 0 < 1 / dMax < 1 / dMin is required")
+    cubes = lo ** 3 + (hi ** 3 - lo ** 3) * (np.arange(n + 1, dtype=np.float64) / n)
+    edges = np.cbrt(cubes) ** 2
+    edges[0], edges[-1] = lo * lo, hi * hi
+    return edges
+
+
+def bFactorTable(B, s2Max, n=1024):
+    """exp(-B s^2 / 4) at n equal steps of s^2 over [0, s2Max] for ``DensitySpectrum.scaled``: B > 0 blurs, B < 0 sharpens."""
+    return np.exp(-0.25 * float(B) * np.linspace(0.0, float(s2Max), int(n)))
+
+
+def resolutionTable(dMin=None, dMax=None, softness=0.1, s2Max=None, n=1024):
+    """A raised-cosine window in s = 1 / d at n equal steps of s^2 over [0, s2Max]: 1 inside the band 1 / dMax <= s <= 1 / dMin and 0 outside,
+    each edge s_c a half cosine from s_c (1 - softness / 2) to s_c (1 + softness / 2) (softness 0: a step).  s2Max defaults to the end of the
+    upper roll-off (pass ``beyond=0``); with dMax alone (a high-pass) s2Max must be given (pass ``beyond=1``)."""
+    soft = float(softness)
+    if not (0.0 <= soft < 2.0):
+        raise ValueError("resolutionTable: softness in [0, 2)")
+    if dMin is None and dMax is None:
+        raise ValueError("resolutionTable takes dMin, dMax or both")
+    if s2Max is None:
+        if dMin is None:
+            raise ValueError("resolutionTable: a high-pass table needs s2Max")
+        s2Max = ((1.0 + 0.5 * soft) / float(dMin)) ** 2 * (1.0 + 2.0 ** -20)
+    s = np.sqrt(np.linspace(0.0, float(s2Max), int(n)))
+
+    def lowpass(sc):
+        a, b = sc * (1.0 - 0.5 * soft), sc * (1.0 + 0.5 * soft)
+        if b <= a:
+            return (s <= sc).astype(np.float64)
+        return np.where(s <= a, 1.0, np.where(s >= b, 0.0, 0.5 * (1.0 + np.cos(np.pi * (np.clip(s, a, b) - a) / (b - a)))))
+    g = np.ones_like(s)
+    if dMin is not None:
+        g = g * lowpass(1.0 / float(dMin))
+    if dMax is not None:
+        g = g * (1.0 - lowpass(1.0 / float(dMax)))
+    return g
+
+
 class DensityHeader(object):
     """CCP4 header + derived cell geometry (ref ccp4.py:130-316).
 
@@ -386,6 +500,77 @@ class DensityHeader(object):
                                      self.orthogonal, np.asarray(self.orthoMat, dtype=np.float64),
                                      np.asarray(self.deOrthoMat, dtype=np.float64),
                                      np.asarray(self.origin, dtype=np.float64), self.gridLength, self.unitVolume)
+
+
+class DensitySpectrum(object):
+    """The Fourier transform of a DensityMatrix, resident in HBM: the Hermitian half [ns][nr][nc / 2 + 1] of numpy's ``rfftn`` of the stored
+    box, complex fp64 (``DensityMatrix.fourier``).  ``metric`` is ``reciprocalMetric`` of the map's header."""
+
+    def __init__(self, densityMatrix, deviceSpectrum):
+        self.densityMatrix = densityMatrix
+        self.header = densityMatrix.header
+        self._spec = deviceSpectrum
+        self.metric = reciprocalMetric(self.header)
+        self._scales = []
+
+    @property
+    def shape(self):
+        """(ns, nr, nc // 2 + 1)."""
+        return self._spec.shape
+
+    def values(self):
+        """The coefficients on the host: complex128 [ns][nr][nc // 2 + 1]."""
+        return self._spec.download()
+
+    def at(self, idx):
+        """The coefficients at integer indices ``idx`` ((n, 3), crs order: column, row, section frequency): any integer, reduced modulo the
+        axis; the missing half through the Hermitian mirror.  complex128 (n,)."""
+        return self._spec.values(idx)
+
+    def scale(self, table, s2Max, beyond=0.0):
+        """Multiply every coefficient IN PLACE by g(s^2): ``table`` holds g at equal steps of s^2 over [0, s2Max], read by linear
+        interpolation; ``beyond`` above s2Max (``pdbeda_spectrum_scale``).  Returns self."""
+        table = np.array(table, dtype=np.float64).reshape(-1)
+        self._spec.scale(self.metric, table, s2Max, beyond)
+        self._scales.append((table, float(s2Max), float(beyond)))
+        return self
+
+    def scaled(self, table, s2Max, beyond=0.0):
+        """A NEW spectrum: this one times g(s^2) (see ``scale``); this one is left as it is (the map is transformed again and the tables
+        this spectrum has seen are applied in their order)."""
+        out = DensitySpectrum(self.densityMatrix, self.densityMatrix._map.fft())
+        for t, s2, b in self._scales:
+            out.scale(t, s2, b)
+        return out.scale(table, s2Max, beyond)
+
+    def toMap(self):
+        """The inverse transform as a device-made DensityMatrix on the header of the map this spectrum came from."""
+        return self.densityMatrix._made(self._spec.inverse(self.densityMatrix._map))
+
+    def shells(self, other=None, edges=None, nShells=20, dMin=None, dMax=None):
+        """Sums over resolution shells (``pdbeda_spectrum_shells``): a dict of arrays per shell -- ``d_max`` and ``d_min`` (the shell's limits
+        in Angstrom), ``n`` (coefficients of the full spectrum), ``power`` (mean |F|^2) and, with ``other`` (a DensitySpectrum of the same
+        shape), ``powerOther``, ``fsc`` = Re sum(A conj B) / sqrt(sum |A|^2 sum |B|^2), ``phaseCosine`` (the cosine of the phase of sum(A conj B) over the STORED half with its weights:
+        1 for maps that agree, below 1 when one is shifted against the other) and ``scale``
+        (the least-squares k of self ~ k other: Re sum(A conj B) / sum |B|^2).  NaN where a denominator is 0.  ``edges`` are in s^2
+        (default: ``shellEdges(header, nShells, dMin, dMax)``)."""
+        edges = shellEdges(self.header, nShells, dMin, dMax) if edges is None else np.asarray(edges, dtype=np.float64).reshape(-1)
+        count, sums = self._spec.shells(None if other is None else other._spec, self.metric, edges)
+        saa, sbb, re, im = sums[:, 0], sums[:, 1], sums[:, 2], sums[:, 3]
+        nan = np.full(len(count), np.nan)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            nf = count.astype(np.float64)
+            out = {"d_max": 1.0 / np.sqrt(edges[:-1]), "d_min": 1.0 / np.sqrt(edges[1:]), "n": count,
+                   "power": np.where(count > 0, saa / nf, np.nan)}
+            if other is None:
+                out.update({"powerOther": nan, "fsc": nan.copy(), "phaseCosine": nan.copy(), "scale": nan.copy()})
+            else:
+                den = np.sqrt(saa * sbb)
+                mod = np.sqrt(re * re + im * im)
+                out.update({"powerOther": np.where(count > 0, sbb / nf, np.nan), "fsc": np.where(den > 0, re / den, np.nan),
+                            "phaseCosine": np.where(mod > 0, re / mod, np.nan), "scale": np.where(sbb > 0, re / sbb, np.nan)})
+        out["sums"] = sums
+        return out
 
 
 class DensityMatrix(object):
@@ -703,6 +888,70 @@ class DensityMatrix(object):
         finds each copy."""
         ops = [identityOperator()] + [_operator(m) for m in rotationMats]
         return self.resampled(cellHeader(self.header) if header is None else header, np.array(ops).reshape(-1, 12), order=order)
+
+    # -- reciprocal space (no reference counterpart) ---------------------------------------------------------------
+    def fourier(self):
+        """The 3-D Fourier transform of this map as a device-resident DensitySpectrum (``pdbeda_map_fft`` in include/pdbeda.h has the
+        contract): numpy's ``rfftn`` of the stored box, which is the period.  Every axis must be a plannable length (``isFourierSize``):
+        transform a whole cell (``symmetryExpanded``, on ``fourierHeader`` where the sampling is not plannable) or a ``fourierBox``."""
+        return DensitySpectrum(self, self._map.fft())
+
+    def fourierFiltered(self, table, s2Max, beyond=0.0):
+        """This map with every Fourier coefficient multiplied by the radial table g(s^2) (``DensitySpectrum.scaled``), as a device-made
+        DensityMatrix: transform, scale, inverse transform, nothing leaves the device."""
+        spec = self.fourier()
+        spec.scale(table, s2Max, beyond)
+        return spec.toMap()
+
+    def resolutionCut(self, dMin, dMax=None, softness=0.1):
+        """This map cut at ``dMin`` Angstrom (and, with ``dMax``, without the terms below 1 / dMax): ``resolutionTable``'s raised-cosine window."""
+        table = resolutionTable(dMin, dMax, softness)
+        s2max = ((1.0 + 0.5 * float(softness)) / float(dMin)) ** 2 * (1.0 + 2.0 ** -20)
+        return self.fourierFiltered(table, s2max, 0.0)
+
+    def sharpened(self, B):
+        """This map with every coefficient multiplied by exp(-B s^2 / 4): B < 0 sharpens, B > 0 blurs (an isotropic B-factor)."""
+        s2max = maxS2(self.header)
+        return self.fourierFiltered(bFactorTable(B, s2max), s2max, 0.0)
+
+    def shellStats(self, other=None, nShells=20, dMin=None, dMax=None):
+        """``DensitySpectrum.shells`` of this map's transform (against ``other``'s, a DensityMatrix of the same shape)."""
+        return self.fourier().shells(None if other is None else other.fourier(), edges=shellEdges(self.header, nShells, dMin, dMax))
+
+    def fsc(self, other, nShells=20, dMin=None, dMax=None):
+        """The Fourier shell correlation of this map with ``other``: a dict ``d_max``, ``d_min``, ``n``, ``fsc`` per resolution shell."""
+        table = self.shellStats(other, nShells, dMin, dMax)
+        return dict((key, table[key]) for key in ("d_max", "d_min", "n", "fsc"))
+
+    def structureFactors(self, hkl):
+        """Structure factors of a WHOLE-CELL map at the Miller indices ``hkl`` ((n, 3), on the cell axes a*, b*, c*) in the crystallographic
+        convention F(h) = V / N sum rho(x) exp(+2 pi i h.x), x the fractional coordinate of a voxel, crsStart included: complex128 (n,).
+        Any integer index is taken modulo the sampling.  ValueError for a map that does not store exactly one cell."""
+        h = self.header
+        if [int(v) for v in h.ncrs] != [int(v) for v in h.crsInterval]:
+            raise ValueError("structureFactors takes a map of the whole unit cell (symmetryExpanded on cellHeader / fourierHeader)")
+        hkl = np.asarray(hkl, dtype=np.int64).reshape(-1, 3)
+        idx = np.stack([hkl[:, h.map2crs[k]] for k in range(3)], axis=1)
+        if len(idx) and np.abs(idx).max() >= 2 ** 31:
+            raise ValueError("structureFactors: an index beyond int32")
+        raw = self.fourier().at(idx)
+        turn = sum(idx[:, k] * int(h.crsStart[k]) / float(h.crsInterval[k]) for k in range(3)) if len(idx) else np.zeros(0)
+        volume = float(h.unitVolume) * float(h.xyzInterval[0]) * float(h.xyzInterval[1]) * float(h.xyzInterval[2])
+        return (volume / float(h.ncrs[0] * h.ncrs[1] * h.ncrs[2])) * np.conj(raw) * np.exp(2j * np.pi * np.asarray(turn, dtype=np.float64))
+
+    def fourierBox(self, margin=0.0):
+        """This map (a cut-out) embedded in zeros on a plannable box, as a device-made DensityMatrix: the same cell and sampling, ``margin``
+        Angstrom (in grid steps of each axis, rounded up) added on every side and every axis then grown at its high end to the next
+        plannable length; ``resampled`` at order 0 with the identity operator and fill 0.  Where the grown box leaves the cell it reads the
+        cell's periodic copies, as every call does."""
+        h = self.header
+        pad = [int(math.ceil(float(margin) / h.gridLength[h.map2crs[k]] - 1e-9)) for k in range(3)]
+        if min(pad) < 0:
+            raise ValueError("fourierBox: margin >= 0")
+        ncrs = [fourierSize(int(h.ncrs[k]) + 2 * pad[k]) for k in range(3)]
+        start = [int(h.crsStart[k]) - pad[k] for k in range(3)]
+        box = _headerFromFields(ncrs, start, h.xyzInterval, h.xyzLength, (h.alpha, h.beta, h.gamma), (h.col2xyz, h.row2xyz, h.sec2xyz), h.spaceGroup)
+        return self.resampled(box, order=0, fill=0.0)
 
     # -- whole-map blobs ------------------------------------------------------------
     def createFullBlobList(self, cutoff):

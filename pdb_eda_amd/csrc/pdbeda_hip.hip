@@ -35,6 +35,7 @@
 #include "pdbeda_blobshape.h"
 #include "pdbeda_contacts.h"
 #include "pdbeda_filter.h"
+#include "pdbeda_fourier.h"
 #include "pdbeda_model.h"
 #include "pdbeda_partition.h"
 #include "pdbeda_peaks.h"
@@ -110,6 +111,7 @@ struct pdbeda_ctx {
     // by that context's thread, which trims its siblings' pools before it gives up
     std::mutex pool_mu;
     std::map<char *, size_t> lent;      // arenas handed out and not yet returned (maps, jobs): an abandoned context frees them too
+    std::map<int, Arena> fft_tables;    // the twiddle table of every line length this context has transformed (pdbeda_fourier_line.h): made once, kept until destroy
 };
 
 // Contexts of this process: live ones (a context short of memory trims the arena pools of its siblings) and the ones the
@@ -121,6 +123,7 @@ static std::mutex g_ctx_mu;
 static std::vector<pdbeda_ctx *> g_live, g_abandoned;
 
 static void ctx_release_device(pdbeda_ctx *ctx, bool lent_too) {
+    ctx->fft_tables.clear();      // (back to the pool, which goes next)
     for (auto &kv : ctx->pool) (void)hipFree(kv.second.base);
     ctx->pool.clear();
     ctx->pool_bytes = 0;
@@ -647,6 +650,7 @@ extern "C" int pdbeda_ctx_destroy(pdbeda_ctx *ctx) {
         return PDBEDA_OK;
     }
     (void)ctx_sync(ctx);
+    ctx->fft_tables.clear();      // (the context's own arenas are not a caller's lost handle)
     const bool lost = ctx->live_handles == 0 && !ctx->lent.empty();   // (no handle is alive and an arena is still out: the library itself lost it)
     ctx_release_device(ctx, false);   // (arenas still lent belong to live handles of the caller)
     delete ctx;
@@ -3898,6 +3902,252 @@ extern "C" int pdbeda_map_resample(pdbeda_map *src, const pdbeda_geometry *dst_g
         }
     made.publish(out);
     if (cov.m) cov.publish(coverage);
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Reciprocal space: the transform of a resident map and the calls on a resident spectrum (no reference counterpart; the contracts: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+struct pdbeda_spectrum {
+    pdbeda_ctx *ctx = nullptr;
+    Arena arena;                      // the half spectrum: goes back to the context's pool with the handle
+    FftCplx *data = nullptr;
+    int32_t ncrs[3] = {0, 0, 0};      // of the map it was made from
+    int32_t nh = 0;
+    int64_t n_coef = 0;
+};
+
+// The plan and the device's twiddle table of one line length; the table is made on first use (one upload, one wait) and cached in the context.
+static int fft_line_setup(pdbeda_ctx *ctx, int n, FftPlan *plan, const FftCplx **table) {
+    if (!pdbeda_fft_plan(n, plan)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "fft: a line of %d is not plannable", n);
+    auto it = ctx->fft_tables.find(n);
+    if (it == ctx->fft_tables.end()) {
+        std::vector<FftCplx> host((size_t)n);
+        pdbeda_fft_twiddles(n, host.data());
+        Arena a;
+        FftCplx *dev = nullptr;
+        if (int rc = arena_carve(ctx, "fft table", &a, [&](Carver &cv) { cv.take(dev, (size_t)n); })) return rc;
+        hipError_t e = h2d_one(ctx, dev, host.data(), sizeof(FftCplx) * (size_t)n);
+        const hipError_t e2 = ctx_sync(ctx);      // (the host's table may be read until here)
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "fft table: %s", hipGetErrorString(e));
+        it = ctx->fft_tables.emplace(n, std::move(a)).first;
+    }
+    *table = reinterpret_cast<const FftCplx *>(it->second.base);
+    return 0;
+}
+
+// The kernels are instantiated per class of line length (their LDS is static): the smallest class that holds n.
+#define FFT_BY_LENGTH(n, LAUNCH)                                                                                         \
+    do {                                                                                                                 \
+        if ((n) <= 64) { LAUNCH(64); } else if ((n) <= 128) { LAUNCH(128); } else if ((n) <= 256) { LAUNCH(256); }       \
+        else if ((n) <= 512) { LAUNCH(512); } else { LAUNCH(1024); }                                                     \
+    } while (0)
+
+struct FftAxes {
+    FftPlan plan[3];
+    const FftCplx *table[3];
+};
+
+static void fft_rows_launch(pdbeda_ctx *ctx, const float *in, int64_t rows, const FftAxes &ax, FftCplx *out) {
+    PROF(ctx, "k_fft_rows");
+    const dim3 grid((unsigned)((rows + FFT_ROWS - 1) / FFT_ROWS));
+#define LAUNCH(NMAX) hipLaunchKernelGGL(k_fft_rows<NMAX>, grid, dim3(256), 0, ctx->stream, in, rows, ax.plan[0], ax.table[0], out)
+    FFT_BY_LENGTH(ax.plan[0].n, LAUNCH);
+#undef LAUNCH
+}
+static void ifft_rows_launch(pdbeda_ctx *ctx, const FftCplx *in, int64_t rows, const FftAxes &ax, double n_total, float *out) {
+    PROF(ctx, "k_ifft_rows");
+    const dim3 grid((unsigned)((rows + FFT_ROWS - 1) / FFT_ROWS));
+#define LAUNCH(NMAX) hipLaunchKernelGGL(k_ifft_rows<NMAX>, grid, dim3(256), 0, ctx->stream, in, rows, ax.plan[0], ax.table[0], n_total, out)
+    FFT_BY_LENGTH(ax.plan[0].n, LAUNCH);
+#undef LAUNCH
+}
+// A pass along r (axis 1) or s (axis 2) of a [ns][nr][nh] volume; in == out runs in place.
+static void fft_cols_launch(pdbeda_ctx *ctx, const FftCplx *in, int nh, int nr, int ns, int axis, const FftAxes &ax, int inverse, FftCplx *out) {
+    PROF(ctx, axis == 1 ? "k_fft_cols_r" : "k_fft_cols_s");
+    const int col_tiles = (nh + FFT_COLS - 1) / FFT_COLS, n_other = axis == 1 ? ns : nr;
+    const int64_t stride = axis == 1 ? (int64_t)nh : (int64_t)nh * nr, other_stride = axis == 1 ? (int64_t)nh * nr : (int64_t)nh;
+    const dim3 grid((unsigned)((int64_t)col_tiles * n_other));
+#define LAUNCH(NMAX) hipLaunchKernelGGL(k_fft_cols<NMAX>, grid, dim3(256), 0, ctx->stream, in, nh, col_tiles, stride, other_stride, ax.plan[axis], ax.table[axis], inverse, out)
+    FFT_BY_LENGTH(ax.plan[axis].n, LAUNCH);
+#undef LAUNCH
+}
+
+// The launch graph: the three tables (made on first use); k_fft_rows from the map into the new spectrum; k_fft_cols along r, then along s, in place.  One wait.
+extern "C" int pdbeda_map_fft(pdbeda_map *map, pdbeda_spectrum **out) {
+    if (!map || !out) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = map->ctx;
+    static const char axis_name[3] = {'c', 'r', 's'};
+    const Geom &g = map->geom;
+    for (int k = 0; k < 3; ++k)
+        if (!pdbeda_fft_plannable(g.ncrs[k])) {
+            const int next = pdbeda_fft_next(g.ncrs[k]);
+            if (next) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map fft: axis %c has %d indices, which is not 2^a 3^b 5^c 7^d; the next plannable length is %d", axis_name[k], g.ncrs[k], next);
+            return fail(ctx, PDBEDA_ERR_ARGUMENT, "map fft: axis %c has %d indices, above the longest plannable line of %d; there is no next plannable length", axis_name[k], g.ncrs[k], PDBEDA_FFT_MAX_AXIS);
+        }
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2], nh = nc / 2 + 1;
+    FftAxes ax;
+    for (int k = 0; k < 3; ++k)
+        if (int rc = fft_line_setup(ctx, g.ncrs[k], &ax.plan[k], &ax.table[k])) return rc;
+    std::unique_ptr<pdbeda_spectrum> sp(new pdbeda_spectrum());
+    sp->ctx = ctx;
+    sp->ncrs[0] = nc; sp->ncrs[1] = nr; sp->ncrs[2] = ns;
+    sp->nh = nh;
+    sp->n_coef = (int64_t)nh * nr * ns;
+    if (int rc = arena_carve(ctx, "map fft", &sp->arena, [&](Carver &cv) { cv.take(sp->data, (size_t)sp->n_coef); })) return rc;
+    fft_rows_launch(ctx, map->dens, (int64_t)nr * ns, ax, sp->data);
+    fft_cols_launch(ctx, sp->data, nh, nr, ns, 1, ax, 0, sp->data);
+    fft_cols_launch(ctx, sp->data, nh, nr, ns, 2, ax, 0, sp->data);
+    hipError_t e = hipGetLastError();
+    const hipError_t e2 = ctx_sync(ctx);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "map fft: %s", hipGetErrorString(e));
+    ctx->live_handles++;
+    *out = sp.release();
+    return PDBEDA_OK;
+}
+
+// The launch graph: k_fft_cols along s from the spectrum into the spare volume; along r in place there; k_ifft_rows into the new map.  One wait.
+extern "C" int pdbeda_spectrum_inverse(pdbeda_spectrum *spec, pdbeda_map *like, pdbeda_map **out) {
+    if (!spec || !like || !out) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = spec->ctx;
+    if (like->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum inverse: the map belongs to another context");
+    if (memcmp(like->geom.ncrs, spec->ncrs, sizeof spec->ncrs) != 0)
+        return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum inverse: the map is %d x %d x %d, the spectrum was made from %d x %d x %d", like->geom.ncrs[0], like->geom.ncrs[1], like->geom.ncrs[2],
+                    spec->ncrs[0], spec->ncrs[1], spec->ncrs[2]);
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int nc = spec->ncrs[0], nr = spec->ncrs[1], ns = spec->ncrs[2], nh = spec->nh;
+    FftAxes ax;
+    for (int k = 0; k < 3; ++k)
+        if (int rc = fft_line_setup(ctx, spec->ncrs[k], &ax.plan[k], &ax.table[k])) return rc;
+    MadeMap made;
+    if (int rc = made.make_like("spectrum inverse", like)) return rc;
+    FftCplx *d_vol = nullptr;
+    const int rc = with_scratch(ctx, "spectrum inverse", [&](Carver &cv) { cv.take(d_vol, (size_t)spec->n_coef); }, [&]() -> int {
+        HIP_TRY(ctx, made.geometry_up());
+        fft_cols_launch(ctx, spec->data, nh, nr, ns, 2, ax, 1, d_vol);
+        fft_cols_launch(ctx, d_vol, nh, nr, ns, 1, ax, 1, d_vol);
+        ifft_rows_launch(ctx, d_vol, (int64_t)nr * ns, ax, (double)((int64_t)nc * nr * ns), made.dens);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    });
+    if (rc) return rc;
+    made.publish(out);
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_spectrum_shape(pdbeda_spectrum *spec, int32_t ncrs[3]) {
+    if (!spec || !ncrs) return PDBEDA_ERR_ARGUMENT;
+    memcpy(ncrs, spec->ncrs, sizeof spec->ncrs);
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_spectrum_download(pdbeda_spectrum *spec, double *out) {
+    if (!spec || !out) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = spec->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, d2h(ctx, out, spec->data, sizeof(FftCplx) * (size_t)spec->n_coef));
+    HIP_TRY(ctx, ctx_sync(ctx));
+    return PDBEDA_OK;
+}
+
+extern "C" int pdbeda_spectrum_free(pdbeda_spectrum *spec) {
+    if (!spec) return PDBEDA_ERR_ARGUMENT;
+    spec->ctx->live_handles--;      // (the arena goes back to the pool in stream order, as a map's)
+    delete spec;
+    return PDBEDA_OK;
+}
+
+static SpectrumShape spectrum_shape_of(const pdbeda_spectrum *spec, const double metric[6]) {
+    SpectrumShape sh;
+    sh.nc = spec->ncrs[0]; sh.nr = spec->ncrs[1]; sh.ns = spec->ncrs[2]; sh.nh = spec->nh;
+    sh.n_coef = spec->n_coef;
+    for (int k = 0; k < 6; ++k) sh.m[k] = metric ? metric[k] : 0.0;
+    return sh;
+}
+
+extern "C" int pdbeda_spectrum_values(pdbeda_spectrum *spec, const int32_t *idx, int64_t n, double *out) {
+    if (!spec || n < 0 || (n > 0 && (!idx || !out))) return PDBEDA_ERR_ARGUMENT;
+    if (n == 0) return PDBEDA_OK;
+    pdbeda_ctx *ctx = spec->ctx;
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Input<int32_t> in{idx, (size_t)(3 * n)};
+    Result<double> res{out, (size_t)(2 * n)};
+    const SpectrumShape sh = spectrum_shape_of(spec, nullptr);
+    return with_scratch(ctx, "spectrum values", [&](Carver &cv) { in.carve(cv); res.carve(cv); }, [&]() -> int {
+        HIP_TRY(ctx, in.send(ctx));
+        hipLaunchKernelGGL(k_spectrum_values, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, spec->data, sh, in.at, n, res.at(ctx));
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, res.finish(ctx));
+        return 0;
+    });
+}
+
+extern "C" int pdbeda_spectrum_scale(pdbeda_spectrum *spec, const double metric[6], const double *table, int32_t n_table, double s2_max, double beyond) {
+    if (!spec) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = spec->ctx;
+    if (!metric || !table) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum scale: no metric or no table");
+    if (n_table < 2 || n_table > PDBEDA_SPECTRUM_MAX_TABLE) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum scale: a table of %d entries is outside 2 .. %d", n_table, PDBEDA_SPECTRUM_MAX_TABLE);
+    if (!all_finite(metric, 6)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum scale: a non-finite metric entry");
+    if (!all_finite(table, n_table)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum scale: a non-finite table entry");
+    if (!std::isfinite(beyond)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum scale: `beyond` is not finite");
+    if (!(std::isfinite(s2_max) && s2_max > 0.0)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum scale: s2_max is not a finite number above 0");
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SpectrumShape sh = spectrum_shape_of(spec, metric);
+    const double t_scale = (double)(n_table - 1) / s2_max;
+    double *d_table = nullptr;
+    return with_scratch(ctx, "spectrum scale", [&](Carver &cv) { cv.take(d_table, (size_t)n_table); }, [&]() -> int {
+        HIP_TRY(ctx, h2d_one(ctx, d_table, table, 8 * (size_t)n_table));
+        { PROF(ctx, "k_spectrum_scale"); hipLaunchKernelGGL(k_spectrum_scale, dim3(grid_for(sh.n_coef, 256, 4096)), dim3(256), 0, ctx->stream, spec->data, sh, d_table, n_table, t_scale, beyond); }
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    });
+}
+
+// The launch graph: the edges in scratch; k_spectrum_shells over a number of workgroups fixed by the shape; k_spectrum_shells_fold; the rows.  One wait.
+extern "C" int pdbeda_spectrum_shells(pdbeda_spectrum *a, pdbeda_spectrum *b, const double metric[6], const double *edges, int32_t n_shells, int64_t *count, double *sums) {
+    if (!a) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = a->ctx;
+    if (!metric || !edges) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum shells: no metric or no edges");
+    if (n_shells < 1 || n_shells > PDBEDA_SPECTRUM_MAX_SHELLS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum shells: %d shells are outside 1 .. %d", n_shells, PDBEDA_SPECTRUM_MAX_SHELLS);
+    if (!all_finite(metric, 6)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum shells: a non-finite metric entry");
+    if (!all_finite(edges, (int64_t)n_shells + 1)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum shells: a non-finite edge");
+    for (int k = 0; k < n_shells; ++k)
+        if (!(edges[k] < edges[k + 1])) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum shells: edge %d does not lie above edge %d", k + 1, k);
+    if (b) {
+        if (b->ctx != ctx) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum shells: spectra of different contexts");
+        if (memcmp(a->ncrs, b->ncrs, sizeof a->ncrs) != 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "spectrum shells: spectra of different shapes");
+    }
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const SpectrumShape sh = spectrum_shape_of(a, metric);
+    const int64_t rounds = (sh.n_coef + 255) / 256;
+    const unsigned blocks = (unsigned)std::min<int64_t>(rounds, FFT_SHELL_BLOCKS);
+    const int64_t chunk = (rounds + blocks - 1) / blocks * 256;
+    int parts = 1;      // lanes that share a shell's scan of the 256 staged coefficients
+    while (2 * parts * n_shells <= 256) parts *= 2;
+    std::vector<double> rows(5 * (size_t)n_shells, 0.0);
+    double *d_edges = nullptr, *d_part = nullptr, *d_res = nullptr;
+    const int rc = with_scratch(ctx, "spectrum shells", [&](Carver &cv) { cv.take(d_edges, (size_t)n_shells + 1); cv.take(d_part, 5 * (size_t)n_shells * blocks); cv.take(d_res, 5 * (size_t)n_shells); },
+                                [&]() -> int {
+        HIP_TRY(ctx, h2d_one(ctx, d_edges, edges, 8 * ((size_t)n_shells + 1)));
+        { PROF(ctx, "k_spectrum_shells"); hipLaunchKernelGGL(k_spectrum_shells, dim3(blocks), dim3(256), 0, ctx->stream, a->data, b ? b->data : (const FftCplx *)nullptr, sh, d_edges, n_shells, parts, chunk, d_part); }
+        { PROF(ctx, "k_spectrum_shells_fold"); hipLaunchKernelGGL(k_spectrum_shells_fold, dim3((unsigned)n_shells), dim3(256), 0, ctx->stream, d_part, (int)blocks, n_shells, d_res); }
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, d2h(ctx, rows.data(), d_res, 40 * (size_t)n_shells));
+        return 0;
+    });
+    if (rc) return rc;
+    for (int j = 0; j < n_shells; ++j) {
+        if (count) count[j] = (int64_t)rows[5 * (size_t)j];
+        if (sums) memcpy(sums + 4 * (size_t)j, rows.data() + 5 * (size_t)j + 1, 32);
+    }
     return PDBEDA_OK;
 }
 

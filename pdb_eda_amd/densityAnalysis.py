@@ -1783,3 +1783,103 @@ class DensityAnalysis(object):
         if "expandedDiff" not in self._local:
             self._local["expandedDiff"] = self._expanded(self.diffDensityObj, 1)
         return self._local["expandedDiff"]
+
+    # ---- reciprocal space: the 2Fo-Fc map of the whole cell against the model, shell by shell (no reference counterpart) ----
+    def _cellAtoms(self, header):
+        """(xyz, amp, expo, radii) of every atom copy whose cut-off sphere reaches the unit cell of ``header``: the model's atoms (those
+        ``_modelAtoms`` keeps, taken from the asymmetric unit) under the identity and the distinct operators of the header's
+        ``rotationMats``, each brought into the cell by whole lattice translations, and its 26 neighbours where the sphere crosses a face."""
+        _requireParams()
+        cols = _structure.columns(self.biopdbObj)
+        names = cols.pair_names
+        electrons = _pairTables(names, max(len(names), 1))["electrons"][cols.pair_of_atom] if len(cols.coord) else np.zeros(0)
+        keep = ~np.isnan(electrons) & (cols.occupancy != 0) if len(cols.coord) else np.zeros(0, dtype=bool)
+        amp, expo, bEff = ccp4.gaussianAtomTerms(electrons[keep], cols.bfactor[keep], cols.occupancy[keep], blur=modelBlur)
+        radii = ccp4.modelRadii(bEff, modelSigmas)
+        xyz = np.asarray(cols.coord, dtype=np.float64).reshape(-1, 3)[keep]
+        ops, seen = [], set()
+        for op in [ccp4.identityOperator()] + [ccp4._operator(m) for m in self.pdbObj.header.rotationMats]:
+            key = tuple(np.round(op.reshape(-1), 5).tolist())
+            if key not in seen:
+                seen.add(key)
+                ops.append(op)
+        ortho, deortho = np.asarray(header.orthoMat, dtype=np.float64), np.asarray(header.deOrthoMat, dtype=np.float64)
+        pad = float(radii.max()) * np.sqrt((deortho ** 2).sum(axis=1)) if len(radii) else np.zeros(3)      # the sphere's reach in fractional units
+        shifts = np.array([(i, j, k) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1)], dtype=np.float64)
+        out_xyz, out_row = [], []
+        for op in ops:
+            frac = ccp4.applyOperator(op, xyz).dot(deortho.T)
+            frac -= np.floor(frac)
+            for shift in shifts:
+                f = frac + shift
+                inside = ((f >= -pad) & (f <= 1.0 + pad)).all(axis=1)
+                out_xyz.append(f[inside].dot(ortho.T))
+                out_row.append(np.nonzero(inside)[0])
+        rows = np.concatenate(out_row) if out_row else np.zeros(0, dtype=np.int64)
+        return (np.concatenate(out_xyz) if out_xyz else np.zeros((0, 3))), amp[rows], expo[rows], radii[rows]
+
+    def _fourierMaps(self):
+        """(observed, model): the 2Fo-Fc map over the whole unit cell -- ``expandedDensityObj`` where the cell's sampling can be transformed,
+        else the tricubic expansion onto ``ccp4.fourierHeader`` -- and the calculated density of every atom copy of the cell on that grid.
+        Both stay in HBM."""
+        if "fourier" not in self._local:
+            header = self.densityObj.header
+            if all(ccp4.isFourierSize(n) for n in header.crsInterval):
+                observed = self.expandedDensityObj
+            else:
+                observed = self.densityObj.symmetryExpanded([np.asarray(m, dtype=np.float64) for m in self.pdbObj.header.rotationMats], header=ccp4.fourierHeader(header), order=3)
+            xyz, amp, expo, radii = self._cellAtoms(observed.header)
+            self._local["fourier"] = (observed, observed.modelDensity(xyz, amp, expo, radii))
+        return self._local["fourier"]
+
+    def modelShellTable(self, nShells=20):
+        """The 2Fo-Fc map against the model per resolution shell (``DensitySpectrum.shells`` of the two whole-cell maps of ``_fourierMaps``,
+        ``nShells`` shells of equal reciprocal volume up to the grid's Nyquist limit): a dict of arrays ``d_max``, ``d_min``, ``n``,
+        ``power``, ``powerOther`` (the model's), ``fsc``, ``phaseCosine`` and ``scale`` (2Fo-Fc ~ scale * model)."""
+        key = ("shells", int(nShells))
+        if key not in self._local:
+            observed, model = self._fourierMaps()
+            self._local[key] = observed.shellStats(model, nShells)
+        return self._local[key]
+
+    def fscResolution(self, threshold=0.5, nShells=20):
+        """The resolution in Angstrom at which the map-model Fourier shell correlation first falls through ``threshold``: the first pair of
+        consecutive shells with fsc[j] >= threshold > fsc[j + 1], linearly interpolated in s between the shells' mid points (s = 1 / d).
+        None if the curve never crosses."""
+        table = self.modelShellTable(nShells)
+        s = 0.5 * (1.0 / table["d_max"] + 1.0 / table["d_min"])
+        fsc = table["fsc"]
+        for j in range(len(fsc) - 1):
+            a, b = fsc[j], fsc[j + 1]
+            if np.isfinite(a) and np.isfinite(b) and a >= threshold > b:
+                return 1.0 / float(s[j] + (a - threshold) / (a - b) * (s[j + 1] - s[j]))
+        return None
+
+    def resolutionCutDensityObj(self, d, dMax=None, softness=0.1):
+        """The whole-cell 2Fo-Fc map cut at ``d`` Angstrom (``DensityMatrix.resolutionCut``), as a device-made DensityMatrix that the blob and
+        peak searches take as it is."""
+        return self._fourierMaps()[0].resolutionCut(d, dMax, softness)
+
+    def sharpenedDensityObj(self, B):
+        """The whole-cell 2Fo-Fc map with the B-factor ``B`` applied in reciprocal space (negative sharpens)."""
+        return self._fourierMaps()[0].sharpened(B)
+
+    def fourierSummary(self, nShells=20):
+        """The grid that was transformed (``grid_c`` / ``grid_r`` / ``grid_s``), its Nyquist limit ``d_min``, the resolutions at which the map-model
+        FSC falls through 0.5 and 0.143 (None: it does not), the FSC and the scale over all shells together, and the number of shells."""
+        table = self.modelShellTable(nShells)
+        sums = table["sums"].sum(axis=0)
+        den = float(np.sqrt(sums[0] * sums[1]))
+        ncrs = self._fourierMaps()[0].header.ncrs
+        return {"grid_c": int(ncrs[0]), "grid_r": int(ncrs[1]), "grid_s": int(ncrs[2]), "d_min": float(table["d_min"][-1]), "num_shells": int(nShells),
+                "fsc_05_resolution": self.fscResolution(0.5, nShells), "fsc_0143_resolution": self.fscResolution(0.143, nShells),
+                "overall_fsc": float(sums[2]) / den if den > 0 else None, "overall_scale": float(sums[2] / sums[1]) if sums[1] > 0 else None}
+
+    fourierShellHeader = ["shell", "d_max", "d_min", "n", "power", "power_model", "fsc", "phase_cosine", "scale"]
+
+    def calculateFourierShells(self, nShells=20):
+        """One row per resolution shell (``fourierShellHeader``) of ``modelShellTable``; None where a value is undefined."""
+        t = self.modelShellTable(nShells)
+        clean = lambda v: [None if x != x else float(x) for x in np.asarray(v, dtype=np.float64).tolist()]
+        return self._rows(list(range(len(t["n"]))), clean(t["d_max"]), clean(t["d_min"]), [int(v) for v in t["n"]], clean(t["power"]), clean(t["powerOther"]), clean(t["fsc"]),
+                          clean(t["phaseCosine"]), clean(t["scale"]))
