@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "pdbeda_kernels.h"
+#include "pdbeda_cloud.h"
 #include "pdbeda_stage.h"
 #include "pdbeda_tile.h"
 #include "pdbeda_upload.h"
@@ -4154,75 +4155,14 @@ extern "C" int pdbeda_spectrum_shells(pdbeda_spectrum *a, pdbeda_spectrum *b, co
 // ------------------------------------------------------------------------------------
 // aggregateCloud (densityAnalysis.py:571-731) behind one call
 // ------------------------------------------------------------------------------------
-struct pdbeda_cloud {
+struct pdbeda_cloud : CloudTables {      // (the tables: pdbeda_cloud.h)
     pdbeda_ctx *ctx = nullptr;
-    std::vector<int32_t> atom_idx;
-    std::vector<double> atom_total, atom_centroid, atom_dist;
-    std::vector<int64_t> atom_nvox;
-    struct Row { int32_t residue; double total; int64_t n; double electrons; double cen[3]; };
-    std::vector<Row> res_rows, dom_rows;
-    std::vector<uint8_t> owner_state;
-    double totals[4] = {0.0, 0.0, 0.0, 0.0};
 };
 // A blob list that pdbeda_aggregate_cloud makes for itself: freed when the call returns, however it returns
 struct ScopedList {
     pdbeda_bloblist *bl = nullptr;
     ~ScopedList() { if (bl) pdbeda_bloblist_free(bl); }
 };
-
-// numpy's add.reduce over a contiguous float64 array (see k_np_chunk_sums): blocks of 8192 accumulated in order, each a
-// pairwise sum.  mode 1: (x - shift)^2.  The centroid-distance cut-off (densityAnalysis.py:607) decides which atoms are
-// pooled, so np.nanmedian + 2.5 * np.nanstd is reproduced operation by operation, not approximated.
-static double np_elem_h(const double *a, int64_t i, int mode, double shift) {
-    double v = a[i];
-    if (mode == 1) { v = v - shift; v = v * v; }
-    return v;
-}
-static double np_pairwise_h(const double *a, int64_t off, int64_t n, int mode, double shift) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int64_t i = 0; i < n; ++i) res += np_elem_h(a, off + i, mode, shift);
-        return res;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int j = 0; j < 8; ++j) r[j] = np_elem_h(a, off + j, mode, shift);
-        int64_t i;
-        for (i = 8; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] += np_elem_h(a, off + i + j, mode, shift);
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += np_elem_h(a, off + i, mode, shift);
-        return res;
-    }
-    int64_t n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_h(a, off, n2, mode, shift) + np_pairwise_h(a, off + n2, n - n2, mode, shift);
-}
-static double np_sum_h(const double *a, int64_t n, int mode, double shift) {
-    double out = 0.0;
-    for (int64_t off = 0; off < n; off += 8192) out += np_pairwise_h(a, off, std::min<int64_t>(8192, n - off), mode, shift);
-    return out;
-}
-static double np_median_h(std::vector<double> v) {   // np.median of a NaN-free 1-D array (the middle order statistics: a selection, not a sort)
-    const size_t n = v.size();
-    if (n == 0) return NAN;
-    std::nth_element(v.begin(), v.begin() + n / 2, v.end());
-    const double hi = v[n / 2];
-    if (n & 1) return hi;
-    const double lo = *std::max_element(v.begin(), v.begin() + n / 2);   // (the largest of what was put below the middle)
-    return (lo + hi) / 2.0;
-}
-static double np_std_h(const std::vector<double> &v) {   // np.std (population) of a NaN-free 1-D array
-    const int64_t n = (int64_t)v.size();
-    if (n == 0) return NAN;
-    const double mean = np_sum_h(v.data(), n, 0, 0.0) / (double)n;
-    return std::sqrt(np_sum_h(v.data(), n, 1, mean) / (double)n);
-}
-
-static inline double norm3(const double *a, const double *b) {   // np.linalg.norm(a - b): sqrt((dx^2 + dy^2) + dz^2)
-    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    return std::sqrt((dx * dx + dy * dy) + dz * dz);
-}
 
 extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *at, float density_cutoff, double min_cloud_electrons,
                                       pdbeda_cloud **out) {
@@ -4274,84 +4214,19 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
     if (rc) return rc;
 
     t_marks[0] = now_s();
-    // ---- 2. host: centroid-distance cut-off, best cloud, pool (604-642) ----
-    std::vector<int64_t> first((size_t)n + 1, 0);       // clouds of atom a: [first[a], first[a + 1])  (sorted by group)
-    for (int64_t c = 0; c < nb; ++c) first[(size_t)c_grp[(size_t)c] + 1]++;
-    for (int64_t a = 0; a < n; ++a) first[(size_t)a + 1] += first[(size_t)a];
-    std::vector<double> c_dist((size_t)nb), min_dist((size_t)n, NAN);
-    std::vector<double> centroidDistances;
-    centroidDistances.reserve((size_t)n);
-    for (int64_t a = 0; a < n; ++a) {
-        double mn = NAN;
-        for (int64_t c = first[(size_t)a]; c < first[(size_t)a + 1]; ++c) {
-            c_dist[(size_t)c] = norm3(at->xyz + 3 * a, c_cen.data() + 3 * c);
-            if (c == first[(size_t)a] || c_dist[(size_t)c] < mn) mn = c_dist[(size_t)c];
-        }
-        min_dist[(size_t)a] = mn;
-        if (first[(size_t)a + 1] > first[(size_t)a]) centroidDistances.push_back(mn);
-    }
-    const double cutoff = np_median_h(centroidDistances) + 2.5 * np_std_h(centroidDistances);
-    res->totals[3] = cutoff;
-    t_marks[1] = now_s();
-    std::vector<int32_t> pool_cloud, pool_atom;
-    pool_cloud.reserve((size_t)nb); pool_atom.reserve((size_t)nb);
-    res->atom_idx.reserve((size_t)n); res->atom_total.reserve((size_t)n); res->atom_nvox.reserve((size_t)n);
-    res->atom_centroid.reserve(3 * (size_t)n); res->atom_dist.reserve((size_t)n);
-    std::vector<int32_t> pooled_of_key((size_t)at->n_keys, -1);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t s = at->alias[i], lo = first[(size_t)s], hi = first[(size_t)s + 1];
-        if (hi == lo) continue;
-        int64_t best = lo;
-        if (hi - lo > 1) {
-            if (min_dist[(size_t)s] > cutoff) continue;
-            for (int64_t c = lo + 1; c < hi; ++c)
-                if (c_dist[(size_t)c] < c_dist[(size_t)best]) best = c;      // the first minimum (distances.index(min))
-        }
-        for (int64_t c = lo; c < hi; ++c) { pool_cloud.push_back((int32_t)c); pool_atom.push_back((int32_t)i); }
-        pooled_of_key[(size_t)at->key[i]] = (int32_t)i;                      // the last atom of a name wins (640)
-        res->atom_idx.push_back((int32_t)i);
-        res->atom_total.push_back(c_tot[(size_t)best]);
-        res->atom_nvox.push_back(c_n[(size_t)best]);
-        for (int k = 0; k < 3; ++k) res->atom_centroid.push_back(c_cen[3 * (size_t)best + k]);
-        res->atom_dist.push_back(norm3(at->xyz + 3 * i, c_cen.data() + 3 * best));
-    }
-    const int64_t n_pool = (int64_t)pool_cloud.size();
+    // ---- 2. host: centroid-distance cut-off, best cloud, pool (604-642), and the residue groups, voxel offsets and bonded pairs of the pool (pdbeda_cloud.h) ----
+    CloudPool pool;
+    if (cloud_pool(*at, c_n, c_tot, c_cen, c_grp, pool, *res, t_marks + 1) != CLOUD_OK) return fail(ctx, PDBEDA_ERR_ARGUMENT, "bonded key out of range");
+    const int64_t n_pool = pool.n_pool();
     if (n_pool == 0) { *out = res.release(); return PDBEDA_OK; }
-    t_marks[2] = now_s();
+    t_marks[3] = now_s();
 
     // ---- 3. device: pooled voxels -> union job (a group per residue + the domain group) ----
     const LabelJob *cj = clouds->job;
-    std::vector<int32_t> pool_group((size_t)n_pool), group_res;     // compact residue groups in increasing order
-    for (int64_t p = 0; p < n_pool; ++p) {
-        const int32_t r = at->residue[pool_atom[(size_t)p]];
-        if (group_res.empty() || group_res.back() != r) group_res.push_back(r);
-        pool_group[(size_t)p] = (int32_t)group_res.size() - 1;
-    }
-    const int n_rg = (int)group_res.size(), n_groups = n_rg + 1;
-    std::vector<int64_t> pool_voff((size_t)n_pool + 1, 0), set_off((size_t)n + 1, 0);
-    for (int64_t p = 0; p < n_pool; ++p) pool_voff[(size_t)p + 1] = pool_voff[(size_t)p] + c_n[(size_t)pool_cloud[(size_t)p]];
-    const int64_t V = pool_voff[(size_t)n_pool];
-    {   // voxel slice (all clouds) of every atom inside the sphere job's list, for the overlap tests
-        std::vector<int64_t> coff((size_t)nb + 1, 0);
-        for (int64_t c = 0; c < nb; ++c) coff[(size_t)c + 1] = coff[(size_t)c] + c_n[(size_t)c];
-        for (int64_t a = 0; a <= n; ++a) set_off[(size_t)a] = coff[(size_t)first[(size_t)a]];
-    }
-    // bonded pairs between pooled names (656): owner o tests its name's atom against every bonded partner that is pooled
-    std::vector<int32_t> pair_a, pair_b, pair_owner;
-    for (int64_t o = 0; o < at->n_owners; ++o) {
-        const int32_t k = at->owner_key[o], ia = pooled_of_key[(size_t)k];
-        if (ia < 0) continue;
-        res->owner_state[(size_t)o] = 1;
-        for (int64_t q = at->bonded_off[k]; q < at->bonded_off[k + 1]; ++q) {
-            const int32_t k2 = at->bonded[q];
-            if (k2 < 0 || k2 >= at->n_keys) return fail(ctx, PDBEDA_ERR_ARGUMENT, "bonded key out of range");
-            const int32_t ib = pooled_of_key[(size_t)k2];
-            if (ib < 0) continue;
-            pair_a.push_back(at->alias[ia]); pair_b.push_back(at->alias[ib]); pair_owner.push_back((int32_t)o);
-        }
-    }
-    const int64_t n_pairs = (int64_t)pair_a.size();
-    t_marks[3] = now_s();
+    const std::vector<int32_t> &pool_cloud = pool.pool_cloud, &pool_atom = pool.pool_atom, &pool_group = pool.pool_group, &pair_a = pool.pair_a, &pair_b = pool.pair_b;
+    const std::vector<int64_t> &pool_voff = pool.pool_voff, &set_off = pool.set_off;
+    const int n_rg = (int)pool.group_res.size(), n_groups = n_rg + 1;
+    const int64_t V = pool.V(), n_pairs = (int64_t)pair_a.size();
 
     GroupSetup gs;
     rc = group_alloc(ctx, 2 * V, n_groups, &gs);
@@ -4518,72 +4393,9 @@ extern "C" int pdbeda_aggregate_cloud(pdbeda_map *m, const pdbeda_cloud_atoms *a
                 1e3 * (t_wait1 - t_call), 1e3 * (t_pooled - t_wait1), 1e3 * (t_marks[0] - t_wait1), 1e3 * (t_marks[1] - t_marks[0]), 1e3 * (t_marks[2] - t_marks[1]),
                 1e3 * (t_marks[3] - t_marks[2]), 1e3 * (t_marks[4] - t_marks[3]), 1e3 * (t_pooled - t_marks[4]), 1e3 * (now_s() - t_pooled));
 
-    // ---- 4. host: overlap completeness, electrons per union component, emission order, totals (652-731) ----
-    for (int64_t q = 0; q < n_pairs; ++q)
-        if (!touch[(size_t)q]) res->owner_state[(size_t)pair_owner[(size_t)q]] = 2;
-    std::vector<double> electrons((size_t)nu, 0.0);
-    std::vector<int64_t> first_pool((size_t)nu, n_pool);
-    // Whose electrons a pooled cloud carries (cloud.atoms, 639 / 690 / 718).  The atoms of one coordinate share the cloud OBJECTS
-    // of the last of them (605, 622), and the atom loop of a residue overwrites their .atoms (639): when two pooled atoms of ONE
-    // residue share a coordinate, both pool entries are the same objects and name only the LATER atom -- the earlier one's
-    // electrons are in no residue or domain cloud (golden analysis_alias; round 3 counted both).  Atoms of different residues
-    // each get their own residue's snapshot (clone(), 675), so both count there and in the domain.
-    std::vector<int32_t> named_by((size_t)n);
-    for (int64_t i = 0; i < n; ++i) named_by[(size_t)i] = (int32_t)i;
-    {
-        std::vector<int32_t> last_of_alias((size_t)n, -1);             // per residue: the last pooled atom that uses the clouds of alias a
-        size_t r0 = 0;
-        const std::vector<int32_t> &pooled = res->atom_idx;            // (in atom order, hence residue by residue)
-        while (r0 < pooled.size()) {
-            size_t r1 = r0;
-            while (r1 < pooled.size() && at->residue[pooled[r1]] == at->residue[pooled[r0]]) ++r1;
-            for (size_t q = r0; q < r1; ++q) last_of_alias[(size_t)at->alias[pooled[q]]] = pooled[q];
-            for (size_t q = r0; q < r1; ++q) named_by[(size_t)pooled[q]] = last_of_alias[(size_t)at->alias[pooled[q]]];
-            for (size_t q = r0; q < r1; ++q) last_of_alias[(size_t)at->alias[pooled[q]]] = -1;
-            r0 = r1;
-        }
-    }
-    std::vector<std::pair<int32_t, int32_t>> members;                  // (union component, atom named by a pooled cloud in it): distinct pairs add electrons once
-    members.reserve(2 * (size_t)n_pool);
-    for (int kind = 0; kind < 2; ++kind) {
-        for (int64_t p = 0; p < n_pool; ++p) {
-            const int32_t k = comp[(size_t)(kind * n_pool + p)];
-            if (k < 0 || k >= nu) return fail(ctx, PDBEDA_ERR_STATE, "aggregate cloud: component rank out of range");
-            members.emplace_back(k, named_by[(size_t)pool_atom[(size_t)p]]);
-            if (p < first_pool[(size_t)k]) first_pool[(size_t)k] = p;
-        }
-    }
-    {   // (summed in atom order per component, as before: pool order is atom order)
-        std::stable_sort(members.begin(), members.end());
-        for (size_t q = 0; q < members.size(); ++q)
-            if (q == 0 || members[q] != members[q - 1]) electrons[(size_t)members[q].first] += at->weight[members[q].second];
-    }
-    std::vector<int64_t> order((size_t)nu);
-    for (int64_t k = 0; k < nu; ++k) order[(size_t)k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        const bool da = u_grp[(size_t)a] == n_rg, db = u_grp[(size_t)b] == n_rg;
-        if (da != db) return db;                                   // residue clouds first, then the domain clouds
-        return first_pool[(size_t)a] < first_pool[(size_t)b];
-    });
-    double num_voxels = 0.0, total_electrons = 0.0, total_density = 0.0;
-    for (int64_t idx = 0; idx < nu; ++idx) {
-        const int64_t k = order[(size_t)idx];
-        const bool dom = u_grp[(size_t)k] == n_rg;
-        pdbeda_cloud::Row row;
-        row.total = u_tot[(size_t)k]; row.n = u_n[(size_t)k]; row.electrons = electrons[(size_t)k];
-        for (int q = 0; q < 3; ++q) row.cen[q] = u_cen[3 * (size_t)k + q];
-        if (dom) {
-            total_electrons += row.electrons;
-            num_voxels += (double)row.n;
-            total_density += row.total;
-            row.residue = at->residue[pool_atom[(size_t)first_pool[(size_t)k]]];
-            if (row.electrons >= min_cloud_electrons) res->dom_rows.push_back(row);
-        } else {
-            row.residue = group_res[(size_t)u_grp[(size_t)k]];
-            if (row.electrons >= min_cloud_electrons) res->res_rows.push_back(row);
-        }
-    }
-    res->totals[0] = num_voxels; res->totals[1] = total_electrons; res->totals[2] = total_density;
+    // ---- 4. host: overlap completeness, electrons per union component, emission order, totals (652-731: pdbeda_cloud.h) ----
+    if (cloud_finish(*at, pool, u_n, u_tot, u_cen, u_grp, comp, touch, min_cloud_electrons, *res) != CLOUD_OK)
+        return fail(ctx, PDBEDA_ERR_STATE, "aggregate cloud: component rank out of range");
     *out = res.release();
     return PDBEDA_OK;
 }
@@ -4606,7 +4418,7 @@ extern "C" int pdbeda_cloud_atom_rows(pdbeda_cloud *c, int32_t *atom, double *to
     return PDBEDA_OK;
 }
 
-static int cloud_rows_out(const std::vector<pdbeda_cloud::Row> &rows, int32_t *residue, double *total_density, int64_t *n_voxels, double *electrons, double *centroid) {
+static int cloud_rows_out(const std::vector<CloudRow> &rows, int32_t *residue, double *total_density, int64_t *n_voxels, double *electrons, double *centroid) {
     for (size_t i = 0; i < rows.size(); ++i) {
         if (residue) residue[i] = rows[i].residue;
         if (total_density) total_density[i] = rows[i].total;

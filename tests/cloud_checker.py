@@ -126,6 +126,29 @@ def aggregate_cloud(header, grid, clouds, xyz, weight, residue, alias, key, bond
             "atom_distance": np.array([a[4] for a in atom_rows], dtype=np.float64), "res": table(res_rows), "dom": table(dom_rows)}
 
 
+def union_job(header, grid, clouds, pool_cloud, pool_group, n_groups, pair_a, pair_b, near=NEAR26):
+    """What the device delivers to the host between the two halves of pdbeda_aggregate_cloud's decisions (pdb_eda_amd/csrc/pdbeda_cloud.h), made
+    with the functions above.  ``clouds`` = atom_clouds(); a pooled cloud is a row of the clouds' table, which lists them atom by atom in list
+    order.  The union job has a group per residue group of the pool (``pool_group``) and the domain group n_groups - 1, which holds every pooled
+    voxel.  Returns u_n, u_total, u_centroid, u_group -- a row per connected component of a group's voxels, in no particular order --, comp
+    (2 x pool entries: the row that holds the entry's voxels in its residue group, then in the domain group) and touch (a flag per pair: the
+    voxels of all clouds of atom pair_a and those of atom pair_b touch)."""
+    flat = [c[0] for mine in clouds for c in mine]
+    rows, comp = [], np.full((2, len(pool_cloud)), -1, dtype=np.int32)
+    for g in range(n_groups):
+        kind = int(g == n_groups - 1)
+        inside = [p for p in range(len(pool_cloud)) if kind or pool_group[p] == g]
+        found = components(set().union(*[flat[pool_cloud[p]] for p in inside]) if inside else set(), near)
+        row_of = {v: len(rows) + k for k, part in enumerate(found) for v in part}
+        for p in inside:
+            comp[kind, p] = row_of[min(flat[pool_cloud[p]])]
+        rows += [(len(part),) + voxel_stats(header, grid, part) + (g,) for part in found]
+    everything = [set().union(*[c[0] for c in mine]) if mine else set() for mine in clouds]
+    touch = np.array([touches(everything[a], everything[b], near) for a, b in zip(pair_a, pair_b)], dtype=np.uint32)
+    return (np.array([r[0] for r in rows], dtype=np.int64), np.array([r[1] for r in rows], dtype=np.float64),
+            np.array([r[2] for r in rows], dtype=np.float64).reshape(-1, 3), np.array([r[3] for r in rows], dtype=np.int32), comp.reshape(-1), touch)
+
+
 def assert_same_tables(got, want, exact=False, ordered=True, what=""):
     """Every row of every table of two aggregate_cloud results.  Counts, atom indices, voxel counts, owner states, residue ordinals
     and numVoxels are exact; electrons and the cut-off agree to 1e-12, densities and centroids to 1e-9 relative (1e-9 absolute on
