@@ -27,6 +27,7 @@
 
 #include "pdbeda_kernels.h"
 #include "pdbeda_cloud.h"
+#include "pdbeda_jobplan.h"
 #include "pdbeda_stage.h"
 #include "pdbeda_tile.h"
 #include "pdbeda_upload.h"
@@ -237,7 +238,8 @@ struct LabelJob {
     float cut_pos = 0.0f, cut_neg = 0.0f;
     bool want_pos = false, want_neg = false;
     uint32_t flags = 0;
-    int tier = 0, unit_form = 0, reruns = 0;
+    bool worst_case = false;           // the run on record has the second run's shape: the worst-case arena and the unit tiles' launches
+    int reruns = 0;
     size_t bytes = 0;                  // bytes the job carved out of its arena (a recycled arena may be larger)
     // what the counters said, once read
     bool have_counts = false;
@@ -1045,10 +1047,9 @@ static int reduce_launch(pdbeda_map *m, int mode, const double *mean_dev, double
     return 0;
 }
 
-// The quantum of the order-independent blob sums of this map (see FixSums in pdbeda_kernels.h): S such that neither
-// sum |rho| over the whole map nor the first moment of one tile / one run (<= 2^22 max |rho|) can leave 62 bits.  Two
-// deterministic reductions over the map, once per map (the result is cached; a borrowed device pointer is taken to hold the
-// same grid for the life of the map).
+// The quantum of the order-independent blob sums of this map (see FixSums in pdbeda_kernels.h; the rule and the bounds it guarantees:
+// map_quantum in pdbeda_jobplan.h).  Two deterministic reductions over the map, once per map (the result is cached; a borrowed device
+// pointer is taken to hold the same grid for the life of the map).
 // The quantum of a map's integer blob sums from its range (sum |x|, max |x|: fixed reduction order, so the quantum is the same in
 // every run).  range_enqueue + range_apply: the pass rides in the same wait as the map's mean / std when those are asked for
 // first (pdbeda_map_stats: every DensityMatrix asks at once) -- a wait of its own in front of the map's first labelling job was
@@ -1063,18 +1064,10 @@ static int range_enqueue(pdbeda_map *m, double *range_host /* [2], filled at the
     return 0;
 }
 static void range_apply(pdbeda_map *m, const double range[2]) {
-    // the integer sums cannot hold a NaN or an infinity (fix_of would saturate without a word): such a map is refused by the
-    // labelling calls instead of producing wrong blob totals (the reference's sums would be NaN / inf for every blob that holds one)
-    if (!std::isfinite(range[0]) || !std::isfinite(range[1])) { m->fix_refused = true; return; }
-    const double bound = std::max(range[0], 4194304.0 * range[1]);
-    int S = 40;
-    if (bound > 0.0 && std::isfinite(bound)) {
-        int e = 0;
-        (void)frexp(bound, &e);        // bound < 2^e
-        S = 61 - e;
-    }
-    S = std::max(-900, std::min(S, 900));
-    m->fix_mul = ldexp(1.0, S);
+    bool refused = false;
+    const double mul = map_quantum(range[0], range[1], &refused);
+    if (refused) m->fix_refused = true;      // (NaN / infinite voxels: the labelling calls refuse the map)
+    else m->fix_mul = mul;
 }
 static int map_fix_mul(pdbeda_map *m) {
     pdbeda_ctx *ctx = m->ctx;
@@ -1086,6 +1079,24 @@ static int map_fix_mul(pdbeda_map *m) {
         range_apply(m, range);
     }
     if (m->fix_refused) return fail(ctx, PDBEDA_ERR_ARGUMENT, "the map holds non-finite density values: blob sums are undefined");
+    return 0;
+}
+// The quantum of sums over the unique box for a caller that leaves NaN / infinite voxels out of its sums (the partition, the basins): the map's
+// own, or -- the map's was refused -- one from the largest finite |rho| of the box (box_quantum; k_partition_range and a wait).  d_range: a
+// zeroed device word of the caller's.
+static int box_fix_mul(pdbeda_map *m, int nc, int nr, int uc, int ur, int us, unsigned long long *d_range, double *fix_mul) {
+    pdbeda_ctx *ctx = m->ctx;
+    *fix_mul = m->fix_mul;
+    if (!m->fix_refused) return 0;
+    const int64_t nbox = (int64_t)uc * ur * us;
+    unsigned long long bits = 0;
+    { PROF(ctx, "k_partition_range"); hipLaunchKernelGGL(k_partition_range, dim3(grid_for(nbox, 256, 4096)), dim3(256), 0, ctx->stream, m->dens, nc, nr, uc, ur, us, d_range); }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, d2h(ctx, &bits, d_range, 8));
+    HIP_TRY(ctx, ctx_sync(ctx));
+    double top;
+    memcpy(&top, &bits, 8);
+    *fix_mul = box_quantum(top, nbox);
     return 0;
 }
 
@@ -1253,29 +1264,27 @@ extern "C" int pdbeda_xyz2crs(pdbeda_map *m, const double *xyz, int64_t n, int32
 // Carve a job out of an arena.  max_runs / max_blobs are worst-case bounds (a run needs a
 // gap: <= bits/2 + 1 per word; a blob owns >= one 2x2x2 cell... we simply bound blobs by runs).
 // max_runs: run ids (comp_of_run); max_comps: component ids (every per-component array; generic jobs: == max_runs, a run is a component)
-static void job_carve(Job &job, Carver &cv, int n_vols, int64_t total_words, int64_t total_keys, int64_t max_runs,
-                        int64_t max_blobs, size_t extra_labels, int32_t **labels_out, int64_t n_tiles = 0, int64_t max_comps = -1) {
+// The rank / key table's arithmetic is plan_key_table's (pdbeda_jobplan.h); the table is returned for the callers that size a clear by it.
+static KeyTable job_carve(Job &job, Carver &cv, int n_vols, int64_t total_words, int64_t total_keys, int64_t max_runs,
+                          int64_t max_blobs, size_t extra_labels, int32_t **labels_out, int64_t n_tiles = 0, int64_t max_comps = -1) {
     if (max_comps < 0) max_comps = max_runs;
     job.run_cap = (uint32_t)max_runs; job.comp_cap = (uint32_t)max_comps; job.blob_cap = (uint32_t)std::min<int64_t>(max_blobs, 0xffffffffll);
     job.n_vols = n_vols;
     job.total_words = total_words;
-    job.key_words = (total_keys + 63) / 64;
-    job.n_fine = (int32_t)((job.key_words + KEY_FINE - 1) / KEY_FINE);
-    job.fine_shift = 4;   // counters per table entry: a power of two >= 16 that covers the job with KEY_GROUPS entries
-    while (((int64_t)KEY_GROUPS << job.fine_shift) < job.n_fine) job.fine_shift++;
-    job.fine_per_group = 1 << job.fine_shift;
-    job.n_groups = (job.n_fine + job.fine_per_group - 1) / job.fine_per_group;
+    const KeyTable kt = plan_key_table(total_keys, n_tiles);
+    job.key_words = kt.key_words;
+    job.n_fine = kt.n_fine; job.fine_shift = kt.fine_shift; job.fine_per_group = kt.fine_per_group; job.n_groups = kt.n_groups; job.n_fine_alloc = kt.n_fine_alloc;
+    job.clear_bits = kt.clear_bits; job.clear_fine = kt.clear_fine; job.clear_mid = kt.clear_mid;   // (what a tile's k_face_merge workgroup clears)
     job.vols = cv.take<VolDesc>(std::max(n_vols, 1));
     // counters, masks, first-key bitmap and rank counters in a row: a sphere / list job clears them with ONE fill (grouped_job;
     // whole-map jobs clear theirs in kernels)
     job.ctr = cv.take<Counters>(1);
     job.mask = cv.take<uint64_t>(total_words);
-    job.key_bits = cv.take<uint64_t>((size_t)(job.key_words + KEY_FINE - 1) / KEY_FINE * KEY_FINE);   // whole fine buckets (rank_of_key loads a bucket whole)
-    // the rank counters sit right behind the bitmap (ONE clear covers both), padded to whole groups
-    job.n_fine_alloc = (int32_t)((job.n_fine + job.fine_per_group - 1) / job.fine_per_group * job.fine_per_group);
-    job.fine_count = cv.take<uint32_t>((size_t)std::max(job.n_fine_alloc / 2, 8));   // 16-bit counters, two per word
-    job.mid_count = cv.take<uint32_t>((size_t)(job.key_words + KEY_FINE - 1) / KEY_FINE * (KEY_FINE / 16));   // a byte per 4 key words: 8 per bucket
-    job.group_count = (n_tiles && job.fine_shift > 4) ? cv.take<uint32_t>(KEY_GROUPS) : nullptr;   // (groups of 32 counters or more: maps beyond 2^25 keys = 256^3 fused)
+    job.key_bits = cv.take<uint64_t>(kt.key_bits_elems);
+    // the rank counters sit right behind the bitmap (ONE clear covers both)
+    job.fine_count = cv.take<uint32_t>(kt.fine_count_elems);
+    job.mid_count = cv.take<uint32_t>(kt.mid_count_elems);
+    job.group_count = kt.has_group_count ? cv.take<uint32_t>(KEY_GROUPS) : nullptr;
     job.run_base = cv.take<uint32_t>(total_words);
     job.comps_are_runs = n_tiles ? 0 : 1;
     job.comp_of_run = n_tiles ? cv.take<uint32_t>(max_runs) : nullptr;
@@ -1287,12 +1296,6 @@ static void job_carve(Job &job, Carver &cv, int n_vols, int64_t total_words, int
     job.tile_runs = n_tiles ? cv.take<uint32_t>(n_tiles) : nullptr;
     job.root_mask = n_tiles ? cv.take<uint64_t>((size_t)n_tiles * 4) : nullptr;
     job.n_tiles = (int32_t)n_tiles;
-    if (n_tiles) {   // (what a tile's k_face_merge workgroup clears)
-        const int64_t nt = n_tiles, nfc = job.n_fine_alloc / 2, nmid = (job.key_words + KEY_FINE - 1) / KEY_FINE * (KEY_FINE / 16);
-        job.clear_bits = (int32_t)((job.key_words + nt - 1) / nt);
-        job.clear_fine = (int32_t)((nfc + nt - 1) / nt);
-        job.clear_mid = (int32_t)((nmid + nt - 1) / nt);
-    }
     job.inbox = n_tiles ? cv.take<InboxEntry>((size_t)n_tiles * INBOX_CAP) : nullptr;
     job.inbox_count = n_tiles ? cv.take<uint32_t>((size_t)n_tiles * INBOX_STRIDE) : nullptr;
     job.vol_sign[0] = job.vol_sign[1] = 1;
@@ -1315,6 +1318,7 @@ static void job_carve(Job &job, Carver &cv, int n_vols, int64_t total_words, int
     job.b_group = cv.take<int32_t>(max_blobs);
     int32_t *lab = extra_labels ? cv.take<int32_t>(extra_labels) : nullptr;
     if (labels_out) *labels_out = lab;
+    return kt;
 }
 
 // Enqueue the labelling engine on a job whose masks are already painted.
@@ -1403,53 +1407,34 @@ static const int32_t *job_signed_labels(const LabelJob *lj, int32_t *scratch) {
     return scratch;
 }
 
-// Enqueue a whole-map job.  tier 0 carves the arena for what maps need in practice -- unit-tile run / component ids for a quarter of
-// the tiles' own run-id range above the tiles' ranges, a blob table of one row per 32 keys -- instead of the worst case (every other
-// voxel a run of a unit tile, a blob per 2x2x2 cell: 2.9 GB at 256^3, of which a job touches a few hundred MB).  A map that
-// needs more raises Counters::overflow on the device, stays inside its arena, and is run again at tier 1 (the worst case)
+// Enqueue a whole-map job.  The first run carves the arena for what maps need in practice instead of the worst case (2.9 GB at 256^3, of
+// which a job touches a few hundred MB), and leaves out the unit tiles' two launches: the sizes are plan_whole_map's (pdbeda_jobplan.h).  A map
+// that needs more raises Counters::overflow on the device, stays inside its arena, and is run again with worst_case set
 // by the first accessor that reads the counters (list_resolve_counts): correct always, slower only where it was slow already.
 // On success the job, its arena and the recipe of this run are written into *out (the record of a job's first run, or of the run it replaces).
-static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool want_pos, bool want_neg, uint32_t flags, int tier, int unit_form, LabelJob *out) {
+static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool want_pos, bool want_neg, uint32_t flags, bool worst_case, LabelJob *out) {
     pdbeda_ctx *ctx = m->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const Geom &g = m->geom;
     const int n_planes = (want_pos ? 1 : 0) + (want_neg ? 1 : 0);
     const int uc = g.unique_ncrs[0], ur = g.unique_ncrs[1], us = g.unique_ncrs[2];
-    const int row_words = (uc + 63) / 64;
-    const int64_t words_pp = (int64_t)row_words * ur * us;
-    const int64_t keys_pp = (int64_t)uc * ur * us;
-    const int64_t total_words = words_pp * n_planes, total_keys = keys_pp * n_planes;
-    // 26-connectivity: all voxels of an aligned 2x2x2 cell are mutually adjacent -> <= 1 blob per cell
-    const int64_t worst_blobs = (int64_t)((uc + 1) / 2) * ((ur + 1) / 2) * ((us + 1) / 2) * n_planes + 1;
     const bool labels = (flags & PDBEDA_FLAG_LABELS) != 0;
-    const size_t lab_elems = labels ? (size_t)keys_pp : 0;   // ONE signed volume, also for a fused call
+    const WholeMapPlan wp = plan_whole_map(uc, ur, us, n_planes, worst_case, labels);
+    if (wp.refusal == PLAN_KEYS || wp.refusal == PLAN_AXIS) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");
+    if (wp.refusal == PLAN_RUN_IDS)
+        return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large for whole-map labelling: %d x %d x %d voxels need %lld run ids (limit 2^31: about 1100^3 for a fused job)",
+                    uc, ur, us, (long long)wp.run_ids_needed);
+    const int64_t tiles_pp = wp.tiles_pp;
 
     TileDims td;
-    td.ctiles = (row_words + 3) / 4;                      // tiles of at most 4 mask words (256 voxels) along c ...
-    td.cw = (row_words + td.ctiles - 1) / td.ctiles;      // ... of equal width: 5 words are 3 + 2, not 4 + 1
-    td.rtiles = (ur + TILE_R - 1) / TILE_R;
-    td.stiles = (us + TILE_S - 1) / TILE_S;
+    td.ctiles = wp.ctiles; td.cw = wp.cw; td.rtiles = wp.rtiles; td.stiles = wp.stiles;
     td.n_planes = n_planes;
-    td.uc = uc; td.ur = ur; td.us = us; td.row_words = row_words;
+    td.uc = uc; td.ur = ur; td.us = us; td.row_words = wp.row_words;
     td.nc = g.ncrs[0]; td.nr = g.ncrs[1];
     td.cut[0] = want_pos ? cut_pos : cut_neg;
     td.sign[0] = want_pos ? 1 : -1;
     td.cut[1] = cut_neg;
     td.sign[1] = -1;
-    const int64_t tiles_pp = (int64_t)td.ctiles * td.rtiles * td.stiles;
-    if (tiles_pp >= (1ll << 31) || keys_pp >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");   // (first keys inside a plane are 31-bit)
-    if (td.rtiles > 65535 || td.stiles > 65535) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");              // (the tile kernels' grids are 3-D)
-    // run / component ids: a fixed range per tile (no allocation atomics) + the ids of the unit tiles above them
-    const int64_t tile_runs = tiles_pp * td.cw * 64 * 32, tile_comps = tiles_pp * CCAP;
-    const int64_t worst_unit = (int64_t)((uc + 1) / 2) * ur * us * n_planes + 1;       // every other voxel a run
-    if (tile_runs + worst_unit >= (1ll << 31))
-        return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large for whole-map labelling: %d x %d x %d voxels need %lld run ids (limit 2^31: about 1100^3 for a fused job)",
-                    uc, ur, us, (long long)(tile_runs + worst_unit));
-    // (tier 0: a quarter of the tiles' own run-id range -- every tile a unit tile of 2 048 word-runs, or a quarter of them at the
-    //  most a tile can hold: a protein-like map at 0.5 sigma, every tile over its LDS capacities, still runs once)
-    const int64_t unit_ids = tier == 0 ? std::min<int64_t>(worst_unit, std::max<int64_t>(65536, tile_runs / 4)) : worst_unit;
-    const int64_t max_blobs = tier == 0 ? std::min<int64_t>(worst_blobs, std::max<int64_t>(4096, total_keys / 32)) : worst_blobs;
-    const int64_t max_runs = tile_runs + unit_ids, max_comps = tile_comps + unit_ids;
 
     int rc_fix = map_fix_mul(m);
     if (rc_fix) return rc_fix;
@@ -1460,13 +1445,13 @@ static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool w
     Arena arena;
     int32_t *labels_dev = nullptr;
     int rc = arena_carve(ctx, "whole-map labelling", &arena, [&](Carver &cv) {
-        job_carve(job, cv, n_planes, total_words, total_keys, max_runs, max_blobs, lab_elems, &labels_dev, tiles_pp, max_comps);
+        job_carve(job, cv, n_planes, wp.total_words, wp.total_keys, wp.max_runs, wp.max_blobs, wp.lab_elems, &labels_dev, tiles_pp, wp.max_comps);
         need = cv.off;
     });
     if (rc) return rc;
     job.vol_sign[0] = td.sign[0];
     job.vol_sign[1] = td.sign[1];
-    job.unit_form = unit_form;
+    job.unit_form = worst_case ? 1 : 0;      // (the second run has both: the worst-case arena and the unit tiles' launches)
     // the job's number: unique in the process (contexts recycle each other's memory through the driver), started at a random value
     // (so is another process's); stale flags of an earlier job in recycled memory never match it.  Never 0 / the poison pattern.
     static std::atomic<uint32_t> g_epoch{[] {
@@ -1483,13 +1468,13 @@ static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool w
         VolDesc &v = init.v[p];
         v.dim[0] = uc; v.dim[1] = ur; v.dim[2] = us;
         v.org[0] = v.org[1] = v.org[2] = 0;
-        v.row_words = row_words;
+        v.row_words = wp.row_words;
         v.group = p;
-        v.word_base = words_pp * p;
-        v.key_base = keys_pp * p;
+        v.word_base = wp.words_pp * p;
+        v.key_base = wp.keys_pp * p;
     }
-    init.runs0 = (unsigned)tile_runs;
-    init.comps0 = (unsigned)tile_comps;
+    init.runs0 = (unsigned)wp.tile_runs;
+    init.comps0 = (unsigned)wp.tile_comps;
     hipStream_t st = ctx->stream;
     int pair_slots = PAIR_SLOTS;   // test hook: a tiny LDS pair set overflows on small inputs (PDBEDA_DEBUG_EDGE_CAP = slots, a power of two)
     if (ctx->debug_edge_cap > 0) { pair_slots = 1; while (pair_slots * 2 <= std::min<int64_t>(ctx->debug_edge_cap, PAIR_SLOTS)) pair_slots *= 2; }
@@ -1511,7 +1496,7 @@ static int whole_map_enqueue(pdbeda_map *m, float cut_pos, float cut_neg, bool w
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, PDBEDA_ERR_DEVICE, "whole-map labelling launch: %s", hipGetErrorString(e));
     out->job = job; out->arena = std::move(arena); out->td = td; out->labels_dev = labels_dev; out->labels_done = labels; out->bytes = need;
-    out->cut_pos = cut_pos; out->cut_neg = cut_neg; out->want_pos = want_pos; out->want_neg = want_neg; out->flags = flags; out->tier = tier; out->unit_form = unit_form;
+    out->cut_pos = cut_pos; out->cut_neg = cut_neg; out->want_pos = want_pos; out->want_neg = want_neg; out->flags = flags; out->worst_case = worst_case;
     return PDBEDA_OK;
 }
 
@@ -1520,8 +1505,8 @@ static int full_blobs_impl(pdbeda_map *m, float cut_pos, float cut_neg, bool wan
     pdbeda_ctx *ctx = m->ctx;
     std::unique_ptr<LabelJob> lj(new_label_job(ctx, m));
     lj->whole_map = true;
-    const int tier = ctx->debug_worst_case_arena ? 1 : 0, form = tier;   // (the debug hook: the second run's shape at once)
-    int rc = whole_map_enqueue(m, cut_pos, cut_neg, want_pos, want_neg, flags, tier, form, lj.get());
+    const bool worst_case = ctx->debug_worst_case_arena;   // (the debug hook: the second run's shape at once)
+    int rc = whole_map_enqueue(m, cut_pos, cut_neg, want_pos, want_neg, flags, worst_case, lj.get());
     if (rc) return rc;
     for (int p = 0; p < lj->td.n_planes; ++p) {
         pdbeda_bloblist *bl = job_view(lj.get(), p, p, p + 1, lj->td.sign[p]);
@@ -1603,11 +1588,10 @@ static int list_resolve_counts(pdbeda_bloblist *bl) {
         // for this map (bits 0 / 1), or when the map has unit tiles and the job was enqueued without their two launches (bit 2,
         // Job::unit_form).  The second run has both: the worst-case arena and the unit launches -- a first run without the unit
         // launches does not know how many ids its unit tiles would have asked for.
-        const int tier = 1, form = 1;
-        if (tier == lj->tier && form == lj->unit_form) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling overflowed its worst-case arena");
+        if (lj->worst_case) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling overflowed its worst-case arena");
         if (lj->voxels_done) return fail(ctx, PDBEDA_ERR_STATE, "whole-map labelling: overflow noticed after the voxel lists were made");
         lj->arena.put();      // the first run's arena goes back BEFORE the larger one is carved: the job's peak is the larger of the two, not their sum (stream order: the first run's kernels are done -- ctx_sync above)
-        int rc = whole_map_enqueue(lj->map, lj->cut_pos, lj->cut_neg, lj->want_pos, lj->want_neg, lj->flags, tier, form, lj);
+        int rc = whole_map_enqueue(lj->map, lj->cut_pos, lj->cut_neg, lj->want_pos, lj->want_neg, lj->flags, true, lj);
         if (rc) return rc;      // (the record holds no arena now)
         lj->reruns += 1;
         const int rc_fetch = fetch();
@@ -1800,11 +1784,11 @@ static int list_moments_compute(pdbeda_bloblist *bl) {
     const RankRange ranks = list_ranks(bl);
     const int64_t cnt = ranks.hi - ranks.lo;
     if (cnt == 0 || nv == 0) { bl->shape_done = true; return PDBEDA_OK; }
-    // What the accumulators hold: F = fix_of(|rho|) < 2^39 (map_fix_mul keeps 2^22 max |rho| inside 61 bits).  The low limbs of the two-limb sums are
-    // below 2^32 per voxel and are read as signed 64-bit: fewer than 2^31 voxels in the list.  sum F is ONE 64-bit word, and the high limb of F d d' is
-    // below 2^37 per voxel: a whole-map blob counts every stored voxel at most once (nothing wraps in the unique box), so the map's sum |rho| < 2^61
-    // bounds sum F and 2^61 * 2^30 / 2^32 the high limbs; a sphere / list batch may meet a stored voxel again through the periodic wrap, so only its
-    // voxel count bounds it: below 2^24 voxels sum F < 2^63 and the high limbs < 2^61.
+    // What the accumulators hold: F = fix_of(|rho|), bounded per voxel and per map by the quantum's rule (map_quantum in pdbeda_jobplan.h).  The low
+    // limbs of the two-limb sums are below 2^32 per voxel and are read as signed 64-bit: fewer than 2^31 voxels in the list.  sum F is ONE 64-bit word,
+    // and the high limb of F d d' is F * 2^30 / 2^32 at the most: a whole-map blob counts every stored voxel at most once (nothing wraps in the unique
+    // box), so the map's bound holds for sum F and a quarter of it for the high limbs; a sphere / list batch may meet a stored voxel again through the
+    // periodic wrap, so only its voxel count bounds it: the rule's wrapped-batch limit, refused below.
     if (cnt >= (1ll << 31) || nv >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a list of 2^31 blobs or voxels, or more");
     if (!lj->whole_map && nv >= (1ll << 24)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "blob moments: a sphere / list batch of 2^24 voxels or more");
     pdbeda_map *m = lj->map;
@@ -2130,9 +2114,9 @@ static int peaks_impl(pdbeda_map *m, int n_planes, const float cut[2], const int
     const Geom &g = m->geom;
     const int64_t nvox = (int64_t)g.unique_ncrs[0] * g.unique_ncrs[1] * g.unique_ncrs[2];
     if (nvox >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");       // (the c-major position is the low word of a key)
-    if ((g.unique_ncrs[1] + PK_R - 1) / PK_R > 65535 || (g.unique_ncrs[2] + PK_S - 1) / PK_S > 65535) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");
-    const int64_t n_tiles = (int64_t)((g.unique_ncrs[0] + PK_C - 1) / PK_C) * ((g.unique_ncrs[1] + PK_R - 1) / PK_R) * ((g.unique_ncrs[2] + PK_S - 1) / PK_S);
-    if (n_tiles * 512 >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");      // (a tile holds at most 512 peaks: no two are neighbours)
+    const TileGrid tg = tile_grid(g.unique_ncrs, PK_C, PK_R, PK_S);
+    const int64_t n_tiles = tg.n;
+    if ((tg.refusal & TILES_AXIS) || n_tiles * 512 >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "grid too large");      // (a tile holds at most 512 peaks: no two are neighbours)
     for (int p = 0; p < n_planes; ++p) {
         const int rc = peaks_check_blobs(m, blobs[p], sign[p], cut[p]);
         if (rc) return rc;
@@ -2353,22 +2337,11 @@ static int basins_compute(pdbeda_peaklist *pl, int32_t *basin_host) {
     std::vector<unsigned long long> acc(BN_ACC * np);
     unsigned long long orphans = 0;
     int rounds = 0;
-    double fix_mul = m->fix_mul;
+    double fix_mul = 0.0;
     auto run = [&]() -> int {
         hipStream_t st = ctx->stream;
         HIP_TRY(ctx, hipMemsetAsync(a.acc, 0, (size_t)((char *)(d_range + 1) - (char *)a.acc), st));
-        if (m->fix_refused) {      // NaN / infinite voxels: they enter no sum, and the quantum comes from the finite voxels of the box (as the partition's)
-            unsigned long long bits = 0;
-            { PROF(ctx, "k_partition_range"); hipLaunchKernelGGL(k_partition_range, dim3(grid_for(nbox, 256, 4096)), dim3(256), 0, st, m->dens, pa.nc, pa.nr, uc, ur, us, d_range); }
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, d2h(ctx, &bits, d_range, 8));
-            HIP_TRY(ctx, ctx_sync(ctx));
-            double top;
-            memcpy(&top, &bits, 8);
-            int S = 40, e = 0;
-            if (top > 0.0) { (void)frexp(top * (double)std::max<int64_t>(nbox, 1ll << 22), &e); S = 61 - e; }      // (|sum| <= voxels x max |rho| < 2^61)
-            fix_mul = ldexp(1.0, std::max(-900, std::min(S, 900)));
-        }
+        if (int rc = box_fix_mul(m, pa.nc, pa.nr, uc, ur, us, d_range, &fix_mul)) return rc;
         HIP_TRY(ctx, h2d_one(ctx, d_peak_box, peak_box.data(), 4 * np));
         a.dens = m->dens;
         a.uc = uc; a.ur = ur; a.us = us; a.nc = pa.nc; a.nr = pa.nr;
@@ -2663,13 +2636,14 @@ static int grouped_job(pdbeda_map *m, GroupSetup &gs, int64_t n_items, int64_t n
     Job &job = lj->job;
     memset(&job, 0, sizeof job);
     job.fix_mul = m->fix_mul;
-    int rc = arena_carve(ctx, "grouped blobs", &lj->arena, [&](Carver &cv) { job_carve(job, cv, (int)n_groups, gs.total_words, gs.total_keys, max_runs, max_runs, 0, nullptr); });
+    KeyTable kt;
+    int rc = arena_carve(ctx, "grouped blobs", &lj->arena, [&](Carver &cv) { kt = job_carve(job, cv, (int)n_groups, gs.total_words, gs.total_keys, max_runs, max_runs, 0, nullptr); });
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     hipError_t e = hipSuccess;
     {   // volume descriptors into the job + zeroes over counters, masks, first-key bitmap and both levels of rank counters (adjacent in the arena: job_carve): one launch
         static_assert(sizeof(VolDesc) % 16 == 0, "VolDesc is copied in 16-byte units");
-        const size_t zero_bytes = ((size_t)((char *)(job.mid_count + (job.key_words + KEY_FINE - 1) / KEY_FINE * (KEY_FINE / 16)) - (char *)job.ctr) + 15) & ~(size_t)15;   // (into the carve's own padding)
+        const size_t zero_bytes = ((size_t)((char *)(job.mid_count + kt.mid_count_elems) - (char *)job.ctr) + 15) & ~(size_t)15;   // (into the carve's own padding)
         const PendingCopy pend = gs.pend.take();      // (the staged inputs, when their copy was left to this launch)
         const size_t vol16 = sizeof(VolDesc) * (size_t)n_groups / 16, in16 = pend.bytes / 16;
         // (volume descriptors that are part of the inputs still to be copied come straight from the staged block)
@@ -2852,10 +2826,7 @@ extern "C" int pdbeda_radial_profiles(pdbeda_map *m, const double *xyz, int64_t 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int rc_fix = map_fix_mul(m);      // (a wait when the map's range is not known yet: before anything is staged)
     if (rc_fix) return rc_fix;
-    // |fix_of(rho)| < 2^39 (map_fix_mul keeps 2^22 max |rho| inside 61 bits), so the integer sum of a shell of up to 2^22 voxels cannot leave 64
-    // bits; a larger box takes a quantum coarser by the factor it is larger by.
-    double fix_mul = m->fix_mul;
-    for (int64_t room = 1ll << 22; room < largest; room <<= 1) fix_mul *= 0.5;
+    const double fix_mul = coarsened_for(m->fix_mul, largest);      // (a shell's sum inside 64 bits: the quantum's rule in pdbeda_jobplan.h)
     const double fix_inv = 1.0 / fix_mul;      // (powers of two: exact)
     const size_t cells = (size_t)n_shells, per_atom = 48 + 32 * cells + 1, slack = 7 * 64;
     const bool direct = copy_kernels() && ctx->pinned.base && pinned_room(ctx) >= per_atom + slack;
@@ -3319,9 +3290,10 @@ extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_
     const Geom &g = m->geom;
     const int uc = g.unique_ncrs[0], ur = g.unique_ncrs[1], us = g.unique_ncrs[2];
     const int64_t nbox = (int64_t)uc * ur * us;
-    const int tiles_c = (uc + PT_C - 1) / PT_C, tiles_r = (ur + PT_R - 1) / PT_R, tiles_s = (us + PT_S - 1) / PT_S;
-    const int64_t n_tiles = (int64_t)tiles_c * tiles_r * tiles_s;
-    if (nbox <= 0 || n_tiles >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map partition: the box is empty or has 2^31 tiles or more");
+    const TileGrid tg = tile_grid(g.unique_ncrs, PT_C, PT_R, PT_S);      // (a 1-D grid of tiles: only their number is limited)
+    const int tiles_c = tg.nc, tiles_r = tg.nr;
+    const int64_t n_tiles = tg.n;
+    if (tg.refusal & (TILES_EMPTY | TILES_2P31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map partition: the box is empty or has 2^31 tiles or more");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (m->fix_mul == 0.0 && !m->fix_refused) {      // (a wait when the map's range is not known yet: before anything is staged)
         const int rc = map_fix_mul(m);
@@ -3354,19 +3326,8 @@ extern "C" int pdbeda_map_partition(pdbeda_map *m, const double *xyz, int64_t n_
         hipStream_t st = ctx->stream;
         HIP_TRY(ctx, hipMemsetAsync(gb.count, 0, 4 * (size_t)cells, st));
         HIP_TRY(ctx, hipMemsetAsync(d_tab, 0, 8 * tables, st));
-        double fix_mul = m->fix_mul;
-        if (m->fix_refused) {      // NaN / infinite voxels: they enter no sum, and the quantum comes from the finite voxels of the box
-            unsigned long long bits = 0;
-            { PROF(ctx, "k_partition_range"); hipLaunchKernelGGL(k_partition_range, dim3(grid_for(nbox, 256, 4096)), dim3(256), 0, st, m->dens, g.ncrs[0], g.ncrs[1], uc, ur, us, d_tab + tables - 1); }
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, d2h(ctx, &bits, d_tab + tables - 1, 8));
-            HIP_TRY(ctx, ctx_sync(ctx));
-            double top;
-            memcpy(&top, &bits, 8);
-            int S = 40, e = 0;
-            if (top > 0.0) { (void)frexp(top * (double)std::max<int64_t>(nbox, 1ll << 22), &e); S = 61 - e; }      // (|sum| <= voxels x max |rho| < 2^61)
-            fix_mul = ldexp(1.0, std::max(-900, std::min(S, 900)));
-        }
+        double fix_mul = 0.0;
+        if (int rc = box_fix_mul(m, g.ncrs[0], g.ncrs[1], uc, ur, us, d_tab + tables - 1, &fix_mul)) return rc;
         if (n_atoms > 0) HIP_TRY(ctx, h2d_one(ctx, d_xyz, xyz, 24 * na));
         gb.sort_points(ctx, grid, d_xyz, n_atoms);
         PartitionArgs a;
@@ -3515,15 +3476,6 @@ extern "C" int pdbeda_atom_qscores(pdbeda_map *m, const double *xyz, int64_t n_a
 // ------------------------------------------------------------------------------------
 // From the model to a map: the density of Gaussian atoms, the sums that correlate two maps (no reference counterpart; the contracts: include/pdbeda.h)
 // ------------------------------------------------------------------------------------
-// The shift of the model density's integer sums: the largest S <= 40 with n_gridded * a_max * 2^S <= 2^62 (fp64; ldexp is exact).
-static int model_shift(int64_t n_gridded, double a_max) {
-    const double prod = (double)n_gridded * a_max;
-    int S = 40;
-    if (!(prod > 0.0)) return S;
-    while (S > -1000 && ldexp(prod, S) > 0x1p62) --S;
-    return S;
-}
-
 // The launch graph: memset of the cell counts and the two counters; the atoms' coordinates, amplitudes, exponents and radii in one row of scratch;
 // the grid build (GridBuild) over the atoms inside the crop box -- the xyz bounding box of the STORED box grown by the largest radius
 // (crop_cell_grid): an atom outside it reaches no voxel, and the grid never grows with atoms that lie far from the map --; k_model_tile, a workgroup per
@@ -3549,9 +3501,10 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
     const double r_max = n_atoms > 0 ? (double)r_top : 1.0;      // (no atom: any cell edge will do)
     if (!reach_below_2p29_steps(g, r_max)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the largest radius spans 2^29 grid steps or more");
     const int nc = g.ncrs[0], nr = g.ncrs[1], ns = g.ncrs[2];
-    const int tiles_c = (nc + PT_C - 1) / PT_C, tiles_r = (nr + PT_R - 1) / PT_R, tiles_s = (ns + PT_S - 1) / PT_S;
-    const int64_t n_tiles = (int64_t)tiles_c * tiles_r * tiles_s;
-    if (like->n_vox <= 0 || n_tiles >= (1ll << 31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the map is empty or has 2^31 tiles or more");
+    const TileGrid tg = tile_grid(g.ncrs, PT_C, PT_R, PT_S);      // (a 1-D grid of tiles: only their number is limited)
+    const int tiles_c = tg.nc, tiles_r = tg.nr;
+    const int64_t n_tiles = tg.n;
+    if (tg.refusal & (TILES_EMPTY | TILES_2P31)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the map is empty or has 2^31 tiles or more");
     const int32_t first[3] = {0, 0, 0}, last[3] = {nc - 1, nr - 1, ns - 1};      // the grid of the atoms within the largest radius of the STORED box
     double blo[3], bhi[3];
     crs_box_xyz(g, first, last, blo, bhi);
@@ -3567,7 +3520,7 @@ extern "C" int pdbeda_model_density(pdbeda_map *like, const double *xyz, int64_t
         a_max = std::max(a_max, t);
     }
     if (!std::isfinite((double)std::max<int64_t>(n_gridded, 1) * a_max)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "model density: the amplitudes of an atom add up beyond fp64");
-    const int S = model_shift(n_gridded, a_max);
+    const int S = model_shift(n_gridded, a_max);      // (pdbeda_jobplan.h)
     if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t cells = grid.n_cells;

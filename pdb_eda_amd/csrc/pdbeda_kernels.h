@@ -12,6 +12,7 @@
 // runs of the 4 "earlier" neighbour rows + the previous word (26-connectivity,
 // non-periodic, cutils.pyx:44-70).
 #pragma once
+#include "pdbeda_jobplan.h"
 #include "pdbeda_spherebox.h"
 #include "pdbeda_wave.h"
 
@@ -188,9 +189,7 @@ struct InboxEntry {           // 88 bytes: what a (tile, root) pair folds into t
 constexpr int INBOX_STRIDE = 32;   // uint32 per inbox counter: a cache line each
 constexpr int INBOX_CAP = 192;   // entries per tile (a root tile of a map-spanning blob overflows: those pairs fold with atomics)
 
-constexpr int TILE_COMPS = 256;   // component ids a whole-map tile owns (== CCAP of pdbeda_tile.h)
-constexpr int KEY_FINE = 32;      // key words per fine counter (2048 keys)
-constexpr int KEY_GROUPS = 1024;  // entries of the prefix table a k_emit block builds in LDS
+// (TILE_COMPS, KEY_FINE, KEY_GROUPS: pdbeda_jobplan.h, shared with the host's planner)
 constexpr int WAVE = 64;
 
 __device__ inline int lane_id() { return threadIdx.x & 63; }

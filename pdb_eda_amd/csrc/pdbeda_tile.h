@@ -51,7 +51,7 @@
 
 namespace pdbeda {
 
-constexpr int TILE_R = 8, TILE_S = 8;
+// (TILE_R, TILE_S: pdbeda_jobplan.h, shared with the host's planner)
 constexpr int RCAP = 1408;  // word-runs of a tile (both signs) whose parents fit the parent table proper
 constexpr int RCAP_DENSE = 4096;   // ... and with the parked values' LDS as more of the same table (a tile that dense re-reads its values from L2 anyway)
 constexpr int CCAP = 256;   // tile-local components (both signs together) handled in LDS
