@@ -563,6 +563,39 @@ int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b /* may be NULL */,
                            pdbeda_map **mean_a, pdbeda_map **std_a, pdbeda_map **z_a,
                            pdbeda_map **mean_b, pdbeda_map **std_b, pdbeda_map **cc);   /* any may be NULL */
 
+/* ---- from a REGION of a map to a map: the ordered spread of a mask ---- */
+/* Dilation, erosion, opening, closing, bounded distance maps, soft edges and masking in one primitive (no reference counterpart): an integer
+ * contract over a caller-made ORDERED table of offsets, as pdbeda_bloblist_nearest has.  Integer up to the last step:
+ * Seeds: a stored voxel u is a seed iff (double)x[u] > (double)threshold, strict; under PDBEDA_SPREAD_BELOW iff (double)x[u] <
+ * (double)threshold.  A NaN is never a seed; infinities compare as IEEE says.
+ * Positions: an index j on an axis follows the wrap rule of pdbeda_map_filter, per axis: if j < 0 or j >= n then j -= floor(j / I) * I;
+ * afterwards an index with n <= j < I is absent.  A position that is absent on any axis is no seed.  So a full-cell map spreads
+ * periodically however often the reach wraps, a cut-out sees nothing outside, a stored box larger than its cell reads its own copies.
+ * Rank: for every stored voxel v over ALL of ncrs, t(v) is the smallest t such that v + offsets[t] (n_offsets x 3: dc, dr, ds) is a seed,
+ * and n_offsets if there is none.  The library gives the table no geometric meaning and does not check its order; duplicate offsets are
+ * legal (the smallest t wins).
+ * Value: *out is a NEW map on the geometry of `map` -- ownership and lifetime are those of pdbeda_map_combine's result (pdbeda_map_free).
+ * Without `base` the voxel is values[t(v)] with its bits kept (values: n_offsets + 1 float32, the last for "no seed in reach"; NaN and
+ * infinities are allowed).  With `base` it is float32((double)base[v] * (double)values[t(v)]): the product of two float32 is exact in
+ * fp64, so this is ONE rounding; values that are not finite propagate.
+ * counters (may be NULL): {seeds among the stored voxels, voxels with t < n_offsets, the path taken: 1 rows, 0 ordered walk}.  A table
+ * whose every (dr, ds) row is a contiguous run of dc with ranks that fall to one minimum and rise behind it (every ball in ascending
+ * distance is one) is searched row by row with two bit scans per row; any other table, and every table under PDBEDA_SPREAD_ROWS=0 in the
+ * environment (read at every call), is walked in order.  The paths agree to the bit.
+ * A lane owns its voxel: no atomic, no reduction of values across lanes; two calls agree to the bit.
+ * PDBEDA_ERR_ARGUMENT before any launch: a NULL map, offsets, values or out; n_offsets outside 1 .. PDBEDA_SPREAD_MAX_OFFSETS; a component
+ * beyond +-PDBEDA_SPREAD_MAX_REACH; a NaN threshold; an unknown flag; a base of another shape or context; an axis of 2^30 indices or more.
+ * Synchronous; a failing call leaves the context usable and *out untouched.  Scratch: the table and two counts per tile, from a
+ * self-releasing device arena. */
+#define PDBEDA_SPREAD_MAX_OFFSETS 16384
+#define PDBEDA_SPREAD_MAX_REACH 32        /* |dc|, |dr|, |ds| of every offset */
+#define PDBEDA_SPREAD_BELOW 1u
+int pdbeda_map_spread(pdbeda_map *map, float threshold, uint32_t flags,
+                      const int32_t *offsets, int64_t n_offsets,   /* n x 3: dc, dr, ds; an ORDERED table */
+                      const float *values,                          /* n_offsets + 1; the last: no seed in reach */
+                      pdbeda_map *base /* may be NULL */,
+                      pdbeda_map **out, int64_t counters[3] /* may be NULL */);
+
 /* ---- from a map to a map on ANOTHER grid: resampling under coordinate operators ---- */
 /* A resident map carried to the grid of `dst_geom` through one or more affine operators (no reference counterpart; every other call stays
  * on the grid the map came with): two entries on one grid, the density under symmetry mates, an average over NCS copies, a finer box.

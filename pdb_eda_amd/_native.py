@@ -126,6 +126,7 @@ _SIGS = {
     "pdbeda_map_pair_moments": (C.c_int, [_p, _p, C.c_float, C.POINTER(_i64), _p]),
     "pdbeda_map_filter": (C.c_int, [_p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_uint32, C.POINTER(_p)]),
     "pdbeda_map_local_stats": (C.c_int, [_p, _p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_double, _p, _p, _p, _p, _p, _p]),
+    "pdbeda_map_spread": (C.c_int, [_p, C.c_float, C.c_uint32, _p, _i64, _p, _p, C.POINTER(_p), _p]),
     "pdbeda_map_resample": (C.c_int, [_p, C.POINTER(Geometry), _p, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _p, C.c_double, C.POINTER(_p), C.POINTER(_p), _p]),
     "pdbeda_map_fft": (C.c_int, [_p, C.POINTER(_p)]),
     "pdbeda_spectrum_inverse": (C.c_int, [_p, _p, C.POINTER(_p)]),
@@ -534,6 +535,9 @@ def radix_select(digit, bits, ranks):
 
 FILTER_MAX_RADIUS = 64           # PDBEDA_FILTER_MAX_RADIUS
 FILTER_RENORMALIZE = 1           # PDBEDA_FILTER_RENORMALIZE
+SPREAD_MAX_OFFSETS = 16384       # PDBEDA_SPREAD_MAX_OFFSETS
+SPREAD_MAX_REACH = 32            # PDBEDA_SPREAD_MAX_REACH
+SPREAD_BELOW = 1                 # PDBEDA_SPREAD_BELOW
 LOCAL_STATS_OUTPUTS = ("mean_a", "std_a", "z_a", "mean_b", "std_b", "cc")      # the output pointers of pdbeda_map_local_stats, in order
 
 
@@ -718,6 +722,21 @@ class DeviceMap(object):
         self._ctx.check(self._ctx._lib.pdbeda_map_filter(self._h, _ptr(taps[0]), len(taps[0]) // 2, _ptr(taps[1]), len(taps[1]) // 2, _ptr(taps[2]), len(taps[2]) // 2,
                                                          FILTER_RENORMALIZE if renormalize else 0, C.byref(h)), "pdbeda_map_filter")
         return type(self)._made(self, h)
+
+    def spread(self, offsets, values, threshold=0.5, below=False, base=None, counters=False):
+        """pdbeda_map_spread: a new resident map -- per stored voxel ``values[t]`` (times ``base``'s voxel, rounded once), t the first entry of the
+        ordered ``offsets`` table (n x 3 int32: dc, dr, ds) that leads to a seed (a voxel > ``threshold``, or < it with ``below``) under the map's
+        wrap rule, and n without one: ``values`` has n + 1 float32 entries.  With ``counters`` the result is (map, {"seeds", "reached", "rows"})."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, 3)
+        values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        if len(values) != len(offsets) + 1:
+            raise ValueError("values must have one entry per offset and a last one for no seed in reach")
+        h = C.c_void_p()
+        ctr = np.zeros(3, dtype=np.int64)
+        self._ctx.check(self._ctx._lib.pdbeda_map_spread(self._h, C.c_float(threshold), SPREAD_BELOW if below else 0, _ptr(offsets) if len(offsets) else None, len(offsets),
+                                                         _ptr(values), base._h if base is not None else None, C.byref(h), _ptr(ctr)), "pdbeda_map_spread")
+        made = type(self)._made(self, h)
+        return (made, {"seeds": int(ctr[0]), "reached": int(ctr[1]), "rows": int(ctr[2])}) if counters else made
 
     def local_stats(self, other, taps_c, taps_r, taps_s, std_floor=0.0, want=None):
         """pdbeda_map_local_stats: a dict of new resident maps out of ``mean_a``, ``std_a``, ``z_a`` and, with ``other``, ``mean_b``, ``std_b``,

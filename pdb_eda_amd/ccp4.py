@@ -866,6 +866,76 @@ class DensityMatrix(object):
         names = {"mean_a": "mean", "std_a": "std", "z_a": "z", "mean_b": "meanOther", "std_b": "stdOther", "cc": "cc"}
         return dict((names[key], self._made(device_map)) for key, device_map in made.items())
 
+    # -- from a region of a map to a map: the ordered spread of a mask (no reference counterpart) ------------------------
+    def spread(self, offsets, values, threshold=0.5, below=False, base=None, counters=False):
+        """The raw call (``pdbeda_map_spread`` in include/pdbeda.h has the contract), as a device-made DensityMatrix: every stored voxel gets
+        ``values[t]``, t the first entry of the ordered ``offsets`` table (n x 3 int32: dc, dr, ds) that leads from it to a seed -- a voxel
+        > ``threshold``, or < it with ``below`` -- under the map's own wrap rule, and ``values[n]`` where none does.  With ``base`` (a
+        DensityMatrix on this grid) the voxel is base * value, rounded once.  With ``counters`` the result is (map, {"seeds", "reached",
+        "rows"}): the seeds among the stored voxels, the voxels with a seed in reach, 1 if the table was searched row by row."""
+        made = self._map.spread(offsets, values, threshold, below, None if base is None else base._map, counters)
+        return (self._made(made[0]), made[1]) if counters else self._made(made)
+
+    def dilated(self, radius, threshold=0.5):
+        """1.0 within ``radius`` Angstrom of a voxel > ``threshold``, 0.0 elsewhere."""
+        offsets = spreadTable(self.header, radius)[0]
+        return self.spread(offsets, np.append(np.ones(len(offsets), dtype=np.float32), np.float32(0.0)), threshold)
+
+    def eroded(self, radius, threshold=0.5):
+        """The complement of the dilated complement: 0.0 within ``radius`` Angstrom of a voxel < ``threshold``, 1.0 elsewhere.  What lies outside
+        a cut-out is no background: its faces are not eroded.  (A voxel that EQUALS the threshold is neither mask nor background.)"""
+        offsets = spreadTable(self.header, radius)[0]
+        return self.spread(offsets, np.append(np.zeros(len(offsets), dtype=np.float32), np.float32(1.0)), threshold, below=True)
+
+    def opened(self, radius, threshold=0.5):
+        """Erosion, then dilation: what a ball of ``radius`` fits into."""
+        return self.eroded(radius, threshold).dilated(radius)
+
+    def closed(self, radius, threshold=0.5):
+        """Dilation, then erosion: gaps a ball of ``radius`` does not fit into are filled."""
+        return self.dilated(radius, threshold).eroded(radius)
+
+    def distanceFrom(self, maxDistance, threshold=0.5, below=False, beyond=np.inf):
+        """The distance in Angstrom (float32) from every voxel to the nearest seed within ``maxDistance``: the table's own distances, 0 on a
+        seed, ``beyond`` where none is in reach."""
+        offsets, distance = spreadTable(self.header, maxDistance)
+        return self.spread(offsets, np.append(distance.astype(np.float32), np.float32(beyond)), threshold, below)
+
+    def softMask(self, radius, width, threshold=0.5):
+        """1 within ``radius`` Angstrom of a voxel > ``threshold``, a raised cosine down to 0 at ``radius + width`` (``softEdgeValues``)."""
+        offsets, distance = spreadTable(self.header, float(radius) + float(width))
+        return self.spread(offsets, softEdgeValues(distance, radius, width), threshold)
+
+    def maskedBy(self, seeds, radius=0.0, width=0.0, threshold=0.5):
+        """This map times the soft mask of ``seeds`` (a DensityMatrix on this grid), in ONE device call: ``seeds.softMask`` with this map as
+        the call's ``base``."""
+        offsets, distance = spreadTable(self.header, float(radius) + float(width))
+        return seeds.spread(offsets, softEdgeValues(distance, radius, width), threshold, base=self)
+
+    def atomMask(self, xyz, radii):
+        """1.0 on every stored voxel within ``radii[a]`` of an atom ``xyz[a]``, else 0.0: ``modelDensity`` with one term of amplitude 1 and exponent
+        0 counts the spheres that cover a voxel (exactly: the sums are integers), and the single offset (0, 0, 0) at threshold 0.5 turns the
+        count into a mask.  Nothing wraps: pass the symmetry atoms."""
+        n = len(np.asarray(xyz).reshape(-1, 3))
+        count = self.modelDensity(xyz, np.ones(n), np.zeros(n), radii)
+        return count.spread(np.zeros((1, 3), dtype=np.int32), np.array([1.0, 0.0], dtype=np.float32), 0.5)
+
+    def solventMask(self, xyz, radii, probe=1.11, shrink=0.9):
+        """1.0 in the solvent, 0.0 in the molecule (the flat bulk-solvent model's mask): the atoms grown by ``probe``, complemented, and what is
+        left of the molecule shrunk back by a ball of ``shrink`` -- a voxel is solvent iff an uncovered voxel lies within ``shrink`` of it."""
+        grown = self.atomMask(xyz, np.asarray(radii, dtype=np.float64) + float(probe))
+        offsets = spreadTable(self.header, shrink)[0]
+        return grown.spread(offsets, np.append(np.ones(len(offsets), dtype=np.float32), np.float32(0.0)), 0.5, below=True)
+
+    def maskStats(self, mask, threshold=0.5):
+        """(n, mean, standard deviation) of this map over the voxels of the non-repeating box where ``mask`` > ``threshold`` (``pairMoments``);
+        NaN without a voxel."""
+        n, sa, _, saa, _, _ = self.pairMoments(mask, threshold)
+        if n == 0:
+            return 0, float("nan"), float("nan")
+        mean = sa / n
+        return n, mean, math.sqrt(max(saa / n - mean * mean, 0.0))
+
     # -- from a map to a map on ANOTHER grid: resampling under coordinate operators (no reference counterpart) --------
     def resampled(self, header, ops=None, order=1, mean=False, fill=0.0, base=None, alpha=1.0, coverage=False):
         """This map on the grid of ``header`` (a DensityHeader: another entry's, ``cellHeader`` / ``boxHeader``), as a device-made
@@ -1249,6 +1319,44 @@ def neighbourOffsets(header, maxDistance):
                          (maxDistance, len(cand), NEAREST_MAX_OFFSETS, NEAREST_MAX_COMPONENT))
     order = np.lexsort((cand[:, 2], cand[:, 1], cand[:, 0], d2))
     return np.ascontiguousarray(cand[order], dtype=np.int32), np.ascontiguousarray(distance[order])
+
+
+SPREAD_MAX_OFFSETS, SPREAD_MAX_REACH = _native.SPREAD_MAX_OFFSETS, _native.SPREAD_MAX_REACH      # PDBEDA_SPREAD_MAX_OFFSETS / _REACH of include/pdbeda.h
+
+# Radii in Angstrom by element for the masks of ``DensityMatrix.atomMask`` / ``solventMask`` (van der Waals radii after Bondi, J. Phys. Chem. 68
+# (1964) 441, hydrogen as the flat bulk-solvent model takes it); ``maskRadii`` gives any other element MASK_VDW_DEFAULT.
+MASK_VDW = {"H": 1.2, "C": 1.7, "N": 1.55, "O": 1.52, "F": 1.47, "P": 1.8, "S": 1.8, "CL": 1.75, "SE": 1.9, "BR": 1.85, "I": 1.98,
+            "NA": 2.27, "MG": 1.73, "K": 2.75, "CA": 2.31, "ZN": 1.39, "FE": 1.8, "MN": 1.8, "CU": 1.4, "NI": 1.63}
+MASK_VDW_DEFAULT = 1.8
+
+
+def maskRadii(elements):
+    """MASK_VDW for a sequence of element symbols (any case, blanks ignored), MASK_VDW_DEFAULT for the others: float64 (n,)."""
+    return np.array([MASK_VDW.get(str(e).strip().upper(), MASK_VDW_DEFAULT) for e in elements], dtype=np.float64)
+
+
+def spreadTable(header, maxDistance):
+    """``neighbourOffsets`` under the limits of ``pdbeda_map_spread``: ValueError for a component beyond +-32 or more than 16384 offsets.  In
+    ascending distance a ball is searched row by row (every row of it falls to one minimum along dc and rises behind it)."""
+    offsets, distance = neighbourOffsets(header, maxDistance)
+    if len(offsets) > SPREAD_MAX_OFFSETS or (len(offsets) and int(np.abs(offsets).max()) > SPREAD_MAX_REACH):
+        raise ValueError("maxDistance = %g A gives %d offsets of up to %d voxels (a spread takes %d of +-%d voxels)" %
+                         (float(maxDistance), len(offsets), int(np.abs(offsets).max()), SPREAD_MAX_OFFSETS, SPREAD_MAX_REACH))
+    return offsets, distance
+
+
+def softEdgeValues(distance, radius, width):
+    """The values of a soft-edged mask for a table's distances: float32 (n + 1,) -- 1 up to ``radius``, the raised cosine
+    0.5 (1 + cos(pi (d - radius) / width)) down to 0 at ``radius + width``, and a last entry of 0 for no seed in reach."""
+    d = np.asarray(distance, dtype=np.float64).reshape(-1)
+    radius, width = float(radius), float(width)
+    if not (radius >= 0 and width >= 0):
+        raise ValueError("radius and width must be non-negative")
+    out = np.where(d <= radius, 1.0, 0.0)
+    if width > 0:
+        edge = (d > radius) & (d < radius + width)
+        out[edge] = 0.5 * (1.0 + np.cos(np.pi * (d[edge] - radius) / width))
+    return np.append(out, 0.0).astype(np.float32)
 
 
 class _DeviceBlobSegment(object):

@@ -44,6 +44,7 @@
 #include "pdbeda_profiles.h"
 #include "pdbeda_qscore.h"
 #include "pdbeda_resample.h"
+#include "pdbeda_spread.h"
 
 using namespace pdbeda;
 
@@ -3767,6 +3768,96 @@ extern "C" int pdbeda_map_local_stats(pdbeda_map *a, pdbeda_map *b, const double
     if (rc) return rc;
     for (int k = 0; k < 6; ++k)
         if (made[k].m) made[k].publish(want[k]);
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// From a region of a map to a map: the ordered spread of a mask (no reference counterpart; the contract: include/pdbeda.h, the plan: pdbeda_spreadplan.h)
+// ------------------------------------------------------------------------------------
+// A workgroup may take more dynamic LDS than the 64 KiB a kernel gets unasked: told to the runtime once per kernel and process.
+template <bool ROWS>
+static hipError_t spread_lds_allowance() {
+    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spread<ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS_BUDGET);
+    return e;
+}
+
+// The launch graph: the table (row records and ranks, or packed offsets) and the values in one row of scratch; k_spread<rows or walk> over the tiles into the
+// new map and the tiles' count slots; k_spread_fold; the two counts.  One wait.  PDBEDA_SPREAD_ROWS=0 (A/B switch, read at every call): the ordered walk for
+// every table.  Equal results to the bit.
+extern "C" int pdbeda_map_spread(pdbeda_map *map, float threshold, uint32_t flags, const int32_t *offsets, int64_t n_offsets, const float *values, pdbeda_map *base,
+                                 pdbeda_map **out, int64_t counters[3]) {
+    if (!map || !offsets || !values || !out) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = map->ctx;
+    const Geom &g = map->geom;
+    int reach[3];
+    switch (spread_check(offsets, n_offsets, std::isnan(threshold), flags, PDBEDA_SPREAD_BELOW, g.ncrs, g.crs_interval, reach)) {
+    case SPREAD_COUNT: return fail(ctx, PDBEDA_ERR_ARGUMENT, "map spread: %lld offsets are outside 1 .. %d", (long long)n_offsets, PDBEDA_SPREAD_MAX_OFFSETS);
+    case SPREAD_REACH: return fail(ctx, PDBEDA_ERR_ARGUMENT, "map spread: an offset reaches beyond +-%d voxels", PDBEDA_SPREAD_MAX_REACH);
+    case SPREAD_THRESHOLD: return fail(ctx, PDBEDA_ERR_ARGUMENT, "map spread: the threshold is NaN");
+    case SPREAD_FLAG: return fail(ctx, PDBEDA_ERR_ARGUMENT, "map spread: unknown flag 0x%x", flags);
+    case SPREAD_AXIS: return fail(ctx, PDBEDA_ERR_ARGUMENT, "map spread: the map is empty, or an axis has 2^30 indices or more");
+    default: break;
+    }
+    if (base)
+        if (int rc = same_grid(ctx, g, map->n_vox, base)) return rc;
+    std::vector<SpreadRow> rows;
+    std::vector<uint16_t> ranks;
+    std::vector<uint32_t> packed;
+    const bool by_rows = env_unless_0("PDBEDA_SPREAD_ROWS") && spread_compile_rows(offsets, n_offsets, &rows, &ranks);
+    if (!by_rows) {
+        rows.clear(); ranks.clear();
+        packed.resize((size_t)n_offsets);
+        for (int64_t t = 0; t < n_offsets; ++t) packed[(size_t)t] = spread_pack(offsets[3 * t], offsets[3 * t + 1], offsets[3 * t + 2]);
+    }
+    const SpreadPlan plan = plan_spread(g.ncrs, reach, (int)ranks.size());
+    if (plan.refusal != SPREAD_OK || plan.lds_total > SP_LDS_BUDGET || map->n_vox <= 0) return fail(ctx, PDBEDA_ERR_ARGUMENT, "map spread: the map is empty or too large for one launch");
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (plan.lds_total > 64 * 1024) HIP_TRY(ctx, by_rows ? spread_lds_allowance<true>() : spread_lds_allowance<false>());
+    MadeMap made;
+    if (int rc = made.make_like("map spread", map)) return rc;
+    SpreadRow *d_rows = nullptr;
+    uint16_t *d_ranks = nullptr;
+    uint32_t *d_packed = nullptr, *d_counts = nullptr;
+    float *d_values = nullptr;
+    int64_t *d_res = nullptr;
+    int64_t res[2] = {0, 0};
+    const int rc = with_scratch(ctx, "map spread", [&](Carver &cv) {
+        cv.take(d_rows, rows.size());
+        cv.take(d_ranks, ranks.size());
+        cv.take(d_packed, packed.size());
+        cv.take(d_values, (size_t)n_offsets + 1);
+        cv.take(d_counts, 2 * (size_t)plan.n_tiles);
+        cv.take(d_res, 2);
+    }, [&]() -> int {
+        HIP_TRY(ctx, made.geometry_up());
+        const H2DItem in[4] = {{d_rows, rows.data(), sizeof(SpreadRow) * rows.size()}, {d_ranks, ranks.data(), 2 * ranks.size()}, {d_packed, packed.data(), 4 * packed.size()},
+                               {d_values, values, 4 * ((size_t)n_offsets + 1)}};
+        HIP_TRY(ctx, h2d_row(ctx, in, 4));
+        SpreadArgs a;
+        memset(&a, 0, sizeof a);
+        a.x = map->dens; a.base = base ? base->dens : nullptr; a.out = made.dens;
+        a.nc = g.ncrs[0]; a.nr = g.ncrs[1]; a.ns = g.ncrs[2];
+        a.ic = g.crs_interval[0]; a.ir = g.crs_interval[1]; a.is = g.crs_interval[2];
+        a.threshold = threshold; a.below = (flags & PDBEDA_SPREAD_BELOW) ? 1 : 0;
+        a.reach_c = reach[0]; a.reach_r = reach[1]; a.reach_s = reach[2];
+        a.tile_r = plan.tile_r; a.tile_s = plan.tile_s; a.words = plan.words; a.box_r = plan.box_r; a.box_s = plan.box_s; a.n_words = plan.n_words;
+        a.tiles_c = plan.tiles_c; a.tiles_r = plan.tiles_r;
+        a.rows = d_rows; a.n_rows = (int32_t)rows.size(); a.ranks = d_ranks; a.n_ranks = (int32_t)ranks.size();
+        a.packed = d_packed; a.n_off = (int32_t)n_offsets; a.values = d_values; a.counts = d_counts;
+        {
+            PROF(ctx, by_rows ? "k_spread_rows" : "k_spread_walk");
+            if (by_rows) hipLaunchKernelGGL(k_spread<true>, dim3((unsigned)plan.n_tiles), dim3(256), (size_t)plan.lds_total, ctx->stream, a);
+            else hipLaunchKernelGGL(k_spread<false>, dim3((unsigned)plan.n_tiles), dim3(256), (size_t)plan.lds_total, ctx->stream, a);
+        }
+        { PROF(ctx, "k_spread_fold"); hipLaunchKernelGGL(k_spread_fold, dim3(1), dim3(256), 0, ctx->stream, d_counts, plan.n_tiles, d_res); }
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, d2h(ctx, res, d_res, 16));
+        return 0;
+    });
+    if (rc) return rc;
+    if (counters) { counters[0] = res[0]; counters[1] = res[1]; counters[2] = by_rows ? 1 : 0; }
+    made.publish(out);
     return PDBEDA_OK;
 }
 

@@ -1797,6 +1797,13 @@ class DensityAnalysis(object):
         amp, expo, bEff = ccp4.gaussianAtomTerms(electrons[keep], cols.bfactor[keep], cols.occupancy[keep], blur=modelBlur)
         radii = ccp4.modelRadii(bEff, modelSigmas)
         xyz = np.asarray(cols.coord, dtype=np.float64).reshape(-1, 3)[keep]
+        copies, rows = self._cellCopies(header, xyz, float(radii.max()) if len(radii) else 0.0)
+        return copies, amp[rows], expo[rows], radii[rows]
+
+    def _cellCopies(self, header, xyz, reach):
+        """(xyz of the copies, the row of ``xyz`` each came from): the atoms ``xyz`` under the identity and the distinct operators of the header's
+        ``rotationMats``, each brought into the unit cell of ``header`` by whole lattice translations, and its 26 neighbours where a sphere of
+        ``reach`` Angstrom around it crosses a face of the cell."""
         ops, seen = [], set()
         for op in [ccp4.identityOperator()] + [ccp4._operator(m) for m in self.pdbObj.header.rotationMats]:
             key = tuple(np.round(op.reshape(-1), 5).tolist())
@@ -1804,7 +1811,7 @@ class DensityAnalysis(object):
                 seen.add(key)
                 ops.append(op)
         ortho, deortho = np.asarray(header.orthoMat, dtype=np.float64), np.asarray(header.deOrthoMat, dtype=np.float64)
-        pad = float(radii.max()) * np.sqrt((deortho ** 2).sum(axis=1)) if len(radii) else np.zeros(3)      # the sphere's reach in fractional units
+        pad = float(reach) * np.sqrt((deortho ** 2).sum(axis=1)) if len(xyz) else np.zeros(3)      # the sphere's reach in fractional units
         shifts = np.array([(i, j, k) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1)], dtype=np.float64)
         out_xyz, out_row = [], []
         for op in ops:
@@ -1816,7 +1823,7 @@ class DensityAnalysis(object):
                 out_xyz.append(f[inside].dot(ortho.T))
                 out_row.append(np.nonzero(inside)[0])
         rows = np.concatenate(out_row) if out_row else np.zeros(0, dtype=np.int64)
-        return (np.concatenate(out_xyz) if out_xyz else np.zeros((0, 3))), amp[rows], expo[rows], radii[rows]
+        return (np.concatenate(out_xyz) if out_xyz else np.zeros((0, 3))), rows
 
     def _fourierMaps(self):
         """(observed, model): the 2Fo-Fc map over the whole unit cell -- ``expandedDensityObj`` where the cell's sampling can be transformed,
@@ -1883,3 +1890,154 @@ class DensityAnalysis(object):
         clean = lambda v: [None if x != x else float(x) for x in np.asarray(v, dtype=np.float64).tolist()]
         return self._rows(list(range(len(t["n"]))), clean(t["d_max"]), clean(t["d_min"]), [int(v) for v in t["n"]], clean(t["power"]), clean(t["powerOther"]), clean(t["fsc"]),
                           clean(t["phaseCosine"]), clean(t["scale"]))
+
+    # ---- masks of the whole cell: molecule, solvent, and the flat bulk-solvent model (no reference counterpart) ----
+    def _maskAtoms(self, header, extra=0.0):
+        """(xyz, radii) of every atom copy whose mask sphere (``ccp4.MASK_VDW`` by ``atom.element``, plus ``extra``) reaches the unit cell of
+        ``header``: the atoms ``_cellAtoms`` keeps, copied the same way."""
+        _requireParams()
+        cols = _structure.columns(self.biopdbObj)
+        names = cols.pair_names
+        electrons = _pairTables(names, max(len(names), 1))["electrons"][cols.pair_of_atom] if len(cols.coord) else np.zeros(0)
+        keep = ~np.isnan(electrons) & (cols.occupancy != 0) if len(cols.coord) else np.zeros(0, dtype=bool)
+        radii = ccp4.maskRadii([getattr(atom, "element", "") or "" for atom in cols.atoms])[keep] if len(cols.coord) else np.zeros(0)
+        xyz = np.asarray(cols.coord, dtype=np.float64).reshape(-1, 3)[keep]
+        copies, rows = self._cellCopies(header, xyz, (float(radii.max()) if len(radii) else 0.0) + float(extra))
+        return copies, radii[rows]
+
+    @property
+    def moleculeMaskObj(self):
+        """1.0 inside the van der Waals spheres of the model's atoms and their symmetry mates, 0.0 outside, on the whole-cell grid of
+        ``_fourierMaps`` (``DensityMatrix.atomMask``); resident."""
+        if "moleculeMask" not in self._local:
+            observed = self._fourierMaps()[0]
+            xyz, radii = self._maskAtoms(observed.header)
+            self._local["moleculeMask"] = observed.atomMask(xyz, radii)
+        return self._local["moleculeMask"]
+
+    @property
+    def solventMaskObj(self):
+        """1.0 in the bulk solvent of the whole cell, 0.0 in the molecule (``DensityMatrix.solventMask`` with the module's ``maskProbe`` and
+        ``maskShrink``); resident."""
+        if "solventMask" not in self._local:
+            observed = self._fourierMaps()[0]
+            xyz, radii = self._maskAtoms(observed.header, maskProbe)
+            self._local["solventMask"] = observed.solventMask(xyz, radii, probe=maskProbe, shrink=maskShrink)
+        return self._local["solventMask"]
+
+    def _wholeCellDiff(self):
+        """The Fo-Fc map on the grid of ``_fourierMaps``."""
+        if "fourierDiff" not in self._local:
+            header = self.densityObj.header
+            if all(ccp4.isFourierSize(n) for n in header.crsInterval):
+                self._local["fourierDiff"] = self.expandedDiffDensityObj
+            else:
+                self._local["fourierDiff"] = self.diffDensityObj.symmetryExpanded([np.asarray(m, dtype=np.float64) for m in self.pdbObj.header.rotationMats],
+                                                                                  header=ccp4.fourierHeader(header), order=3)
+        return self._local["fourierDiff"]
+
+    def maskSummary(self):
+        """The solvent fraction of the cell, mean and standard deviation of the 2Fo-Fc and Fo-Fc maps in the solvent and in the protein (the
+        complement of the solvent mask), and ``solvent_noise``: the Fo-Fc sigma of the solvent, a noise estimate from where there is no model --
+        ``partitionSummary``'s ``unowned_std`` asks the same of a distance to atom centres."""
+        solvent = self.solventMaskObj
+        protein = solvent.spread(np.zeros((1, 3), dtype=np.int32), np.array([1.0, 0.0], dtype=np.float32), 0.5, below=True)
+        observed, diff = self._fourierMaps()[0], self._wholeCellDiff()
+        n_solvent = observed.maskStats(solvent)[0]
+        n_protein = observed.maskStats(protein)[0]
+        out = {"cell_voxels": n_solvent + n_protein, "solvent_voxels": n_solvent, "solvent_fraction": n_solvent / max(n_solvent + n_protein, 1)}
+        for region, mask in (("solvent", solvent), ("protein", protein)):
+            for name, dm in (("density", observed), ("diff", diff)):
+                _, mean, std = dm.maskStats(mask)
+                out["%s_%s_mean" % (region, name)], out["%s_%s_std" % (region, name)] = mean, std
+        out["solvent_noise"] = out["solvent_diff_std"]
+        return out
+
+    def maskedModelShellTable(self, nShells=20, width=3.0):
+        """``modelShellTable`` with both whole-cell maps multiplied by the soft molecule mask: 1 inside the molecule, a raised cosine of
+        ``width`` Angstrom outside it (``DensityMatrix.maskedBy``) -- the solvent region, where the model has nothing, stays out of the FSC."""
+        key = ("maskedShells", int(nShells), float(width))
+        if key not in self._local:
+            observed, model = self._fourierMaps()
+            mask = self.moleculeMaskObj
+            self._local[key] = observed.maskedBy(mask, 0.0, width).shellStats(model.maskedBy(mask, 0.0, width), nShells)
+        return self._local[key]
+
+    def bulkSolventFit(self, bGrid=(20, 35, 50, 65, 80), nShells=20):
+        """The flat bulk-solvent model Fo ~ a Fc + b S_B fitted over all shells: S_B is the spectrum of the solvent mask under
+        ``ccp4.bFactorTable(B)``; for every B of ``bGrid`` the three pairwise shell sums of (Fo, Fc), (Fo, S_B) and (Fc, S_B) give the 2 x 2
+        normal equations and the residual (``flatSolventFit``: host arithmetic on shell sums), and the B of the least residual wins.  A dict
+        ``k_sol`` = b / a, ``b_sol``, ``scale`` = a, ``residual``, ``residuals`` (one per B), ``fsc_before`` / ``fsc_after`` per shell and the
+        shells' ``d_max`` / ``d_min``.  Fo is the 2Fo-Fc map of the whole cell, Fc the model of ``_fourierMaps``."""
+        key = ("bulkSolvent", tuple(float(b) for b in bGrid), int(nShells))
+        if key not in self._local:
+            observed, model = self._fourierMaps()
+            fo, fc, s = observed.fourier(), model.fourier(), self.solventMaskObj.fourier()
+            edges = ccp4.shellEdges(observed.header, nShells)
+            s2Max = ccp4.maxS2(observed.header)
+            base = fo.shells(fc, edges=edges)
+            oo, cc, oc = base["sums"][:, 0], base["sums"][:, 1], base["sums"][:, 2]
+            best, residuals = None, []
+            for B in key[1]:
+                sb = s.scaled(ccp4.bFactorTable(B, s2Max), s2Max)
+                with_fo, with_fc = fo.shells(sb, edges=edges)["sums"], fc.shells(sb, edges=edges)["sums"]
+                fit = flatSolventFit(oo, cc, with_fo[:, 1], oc, with_fo[:, 2], with_fc[:, 2])
+                residuals.append(fit["residual"])
+                if best is None or fit["residual"] < best[1]["residual"]:
+                    best = (B, fit)
+            B, fit = best
+            self._local[key] = {"k_sol": fit["kSol"], "b_sol": B, "scale": fit["scale"], "residual": fit["residual"], "residuals": residuals,
+                                "fsc_before": fit["fscBefore"], "fsc_after": fit["fscAfter"], "d_max": base["d_max"], "d_min": base["d_min"], "n": base["n"]}
+        return self._local[key]
+
+    def modelWithSolventObj(self, bGrid=(20, 35, 50, 65, 80), nShells=20):
+        """The model plus the fitted bulk solvent on the whole-cell grid: combine(model, inverse(S_B), k_sol); resident."""
+        fit = self.bulkSolventFit(bGrid, nShells)
+        key = ("modelWithSolvent", fit["b_sol"], fit["k_sol"])
+        if key not in self._local:
+            observed, model = self._fourierMaps()
+            s2Max = ccp4.maxS2(observed.header)
+            smooth = self.solventMaskObj.fourier().scale(ccp4.bFactorTable(fit["b_sol"], s2Max), s2Max).toMap()
+            self._local[key] = ccp4.DensityMatrix.fromDeviceMap(model.header, model.origin, type(model._map).combine(model._map, smooth._map, fit["k_sol"]), model.pdbid, model._ctx)
+        return self._local[key]
+
+    def solventShellTable(self, nShells=20):
+        """``modelShellTable`` against ``modelWithSolventObj()``."""
+        key = ("solventShells", int(nShells))
+        if key not in self._local:
+            self._local[key] = self._fourierMaps()[0].shellStats(self.modelWithSolventObj(nShells=nShells), nShells)
+        return self._local[key]
+
+    maskShellHeader = ["shell", "d_max", "d_min", "n", "fsc", "fsc_masked", "fsc_with_solvent"]
+
+    def calculateMaskShells(self, nShells=20):
+        """One row per resolution shell (``maskShellHeader``): the map-model FSC without a mask, inside the soft molecule mask, and with the fitted
+        bulk solvent added to the model; None where a value is undefined."""
+        plain, masked, solvent = self.modelShellTable(nShells), self.maskedModelShellTable(nShells), self.solventShellTable(nShells)
+        clean = lambda v: [None if x != x else float(x) for x in np.asarray(v, dtype=np.float64).tolist()]
+        return self._rows(list(range(len(plain["n"]))), clean(plain["d_max"]), clean(plain["d_min"]), [int(v) for v in plain["n"]], clean(plain["fsc"]), clean(masked["fsc"]),
+                          clean(solvent["fsc"]))
+
+
+maskProbe = 1.11         # DensityMatrix.solventMask's defaults: the atoms are grown by the probe, the molecule shrunk back by a ball
+maskShrink = 0.9
+
+
+def flatSolventFit(oo, cc, ss, oc, os_, cs):
+    """The least-squares fit Fo ~ a Fc + b S over all shells from per-shell sums: ``oo``, ``cc``, ``ss`` = sum |Fo|^2, |Fc|^2, |S|^2 and ``oc``,
+    ``os_``, ``cs`` = Re sum Fo Fc*, Fo S*, Fc S*.  The 2 x 2 normal equations [[CC, CS], [CS, SS]] (a, b) = (OC, OS) over the totals; where S
+    vanishes or is parallel to Fc, a scale alone (b = 0).  A dict ``scale`` = a, ``b``, ``kSol`` = b / a, ``residual`` = sum |Fo - a Fc - b S|^2
+    from the same sums, and per shell ``fscBefore`` (Fo against Fc) and ``fscAfter`` (Fo against a Fc + b S); NaN where a denominator is 0."""
+    oo, cc, ss, oc, os_, cs = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (oo, cc, ss, oc, os_, cs))
+    OO, CC, SS, OC, OS, CS = (math.fsum(v.tolist()) for v in (oo, cc, ss, oc, os_, cs))
+    det = CC * SS - CS * CS
+    if SS > 0 and det > 1e-12 * CC * SS:
+        a, b = (OC * SS - OS * CS) / det, (OS * CC - OC * CS) / det
+    else:
+        a, b = (OC / CC if CC > 0 else float("nan")), 0.0
+    residual = OO - 2.0 * a * OC - 2.0 * b * OS + a * a * CC + 2.0 * a * b * CS + b * b * SS
+    with np.errstate(divide="ignore", invalid="ignore"):
+        before = np.where(oo * cc > 0, oc / np.sqrt(oo * cc), np.nan)
+        fitted = a * a * cc + 2.0 * a * b * cs + b * b * ss
+        after = np.where(oo * fitted > 0, (a * oc + b * os_) / np.sqrt(oo * fitted), np.nan)
+    return {"scale": a, "b": b, "kSol": b / a if a else float("nan"), "residual": residual, "fscBefore": before, "fscAfter": after}

@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore", "model", "local", "fourier")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore", "model", "local", "fourier", "mask")
 
 
 def numpyConverter(obj):
@@ -142,6 +142,15 @@ def _fourierSummaryTable(analyzer, o):
     return [[summary[name] for name in _FOURIER_SUMMARY]]
 
 
+def _maskSummaryTable(analyzer, o):
+    summary = dict(analyzer.maskSummary())
+    fit = analyzer.bulkSolventFit(nShells=o["shells"])
+    summary.update({"k_sol": fit["k_sol"], "b_sol": fit["b_sol"], "solvent_scale": fit["scale"], "solvent_residual": fit["residual"]})
+    return [[summary[name] for name in _MASK_SUMMARY]]
+
+
+_MASK_SUMMARY = ["cell_voxels", "solvent_voxels", "solvent_fraction"] + ["%s_%s_%s" % (region, name, what) for region in ("solvent", "protein") for name in ("density", "diff")
+                                                                       for what in ("mean", "std")] + ["solvent_noise", "k_sol", "b_sol", "solvent_scale", "solvent_residual"]
 _FOURIER_SUMMARY = ["grid_c", "grid_r", "grid_s", "d_min", "num_shells", "fsc_05_resolution", "fsc_0143_resolution", "overall_fsc", "overall_scale"]
 _LOCAL_SUMMARY = ["window_sigma", "window_truncate", "radius_c", "radius_r", "radius_s", "num_local_green_blobs", "num_local_red_blobs", "num_green_blobs", "num_red_blobs",
                   "median_atom_local_cc", "min_atom_local_cc"]
@@ -207,6 +216,9 @@ TABLES = {
     # (no reference counterpart: the whole-cell 2Fo-Fc map against the model in reciprocal space; ``shells`` is the number of resolution shells)
     ("fourier", "shell"): (lambda an: _DA.fourierShellHeader, lambda an, o: an.calculateFourierShells(o["shells"])),
     ("fourier", "summary"): (lambda an: list(_FOURIER_SUMMARY), _fourierSummaryTable),
+    # (no reference counterpart: the whole cell divided into molecule and solvent, the flat bulk-solvent fit; ``shells`` is the number of resolution shells)
+    ("mask", "shell"): (lambda an: _DA.maskShellHeader, lambda an, o: an.calculateMaskShells(o["shells"])),
+    ("mask", "summary"): (lambda an: list(_MASK_SUMMARY), _maskSummaryTable),
     ("statistics", "residue"): (lambda an: an.residueMetricsHeaderList, lambda an, o: an.residueMetrics()),
     ("statistics", "atom"): (lambda an: an.atomMetricsHeaderList, lambda an, o: _plainColumns(an.atomMetrics(), **_SYM)),
 }
@@ -216,9 +228,9 @@ def rows(analyzer, mode, level="atom", radius=None, numSD=None, type="", atomMas
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore | model | local | fourier;  level: atom | residue | domain | symmetry-atom
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore | model | local | fourier | mask;  level: atom | residue | domain | symmetry-atom
     (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak, basin, shape and dipole) | atom-type (profile) | summary | blob
-    (partition) | summary (qscore: atom | residue | summary, no other option applies; model: atom | residue | summary, ``radius`` is the sphere's, by default the one of the statistics mode; local: atom | residue | summary under the module's window, no other option applies; fourier: shell | summary, ``shells`` resolution shells);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
+    (partition) | summary (qscore: atom | residue | summary, no other option applies; model: atom | residue | summary, ``radius`` is the sphere's, by default the one of the statistics mode; local: atom | residue | summary under the module's window, no other option applies; fourier: shell | summary, ``shells`` resolution shells; mask: shell | summary, ``shells`` resolution shells);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
     (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
     maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default);  dipole: always the fused green
     and red lists (numSD default 3.0), ``radius`` is the largest gap between the two blobs when given (else 2.5 A);  radius default 3.5 elsewhere."""
