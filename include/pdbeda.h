@@ -513,6 +513,46 @@ int pdbeda_model_density(pdbeda_map *like,
  * Synchronous; either output may be NULL. */
 int pdbeda_map_pair_moments(pdbeda_map *a, pdbeda_map *b, float b_floor, int64_t *n, double sums[5]);  /* Sa, Sb, Saa, Sbb, Sab */
 
+/* ---- from a map back to the atoms: the adjoint of the model density ------------------------- */
+/* Per atom and Gaussian term the sums of a weight map against the atom's own Gaussian, against the Gaussian times the offset vector and
+ * against the Gaussian times the squared distance (no reference counterpart).  With the weight map a residual obs - s * calc - o these are
+ * the derivatives of the least-squares map-model target with respect to occupancy, position and B: what real-space refinement needs.
+ * The pair set is EXACTLY pdbeda_model_density's: p = crs2xyzCoord(v); dx = p.x - x_a, likewise dy, dz; d2 = (dx*dx + dy*dy) + dz*dz in
+ * unfused fp64; voxel v pairs with atom a iff sqrt(d2) <= (double)radii[a] (IEEE sqrt, inclusive).  Nothing wraps: the caller passes
+ * the symmetry images, as for the model.
+ * Domain: ALL stored voxels ncrs, the model's domain.  Under PDBEDA_MOMENTS_UNIQUE_BOX only the non-repeating box header.uniqueNcrs,
+ * the domain of pdbeda_map_pair_moments: the sums are then derivatives of exactly the target that the correlation fits.
+ * Terms: for atom a, term j, voxel v: e = exp(-(expo[a][j] * d2)) with the device library's fp64 exp, one rounding for the product
+ * inside, as in the model; t0 = (double)w(v) * e; the five terms are t0, t0*dx, t0*dy, t0*dz, t0*d2, each product rounded once.
+ * moments[a][j] = {M0, Mx, My, Mz, M2}, their sums over the atom's pairs.  Amplitudes do not enter: the sums are linear in them and
+ * the host multiplies.  expo >= 0 (0: the plain moments of the weight inside the sphere).
+ * Order independence: every term is rounded ONCE, half to even, to the quantum 2^-S and added as a 64-bit integer; an output is
+ * (double)sum * 2^-S.  S = 61 - e with B < 2^e (the rule of every integer sum of the library; 40 where B is 0) for the bound B =
+ * max|w| * max(1, r_max^2) * max(V_max, 2^22), evaluated by the host in fp64 in that order: max|w| the largest |w| over the STORED
+ * map (one fixed-order reduction, cached with the map until pdbeda_map_invalidate), r_max = (double) of the largest radius, V_max
+ * the voxels of the largest box (below).  Two calls agree to the bit; so do calls with the atoms permuted, rows re-mapped; and while S
+ * is the same the result of an atom does not depend on which other atoms are in the call (only r_max and V_max tie them).
+ * The box: the host covers every sphere with a box of crs indices -- half-width radius * |row k of the xyz -> crs matrix| along crs
+ * axis k, which covers on any cell, skewed ones included, widened by 2^-30 of the magnitudes involved so that no rounding loses a
+ * voxel -- and clips it to the domain.  The box only bounds the search: membership is the sphere test above.
+ * n_voxels[a] = the pairs of atom a.  An atom that reaches no voxel of the domain has n_voxels = 0 and moments of exactly +0.0.
+ * counters = {S, V_max, the atoms whose covering box the domain clipped (atoms wholly outside it included)}.
+ * A weight map with non-finite voxels is refused with PDBEDA_ERR_ARGUMENT, as the labelling calls refuse it.  PDBEDA_ERR_ARGUMENT
+ * before any launch: n_terms outside 1 .. PDBEDA_MODEL_MAX_TERMS, an unknown flag, n_atoms >= 2^31, a non-finite coordinate or
+ * exponent, a negative exponent, a radius that is not finite or <= 0, a radius of 2^29 grid steps or more along a crs axis, a clipped
+ * box of 2^31 voxels or more.  n_atoms == 0 succeeds and touches nothing.  Synchronous; a failing call leaves the context usable and
+ * the outputs untouched. */
+#define PDBEDA_MOMENTS_UNIQUE_BOX 1u
+int pdbeda_atom_moments(pdbeda_map *weight,
+                        const double *xyz, int64_t n_atoms,
+                        int32_t n_terms,                    /* 1 .. PDBEDA_MODEL_MAX_TERMS */
+                        const double *expo,                 /* [n_atoms][n_terms], >= 0 */
+                        const float *radii,                 /* [n_atoms] */
+                        uint32_t flags,
+                        double *moments,                    /* [n_atoms][n_terms][5]: M0, Mx, My, Mz, M2 */
+                        int32_t *n_voxels,                  /* [n_atoms] */
+                        int64_t counters[3]);               /* any output may be NULL */
+
 /* ---- from a map to a map through a neighbourhood: separable filters, local statistics ---- */
 /* A separable filter of a resident map (no reference counterpart; every other map-to-map call is voxel-wise).
  * Output and domain: *out is a NEW map owned by the library on the geometry of `map` -- ownership and lifetime are those of

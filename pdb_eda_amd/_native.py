@@ -124,6 +124,7 @@ _SIGS = {
     "pdbeda_atom_qscores": (C.c_int, [_p, _p, _i64, _p, _i64, C.c_float, C.c_int32, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p]),
     "pdbeda_model_density": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, _p, C.POINTER(_p), _p]),
     "pdbeda_map_pair_moments": (C.c_int, [_p, _p, C.c_float, C.POINTER(_i64), _p]),
+    "pdbeda_atom_moments": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, C.c_uint32, _p, _p, _p]),
     "pdbeda_map_filter": (C.c_int, [_p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_uint32, C.POINTER(_p)]),
     "pdbeda_map_local_stats": (C.c_int, [_p, _p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_double, _p, _p, _p, _p, _p, _p]),
     "pdbeda_map_spread": (C.c_int, [_p, C.c_float, C.c_uint32, _p, _i64, _p, _p, C.POINTER(_p), _p]),
@@ -538,6 +539,7 @@ FILTER_RENORMALIZE = 1           # PDBEDA_FILTER_RENORMALIZE
 SPREAD_MAX_OFFSETS = 16384       # PDBEDA_SPREAD_MAX_OFFSETS
 SPREAD_MAX_REACH = 32            # PDBEDA_SPREAD_MAX_REACH
 SPREAD_BELOW = 1                 # PDBEDA_SPREAD_BELOW
+MOMENTS_UNIQUE_BOX = 1           # PDBEDA_MOMENTS_UNIQUE_BOX
 LOCAL_STATS_OUTPUTS = ("mean_a", "std_a", "z_a", "mean_b", "std_b", "cc")      # the output pointers of pdbeda_map_local_stats, in order
 
 
@@ -705,6 +707,25 @@ class DeviceMap(object):
         self._ctx.check(self._ctx._lib.pdbeda_map_pair_moments(self._h, other._h, C.c_float(-np.inf if floor is None else floor), C.byref(n), _ptr(sums)),
                         "pdbeda_map_pair_moments")
         return int(n.value), sums
+
+    def atom_moments(self, xyz, expo, radii, unique_box=False):
+        """pdbeda_atom_moments: the adjoint of ``model_density`` with this map as the weight -- per atom and term the sums M0, Mx, My, Mz, M2 of
+        w e, w e dx, w e dy, w e dz, w e d^2 (e = exp(-expo d^2)) over the voxels within ``radii[a]``, over all stored voxels or, with
+        ``unique_box``, over the non-repeating box.  ``expo`` is (n,) or (n, n_terms).  A dict: ``moments`` (n, n_terms, 5), ``nVoxels`` (n,)
+        int32 and ``counters`` {"shift", "maxBoxVoxels", "clippedAtoms"}."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        na = len(xyz)
+        expo = np.ascontiguousarray(expo, dtype=np.float64).reshape(na, -1) if na else np.zeros((0, 1))
+        radii = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+        if len(radii) != na:
+            raise ValueError("radii must have one value per atom")
+        moments = np.zeros((na, expo.shape[1], 5), dtype=np.float64)
+        n_voxels = np.zeros(na, dtype=np.int32)
+        ctr = np.zeros(3, dtype=np.int64)
+        self._ctx.check(self._ctx._lib.pdbeda_atom_moments(self._h, _ptr(xyz) if na else None, na, int(expo.shape[1]), _ptr(expo) if na else None, _ptr(radii) if na else None,
+                                                           MOMENTS_UNIQUE_BOX if unique_box else 0, _ptr(moments) if na else None, _ptr(n_voxels) if na else None, _ptr(ctr)),
+                        "pdbeda_atom_moments")
+        return {"moments": moments, "nVoxels": n_voxels, "counters": {"shift": int(ctr[0]), "maxBoxVoxels": int(ctr[1]), "clippedAtoms": int(ctr[2])}}
 
     @classmethod
     def _made(cls, like, h):

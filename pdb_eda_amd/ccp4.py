@@ -157,6 +157,77 @@ def modelRadii(bEff, nSigma=MODEL_N_SIGMA):
     return (float(nSigma) * np.sqrt(np.asarray(bEff, dtype=np.float64) / (8.0 * np.pi ** 2))).astype(np.float32)
 
 
+def gaussianAtomGradients(moments, electrons, bfactors, occupancies, blur=0.0, minB=MODEL_MIN_B):
+    """The chain rule of ``gaussianAtomTerms``' one-Gaussian model on the sums of ``DensityMatrix.atomMoments``: the derivatives of
+    F = sum_v w(v) rho_a(v) with respect to the atom's position, B and occupancy, as a dict ``dXyz`` (n, 3), ``dB`` and ``dOcc`` (n,).
+    ``moments`` is (n, 5) or (n, 1, 5): M0, Mx, My, Mz, M2 of term 0, the offsets being voxel minus atom.  With rho = amp exp(-expo d^2),
+    amp = occ Z (4 pi / B')^(3/2), expo = 4 pi^2 / B':  dXyz = 2 expo amp (Mx, My, Mz);  dOcc = Z (4 pi / B')^(3/2) M0 (amp / occ without
+    the division: an occupancy of 0 has a derivative);  dB = amp (-1.5 M0 / B' + 4 pi^2 M2 / B'^2), and 0 where B + blur < minB: the
+    clamp B' = max(B + blur, minB) is flat there."""
+    z = np.asarray(electrons, dtype=np.float64).reshape(-1)
+    n = len(z)
+    m = np.asarray(moments, dtype=np.float64).reshape(n, -1, 5)[:, 0, :] if n else np.zeros((0, 5))
+    raw = np.asarray(bfactors, dtype=np.float64).reshape(-1) + float(blur)
+    b = np.maximum(raw, float(minB))
+    occ = np.asarray(occupancies, dtype=np.float64).reshape(-1)
+    unit = z * (4.0 * np.pi / b) ** 1.5
+    amp, expo = occ * unit, 4.0 * np.pi ** 2 / b
+    dB = amp * (-1.5 * m[:, 0] / b + 4.0 * np.pi ** 2 * m[:, 4] / (b * b))
+    return {"dXyz": (2.0 * expo * amp)[:, None] * m[:, 1:4], "dB": np.where(raw < float(minB), 0.0, dB), "dOcc": unit * m[:, 0]}
+
+
+def gaussianAtomCurvatures(electrons, bfactors, occupancies, unitVolume, blur=0.0, minB=MODEL_MIN_B):
+    """The diagonal Gauss-Newton curvature of sum_v rho_a(v)^2 / 2 for an ISOLATED Gaussian atom, from closed-form integrals divided by
+    the voxel volume: with G = (pi / (2 expo))^(3/2), int (d rho / d x)^2 = expo amp^2 G, int (d rho / d B)^2 = (15 / 16) (amp / B')^2 G,
+    int (d rho / d occ)^2 = (amp / occ)^2 G.  A dict ``xyz``, ``b``, ``occ`` of (n,) arrays.  Overlap with neighbours and the ragged
+    cut-off are ignored: the step that divides by these is checked against the target before it is taken."""
+    z = np.asarray(electrons, dtype=np.float64).reshape(-1)
+    b = np.maximum(np.asarray(bfactors, dtype=np.float64).reshape(-1) + float(blur), float(minB))
+    occ = np.asarray(occupancies, dtype=np.float64).reshape(-1)
+    unit = z * (4.0 * np.pi / b) ** 1.5
+    amp, expo = occ * unit, 4.0 * np.pi ** 2 / b
+    g = (np.pi / (2.0 * expo)) ** 1.5 / float(unitVolume)
+    return {"xyz": expo * amp * amp * g, "b": (15.0 / 16.0) * (amp / b) ** 2 * g, "occ": unit * unit * g}
+
+
+def foldImageGradients(grad, rows, rotations, nAtoms):
+    """The gradients of image atoms brought back to the atoms they are copies of: image k is atom ``rows[k]`` under x -> R_k x + t_k, so its
+    positional gradient comes back through the TRANSPOSE of R_k; dB and dOcc simply add.  ``grad`` is the dict of
+    ``gaussianAtomGradients`` over the images, ``rotations`` (m, 3, 3); the result is that dict over ``nAtoms`` atoms.  Added in the order
+    of the images (np.add.at): one order, one result."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+    rot = np.asarray(rotations, dtype=np.float64).reshape(-1, 3, 3)
+    back = np.einsum("kji,kj->ki", rot, np.asarray(grad["dXyz"], dtype=np.float64).reshape(-1, 3))
+    out = {"dXyz": np.zeros((nAtoms, 3)), "dB": np.zeros(nAtoms), "dOcc": np.zeros(nAtoms)}
+    np.add.at(out["dXyz"], rows, back)
+    np.add.at(out["dB"], rows, np.asarray(grad["dB"], dtype=np.float64))
+    np.add.at(out["dOcc"], rows, np.asarray(grad["dOcc"], dtype=np.float64))
+    return out
+
+
+def gaussNewtonStep(gradT, curvature, scale, what, maxShift, maxDeltaB=20.0, damping=1.0):
+    """The damped diagonal Gauss-Newton step against the gradient of T: delta = -damping g / (scale^2 curvature), 0 where the curvature is.
+    A dict ``xyz`` (n, 3; the vector is shortened to ``maxShift``), ``b`` (capped at +-maxDeltaB) and ``occ``; zeros for what is not in
+    ``what``."""
+    n = len(gradT["dB"])
+    s2 = float(scale) ** 2
+
+    def ratio(g, h):
+        h = s2 * np.asarray(h, dtype=np.float64)
+        return np.where(h > 0, -float(damping) * g / np.where(h > 0, h, 1.0), 0.0)
+
+    step = {"xyz": np.zeros((n, 3)), "b": np.zeros(n), "occ": np.zeros(n)}
+    if "xyz" in what:
+        d = ratio(gradT["dXyz"], np.asarray(curvature["xyz"])[:, None])
+        length = np.sqrt((d * d).sum(axis=1))
+        step["xyz"] = d * np.where(length > maxShift, maxShift / np.where(length > 0, length, 1.0), 1.0)[:, None]
+    if "b" in what:
+        step["b"] = np.clip(ratio(gradT["dB"], curvature["b"]), -float(maxDeltaB), float(maxDeltaB))
+    if "occ" in what:
+        step["occ"] = ratio(gradT["dOcc"], curvature["occ"])
+    return step
+
+
 def gaussianTaps(sigmaVoxels, truncate=4.0):
     """The weights of a Gaussian of ``sigmaVoxels`` grid steps for ``DensityMatrix.filtered`` / ``localStats``: radius int(truncate sigma +
     0.5), exp(-x^2 / 2 sigma^2) divided by its sum -- ``scipy.ndimage.gaussian_filter``'s own weights.  sigma = 0 gives [1.0]."""
@@ -818,6 +889,103 @@ class DensityMatrix(object):
         scale = cov / vb if vb > 0 else nan
         return {"n": n, "cc": min(1.0, max(-1.0, cov / math.sqrt(va * vb))) if va > 0 and vb > 0 else nan, "scale": scale,
                 "offset": (sa - scale * sb) / n if vb > 0 else nan}
+
+    # -- from a map back to the atoms: gradient sums, real-space refinement (no reference counterpart) --
+    def atomMoments(self, xyz, expo, radii, uniqueBox=False):
+        """The adjoint of ``modelDensity`` with THIS map as the weight w, in one device call (``pdbeda_atom_moments`` in include/pdbeda.h
+        has the contract): per atom and term the sums over the voxels within radii[a] -- ``modelDensity``'s pair set exactly -- of w e,
+        w e dx, w e dy, w e dz and w e d^2 with e = exp(-expo d^2) and (dx, dy, dz) = voxel - atom.  Over all stored voxels, or with
+        ``uniqueBox`` over the non-repeating box, the domain of ``pairMoments``.  A dict ``moments`` (n, terms, 5), ``nVoxels`` (n,) and
+        ``counters`` (the shift S of the integer sums, the voxels of the largest box, the atoms whose box the domain clipped).  Results
+        are the same bits in every run and for every order of the atoms.  ``gaussianAtomGradients`` turns them into derivatives."""
+        return self._map.atom_moments(xyz, expo, radii, uniqueBox)
+
+    def _leastSquaresTarget(self, model):
+        """(T, scale, offset, cc) of this map against ``model`` over the non-repeating box: T = sum (self - scale model - offset)^2 / 2 at
+        the least-squares scale and offset, from the device's ``pairMoments``."""
+        n, sa, sb, saa, sbb, sab = self.pairMoments(model)
+        if n == 0:
+            raise RuntimeError("no finite voxel pair in the non-repeating box")
+        va, vb, cov = saa - sa * sa / n, sbb - sb * sb / n, sab - sa * sb / n
+        if not vb > 0:
+            raise RuntimeError("the model density is constant over the map: there is no scale to fit")
+        scale = cov / vb
+        return 0.5 * max(va - cov * cov / vb, 0.0), scale, (sa - scale * sb) / n, (cov / math.sqrt(va * vb) if va > 0 else float("nan"))
+
+    def _residual(self, model, scale, offset):
+        """self - scale * model - offset as a resident map: two ``pdbeda_map_combine`` calls, the second against a map of ones."""
+        if self.__dict__.get("_ones") is None:
+            nc, nr, ns = (int(v) for v in self.header.ncrs)
+            self.__dict__["_ones"] = _native.DeviceMap(self._ctx, np.ones((ns, nr, nc), dtype=np.float32), self.header.geometry())
+        kind = type(self._map)
+        return self._made(kind.combine(kind.combine(self._map, model._map, -scale), self.__dict__["_ones"], -offset))
+
+    def refineGaussianAtoms(self, xyz, electrons, bfactors, occupancies, what=("xyz", "b"), cycles=10, maxShift=0.3, images=None, imageAtoms=None,
+                            blur=0.0, minB=MODEL_MIN_B, nSigma=MODEL_N_SIGMA, maxHalvings=6):
+        """Real-space refinement of one-Gaussian atoms (``gaussianAtomTerms``) against THIS map, on plain arrays; no voxel leaves the device.
+        A cycle: ``modelDensity`` of the atoms; ``pairMoments`` for the scale s and offset o of self ~ s calc + o; the residual R = self -
+        s calc - o by ``pdbeda_map_combine``; ``atomMoments(uniqueBox=True)`` of R; a host step.  The target is T = sum (self - s calc -
+        o)^2 / 2 over the non-repeating box.  Because s and o MINIMISE T, its derivatives with respect to them vanish, and dT/dtheta =
+        -s sum_v R d rho / d theta at fixed s and o is the FULL derivative of the profiled target (the envelope argument).  The step is
+        damped diagonal Gauss-Newton, the curvature from the closed-form integrals of an isolated Gaussian (``gaussianAtomCurvatures``):
+        shifts are capped at ``maxShift`` A, B stays >= ``minB``, occupancy in [0, 1].  A step is taken only if T, evaluated on the
+        device, goes down; otherwise it is halved, ``maxHalvings`` times at the most, and a cycle without an accepted step ends the loop.
+        ``what``: any of "xyz", "b", "occ".  ``images``: operators (3 x 4) whose copies of every atom make the model (the identity is not
+        implied: list it); ``imageAtoms`` = (rows, operators) names the copies one by one instead (copy k is atom rows[k] under
+        operators[k]).  The gradient of a copy comes back through the transpose of its rotation.  Returns a dict ``xyz``, ``bfactors``,
+        ``occupancies`` and ``trace``: lists ``T``, ``scale``, ``cc`` (before the first cycle and after every cycle run) and ``halvings``
+        (per cycle; -1: no step was accepted)."""
+        xyz = np.array(xyz, dtype=np.float64).reshape(-1, 3)
+        n = len(xyz)
+        z = np.asarray(electrons, dtype=np.float64).reshape(-1)
+        b = np.array(bfactors, dtype=np.float64).reshape(-1)
+        occ = np.array(occupancies, dtype=np.float64).reshape(-1)
+        unknown = set(what) - {"xyz", "b", "occ"}
+        if unknown:
+            raise ValueError("what: unknown parameter kinds %s" % sorted(unknown))
+        if imageAtoms is not None:
+            rows = np.asarray(imageAtoms[0], dtype=np.int64).reshape(-1)
+            ops = np.asarray(imageAtoms[1], dtype=np.float64).reshape(-1, 3, 4)
+        else:
+            each = [identityOperator()] if images is None else [_operator(op) for op in images]
+            rows = np.tile(np.arange(n, dtype=np.int64), len(each))
+            ops = np.repeat(np.array(each, dtype=np.float64).reshape(-1, 3, 4), n, axis=0)
+        copies = np.bincount(rows, minlength=n).astype(np.float64)
+        unitVolume = float(self.header.unitVolume)
+
+        def place(xyz, b, occ):
+            where = np.einsum("kij,kj->ki", ops[:, :, :3], xyz[rows]) + ops[:, :, 3]
+            amp, expo, bEff = gaussianAtomTerms(z[rows], b[rows], occ[rows], blur=blur, minB=minB)
+            radii = modelRadii(bEff, nSigma)
+            return where, expo, radii, self.modelDensity(where, amp, expo, radii)
+
+        where, expo, radii, model = place(xyz, b, occ)
+        target, scale, offset, cc = self._leastSquaresTarget(model)
+        trace = {"T": [target], "scale": [scale], "cc": [cc], "halvings": []}
+        for _ in range(int(cycles)):
+            moments = self._residual(model, scale, offset).atomMoments(where, expo, radii, uniqueBox=True)["moments"]
+            grad = foldImageGradients(gaussianAtomGradients(moments, z[rows], b[rows], occ[rows], blur=blur, minB=minB), rows, ops[:, :, :3], n)
+            gradT = {k: -scale * v for k, v in grad.items()}
+            curv = gaussianAtomCurvatures(z, b, occ, unitVolume, blur=blur, minB=minB)
+            step = gaussNewtonStep(gradT, {k: v * copies for k, v in curv.items()}, scale, what, maxShift)
+            taken = -1
+            for h in range(int(maxHalvings) + 1):
+                f = 0.5 ** h
+                xyz2 = xyz + f * step["xyz"]
+                b2 = np.maximum(b + f * step["b"], float(minB)) if "b" in what else b
+                occ2 = np.clip(occ + f * step["occ"], 0.0, 1.0) if "occ" in what else occ
+                trial = place(xyz2, b2, occ2)
+                t2, s2, o2, cc2 = self._leastSquaresTarget(trial[3])
+                if t2 < target:
+                    xyz, b, occ, taken = xyz2, b2, occ2, h
+                    where, expo, radii, model = trial
+                    target, scale, offset, cc = t2, s2, o2, cc2
+                    break
+            trace["halvings"].append(taken)
+            trace["T"].append(target); trace["scale"].append(scale); trace["cc"].append(cc)
+            if taken < 0:
+                break
+        return {"xyz": xyz, "bfactors": b, "occupancies": occ, "trace": trace}
 
     # -- from a map to a map through a neighbourhood (no reference counterpart) ------------
     def _made(self, device_map):

@@ -38,6 +38,7 @@
 #include "pdbeda_contacts.h"
 #include "pdbeda_filter.h"
 #include "pdbeda_fourier.h"
+#include "pdbeda_gradient.h"
 #include "pdbeda_model.h"
 #include "pdbeda_partition.h"
 #include "pdbeda_peaks.h"
@@ -202,6 +203,7 @@ struct pdbeda_map {
     int64_t n_vox = 0;
     double fix_mul = 0.0;             // 2^S of the order-independent blob sums (FixSums); 0 = not yet derived from the map's range
     bool fix_refused = false;         // the range pass found a NaN / infinity: labelling calls refuse the map (map_fix_mul)
+    double max_abs = 0.0;             // the largest |rho| of the stored map, from the same range pass (valid while fix_mul != 0): pdbeda_atom_moments' quantum
 };
 
 // A blob list is a VIEW of a labelling job: the whole job, or one plane of a fused whole-map job (the handle is &job->view[p])
@@ -1068,7 +1070,7 @@ static void range_apply(pdbeda_map *m, const double range[2]) {
     bool refused = false;
     const double mul = map_quantum(range[0], range[1], &refused);
     if (refused) m->fix_refused = true;      // (NaN / infinite voxels: the labelling calls refuse the map)
-    else m->fix_mul = mul;
+    else { m->fix_mul = mul; m->max_abs = range[1]; }
 }
 static int map_fix_mul(pdbeda_map *m) {
     pdbeda_ctx *ctx = m->ctx;
@@ -1107,6 +1109,7 @@ static int box_fix_mul(pdbeda_map *m, int nc, int nr, int uc, int ur, int us, un
 extern "C" int pdbeda_map_invalidate(pdbeda_map *m) {
     if (!m) return PDBEDA_ERR_ARGUMENT;
     m->fix_mul = 0.0;
+    m->max_abs = 0.0;
     m->fix_refused = false;
     return PDBEDA_OK;
 }
@@ -3592,6 +3595,107 @@ extern "C" int pdbeda_map_pair_moments(pdbeda_map *a, pdbeda_map *b, float b_flo
     if (rc) return rc;
     if (n) *n = (int64_t)res[0];
     if (sums) memcpy(sums, res + 1, 40);
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// From a map back to the atoms: the adjoint of the model density (no reference counterpart; the contract: include/pdbeda.h)
+// ------------------------------------------------------------------------------------
+// The xyz -> crs map of a geometry as the plan takes it (xyz2frac's arithmetic, row by row) and the domain.
+static GradGrid grad_grid_of(const Geom &g, bool unique_box) {
+    GradGrid gg = GradGrid();
+    for (int k = 0; k < 3; ++k) {
+        const int a = g.map2crs[k];
+        if (g.orthogonal) {
+            gg.rows[3 * k + a] = 1.0 / g.grid_len[a];
+            gg.off[k] = -(g.origin[a] / g.grid_len[a]);
+        } else {
+            for (int i = 0; i < 3; ++i) gg.rows[3 * k + i] = g.deortho[3 * a + i] * (double)g.xyz_interval[a];
+            gg.off[k] = -(double)sel3(g.crs_start, g.map2xyz[a]);
+        }
+        gg.dom[k] = unique_box ? std::min(g.unique_ncrs[k], g.ncrs[k]) : g.ncrs[k];
+    }
+    grad_grid_norms(&gg);
+    return gg;
+}
+
+template <int NT>
+static void atom_moments_launch(pdbeda_ctx *ctx, unsigned blocks, const GradArgs &a) {
+    PROF(ctx, "k_atom_moments");
+    hipLaunchKernelGGL(k_atom_moments<NT>, dim3(blocks), dim3(256), 0, ctx->stream, a);
+}
+
+// The launch graph: the host's checks and boxes (pdbeda_gradplan.h); the range pass when the map's max |w| is not cached yet (a wait); the atoms'
+// coordinates, exponents, radii and boxes in one row of scratch; k_atom_moments<n_terms>, a wave per atom; the results.  One wait.
+extern "C" int pdbeda_atom_moments(pdbeda_map *weight, const double *xyz, int64_t n_atoms, int32_t n_terms, const double *expo, const float *radii, uint32_t flags,
+                                   double *moments, int32_t *n_voxels, int64_t counters[3]) {
+    if (!weight || (n_atoms > 0 && (!xyz || !expo || !radii))) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = weight->ctx;
+    int64_t bad = -1;
+    float r_top = 0.0f;
+    switch (grad_check(xyz, n_atoms, n_terms, expo, radii, flags, PDBEDA_MOMENTS_UNIQUE_BOX, &bad, &r_top)) {
+    case GRAD_TERMS: return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom moments: n_terms must be 1 .. %d", PDBEDA_MODEL_MAX_TERMS);
+    case GRAD_FLAG: return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom moments: unknown flag 0x%x", flags);
+    case GRAD_COUNT: return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom moments: a negative number of atoms, or 2^31 or more");
+    case GRAD_XYZ: return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom moments: a coordinate of atom %lld is not finite", (long long)bad);
+    case GRAD_EXPO: return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom moments: an exponent of atom %lld is not finite or negative", (long long)bad);
+    case GRAD_RADIUS: return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom moments: the radius of atom %lld is not finite or <= 0", (long long)bad);
+    default: break;
+    }
+    if (n_atoms == 0) return PDBEDA_OK;
+    const Geom &g = weight->geom;
+    const GradGrid gg = grad_grid_of(g, (flags & PDBEDA_MOMENTS_UNIQUE_BOX) != 0);
+    const double r_max = (double)r_top;
+    if (!grad_reach_ok(gg, r_max)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom moments: the largest radius spans 2^29 grid steps or more");
+    std::vector<GradBox> boxes((size_t)n_atoms);
+    int64_t v_max = 0, n_clipped = 0;
+    for (int64_t i = 0; i < n_atoms; ++i) {
+        bool clipped = false;
+        const int64_t vox = grad_box(gg, xyz + 3 * i, (double)radii[i], &boxes[(size_t)i], &clipped);
+        if (grad_box_too_large(vox)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "atom moments: the box of atom %lld holds 2^31 voxels or more", (long long)i);
+        v_max = std::max(v_max, vox);
+        n_clipped += clipped ? 1 : 0;
+    }
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = map_fix_mul(weight)) return rc;      // (a wait when the map's range is not known yet; a map with non-finite voxels is refused here)
+    const int S = grad_shift(weight->max_abs, r_max, v_max);
+    const size_t na = (size_t)n_atoms, np = na * (size_t)n_terms;
+    double *d_xyz = nullptr, *d_expo = nullptr, *d_mom = nullptr;
+    float *d_radii = nullptr;
+    GradBox *d_box = nullptr;
+    int32_t *d_nv = nullptr;
+    const int rc = with_scratch(ctx, "atom moments", [&](Carver &cv) {
+        cv.take(d_xyz, 3 * na);
+        cv.take(d_expo, np);
+        cv.take(d_radii, na);
+        cv.take(d_box, na);
+        cv.take(d_mom, 5 * np);
+        cv.take(d_nv, na);
+    }, [&]() -> int {
+        const H2DItem in[4] = {{d_xyz, xyz, 24 * na}, {d_expo, expo, 8 * np}, {d_radii, radii, 4 * na}, {d_box, boxes.data(), sizeof(GradBox) * na}};
+        HIP_TRY(ctx, h2d_row(ctx, in, 4));
+        GradArgs a;
+        a.geom = weight->geom_dev; a.w = weight->dens;
+        a.xyz = d_xyz; a.expo = d_expo; a.radii = d_radii; a.box = d_box; a.n_atoms = (int)n_atoms;
+        a.fix_mul = ldexp(1.0, S); a.fix_inv = ldexp(1.0, -S);
+        a.moments = d_mom; a.n_voxels = d_nv;
+        const unsigned blocks = grid_for(n_atoms, GP_WAVES, 8192);
+        switch (n_terms) {
+        case 1: atom_moments_launch<1>(ctx, blocks, a); break;
+        case 2: atom_moments_launch<2>(ctx, blocks, a); break;
+        case 3: atom_moments_launch<3>(ctx, blocks, a); break;
+        case 4: atom_moments_launch<4>(ctx, blocks, a); break;
+        case 5: atom_moments_launch<5>(ctx, blocks, a); break;
+        default: atom_moments_launch<6>(ctx, blocks, a); break;
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        const D2HItem parts[2] = {{moments, d_mom, 40 * np}, {n_voxels, d_nv, 4 * na}};
+        HIP_TRY(ctx, d2h_each(ctx, parts, 2));
+        return 0;
+    });
+    if (rc) return rc;
+    if (counters) { counters[0] = S; counters[1] = v_max; counters[2] = n_clipped; }
     return PDBEDA_OK;
 }
 

@@ -38,6 +38,8 @@ pdbfolder = './pdb_data/'
 # the calculated (model) density: added to every B-factor (A^2), and the cut-off of an atom in standard deviations of its Gaussian
 modelBlur = 0.0
 modelSigmas = ccp4.MODEL_N_SIGMA
+refineCycles = 5          # cycles of ``refineAtoms`` / the "refine" mode
+refineMaxShift = 0.3      # A: the longest shift of an atom in one refinement cycle
 
 # the local statistics of a map: the Gaussian window's standard deviation (A) and cut-off (standard deviations), and the floor under a local
 # standard deviation as a fraction of the whole map's stdDensity (a flat solvent region must not turn rounding noise into z-scores)
@@ -427,6 +429,10 @@ class DensityAnalysis(object):
     atomQScoreHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'valid', 'q_score', 'n_points']
     residueQScoreHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'mean_q_score', 'min_q_score', 'num_atoms_scored']
     atomModelCorrelationHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'rscc_model', 'rsr_model']
+    atomGradientHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'dT_dx', 'dT_dy', 'dT_dz', 'dT_dB', 'dT_docc',
+                          'shift_x', 'shift_y', 'shift_z', 'shift_b', 'shift_occ', 'num_voxels']
+    refineAtomHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'refined_x', 'refined_y', 'refined_z', 'refined_bfactor',
+                        'refined_occupancy', 'shift', 'delta_b']
     residueModelCorrelationHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'rscc_model', 'rsr_model']
     atomLocalHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'local_cc', 'local_z_diff', 'local_std_diff']
     residueLocalHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'mean_local_cc', 'min_local_cc', 'extreme_local_z_diff']
@@ -448,6 +454,7 @@ class DensityAnalysis(object):
         self._qScores = None
         self._model = None
         self._modelDifference = None
+        self._refined = None
         self._local = {}
         self._redBlobList = None
         self._blueBlobList = None
@@ -1618,6 +1625,102 @@ class DensityAnalysis(object):
         total = model.pairMoments(model)[1]
         return {"cc": fit["cc"], "scale": fit["scale"], "offset": fit["offset"], "n": fit["n"], "electrons_placed": self._model[1],
                 "electrons_found": total * self.densityObj.header.unitVolume}
+
+    # ---- the way back from the maps to the atoms: gradients of the map-model target, real-space refinement (no reference counterpart) ----
+    def _refinementAtoms(self):
+        """What the gradient and refinement calls work on: a dict ``atomRows`` (rows of the structure columns of the atoms of the asymmetric
+        unit that ``modelDensityObj`` places: electrons known, occupancy not 0), their ``xyz``, ``electrons``, ``bfactors`` and
+        ``occupancies``, and for every symmetry atom the model is made from -- in ``_modelAtoms``' order -- ``rows`` (its atom, as an index
+        into ``atomRows``) and ``operators`` ([R | t] with the lattice translation of its cell folded into t; the operator index is the
+        fourth entry of the symmetry tag that ``symmetryAtoms.columns`` gives)."""
+        _requireParams()
+        cols = _structure.columns(self.biopdbObj)
+        names = cols.pair_names
+        n = len(cols.atoms)
+        electrons = _pairTables(names, max(len(names), 1))["electrons"][cols.pair_of_atom] if n else np.zeros(0)
+        occupancy = np.asarray(cols.occupancy, dtype=np.float64) if n else np.zeros(0)
+        keep = ~np.isnan(electrons) & (occupancy != 0)
+        kept = np.nonzero(keep)[0]
+        position = np.full(n, -1, dtype=np.int64)
+        position[kept] = np.arange(len(kept))
+        sym = self.symmetryAtoms
+        idx, tags = np.asarray(sym._idx, dtype=np.int64), np.asarray(sym._sym, dtype=np.int64).reshape(-1, 4)
+        use = keep[idx] if len(idx) else np.zeros(0, dtype=bool)
+        rot = np.array([np.asarray(m, dtype=np.float64) for m in self.pdbObj.header.rotationMats]).reshape(-1, 3, 4)
+        ortho = np.asarray(self.densityObj.header.orthoMat, dtype=np.float64)
+        operators = rot[tags[use, 3]].copy() if use.any() else np.zeros((0, 3, 4))
+        if len(operators):
+            operators[:, :, 3] += tags[use, :3].astype(np.float64).dot(ortho.T)
+        return {"atomRows": kept, "xyz": np.asarray(cols.coord, dtype=np.float64).reshape(-1, 3)[kept], "electrons": electrons[kept],
+                "bfactors": np.asarray(cols.bfactor, dtype=np.float64)[kept], "occupancies": occupancy[kept], "rows": position[idx[use]], "operators": operators}
+
+    def _atomGradients(self):
+        """(atoms of ``_refinementAtoms``, dT/dtheta folded over the images, the Gauss-Newton step, pairs per atom, the fit) at the deposited model."""
+        atoms = self._refinementAtoms()
+        d, model = self.densityObj, self.modelDensityObj
+        target, scale, offset, cc = d._leastSquaresTarget(model)
+        xyz, amp, expo, radii, _ = self._modelAtoms()
+        rows, n = atoms["rows"], len(atoms["atomRows"])
+        got = d._residual(model, scale, offset).atomMoments(xyz, expo, radii, uniqueBox=True)
+        each = ccp4.gaussianAtomGradients(got["moments"], atoms["electrons"][rows], atoms["bfactors"][rows], atoms["occupancies"][rows], blur=modelBlur)
+        folded = ccp4.foldImageGradients(each, rows, atoms["operators"][:, :, :3], n)
+        gradT = {k: -scale * v for k, v in folded.items()}
+        copies = np.bincount(rows, minlength=n).astype(np.float64)
+        curv = ccp4.gaussianAtomCurvatures(atoms["electrons"], atoms["bfactors"], atoms["occupancies"], d.header.unitVolume, blur=modelBlur)
+        step = ccp4.gaussNewtonStep(gradT, {k: v * copies for k, v in curv.items()}, scale, ("xyz", "b", "occ"), refineMaxShift)
+        pairs = np.zeros(n, dtype=np.int64)
+        np.add.at(pairs, rows, got["nVoxels"].astype(np.int64))
+        return atoms, gradT, step, pairs, {"T": target, "scale": scale, "offset": offset, "cc": cc}
+
+    def calculateAtomGradients(self):
+        """One row per atom of the asymmetric unit (``atomGradientHeader``; the atoms and leading columns of
+        ``calculateAtomRegionDensity``): the derivatives of T = sum (2Fo-Fc - s model - o)^2 / 2 over the non-repeating box -- s and o the
+        fit of ``modelCorrelation()`` -- with respect to the atom's x, y, z, B and occupancy, the damped Gauss-Newton shift each implies
+        (``ccp4.gaussNewtonStep``; the position shift capped at the module's ``refineMaxShift``) and the voxel pairs the sums ran over.
+        The contributions of the atom's symmetry copies are folded in: a copy's positional gradient comes back through the transpose
+        of its operator's rotation.  An atom the model does not place (no electrons known, occupancy 0) has zeros: T does not depend
+        on it."""
+        cols, pick, lead = self._atomPick("")
+        atoms, gradT, step, pairs, _ = self._atomGradients()
+        n, at = len(cols.atoms), atoms["atomRows"]
+        table = np.zeros((n, 10))
+        table[at, 0:3], table[at, 3], table[at, 4] = gradT["dXyz"], gradT["dB"], gradT["dOcc"]
+        table[at, 5:8], table[at, 8], table[at, 9] = step["xyz"], step["b"], step["occ"]
+        count = np.zeros(n, dtype=np.int64)
+        count[at] = pairs
+        return self._rows(*lead, cols.bfactor[pick], *[table[:, k] for k in range(10)], count)
+
+    def refineAtoms(self, what=("xyz", "b"), cycles=None):
+        """Real-space refinement of the deposited atoms against the 2Fo-Fc map (``DensityMatrix.refineGaussianAtoms`` on the atoms of the
+        asymmetric unit, their symmetry copies following them): one row per atom (``refineAtomHeader``) with the refined coordinate, B
+        and occupancy, the length of the shift and the change of B.  The structure itself is left as it is; the result of the last call
+        is kept for ``refineSummary``.  ``cycles`` defaults to the module's ``refineCycles``."""
+        cols, pick, lead = self._atomPick("")
+        atoms = self._refinementAtoms()
+        out = self.densityObj.refineGaussianAtoms(atoms["xyz"], atoms["electrons"], atoms["bfactors"], atoms["occupancies"], what=tuple(what),
+                                                  cycles=refineCycles if cycles is None else cycles, maxShift=refineMaxShift,
+                                                  imageAtoms=(atoms["rows"], atoms["operators"]), blur=modelBlur, nSigma=modelSigmas)
+        self._refined = (atoms, out)
+        n, at = len(cols.atoms), atoms["atomRows"]
+        xyz = np.asarray(cols.coord, dtype=np.float64).reshape(-1, 3).copy()
+        b, occ = np.asarray(cols.bfactor, dtype=np.float64).copy(), np.asarray(cols.occupancy, dtype=np.float64).copy()
+        xyz[at], b[at], occ[at] = out["xyz"], out["bfactors"], out["occupancies"]
+        shift, deltaB = np.zeros(n), np.zeros(n)
+        shift[at] = np.sqrt(((out["xyz"] - atoms["xyz"]) ** 2).sum(axis=1))
+        deltaB[at] = out["bfactors"] - atoms["bfactors"]
+        return self._rows(*lead, cols.bfactor[pick], xyz[:, 0], xyz[:, 1], xyz[:, 2], b, occ, shift, deltaB)
+
+    def refineSummary(self):
+        """T, the correlation and the scale before and after the last ``refineAtoms`` call (made with its defaults when there was none), the
+        cycles run, and the rms shift and rms change of B over the refined atoms."""
+        if self._refined is None:
+            self.refineAtoms()
+        atoms, out = self._refined
+        trace = out["trace"]
+        n = max(len(atoms["atomRows"]), 1)
+        return {"num_atoms": len(atoms["atomRows"]), "cycles": len(trace["halvings"]), "target_before": trace["T"][0], "target_after": trace["T"][-1],
+                "cc_before": trace["cc"][0], "cc_after": trace["cc"][-1], "scale_before": trace["scale"][0], "scale_after": trace["scale"][-1],
+                "rms_shift": float(np.sqrt(((out["xyz"] - atoms["xyz"]) ** 2).sum() / n)), "rms_delta_b": float(np.sqrt(((out["bfactors"] - atoms["bfactors"]) ** 2).sum() / n))}
 
     # ---- local statistics: significance against the surroundings, local map-model correlation (no reference counterpart) ----
     def _localTaps(self, densityObj):

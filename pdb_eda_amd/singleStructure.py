@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore", "model", "local", "fourier", "mask")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore", "model", "local", "fourier", "mask", "refine")
 
 
 def numpyConverter(obj):
@@ -132,6 +132,11 @@ def _modelSummaryTable(analyzer, o):
     return [[summary[name] for name in _MODEL_SUMMARY]]
 
 
+def _refineSummaryTable(analyzer, o):
+    summary = analyzer.refineSummary()
+    return [[summary[name] for name in _REFINE_SUMMARY]]
+
+
 def _localSummaryTable(analyzer, o):
     summary = analyzer.localSummary()
     return [[summary[name] for name in _LOCAL_SUMMARY]]
@@ -151,6 +156,7 @@ def _maskSummaryTable(analyzer, o):
 
 _MASK_SUMMARY = ["cell_voxels", "solvent_voxels", "solvent_fraction"] + ["%s_%s_%s" % (region, name, what) for region in ("solvent", "protein") for name in ("density", "diff")
                                                                        for what in ("mean", "std")] + ["solvent_noise", "k_sol", "b_sol", "solvent_scale", "solvent_residual"]
+_REFINE_SUMMARY = ["num_atoms", "cycles", "target_before", "target_after", "cc_before", "cc_after", "scale_before", "scale_after", "rms_shift", "rms_delta_b"]
 _FOURIER_SUMMARY = ["grid_c", "grid_r", "grid_s", "d_min", "num_shells", "fsc_05_resolution", "fsc_0143_resolution", "overall_fsc", "overall_scale"]
 _LOCAL_SUMMARY = ["window_sigma", "window_truncate", "radius_c", "radius_r", "radius_s", "num_local_green_blobs", "num_local_red_blobs", "num_green_blobs", "num_red_blobs",
                   "median_atom_local_cc", "min_atom_local_cc"]
@@ -219,6 +225,9 @@ TABLES = {
     # (no reference counterpart: the whole cell divided into molecule and solvent, the flat bulk-solvent fit; ``shells`` is the number of resolution shells)
     ("mask", "shell"): (lambda an: _DA.maskShellHeader, lambda an, o: an.calculateMaskShells(o["shells"])),
     ("mask", "summary"): (lambda an: list(_MASK_SUMMARY), _maskSummaryTable),
+    # (no reference counterpart: real-space refinement of the deposited atoms against the 2Fo-Fc map, x, y, z and B; no option applies)
+    ("refine", "atom"): (lambda an: _DA.refineAtomHeader, lambda an, o: an.refineAtoms()),
+    ("refine", "summary"): (lambda an: list(_REFINE_SUMMARY), _refineSummaryTable),
     ("statistics", "residue"): (lambda an: an.residueMetricsHeaderList, lambda an, o: an.residueMetrics()),
     ("statistics", "atom"): (lambda an: an.atomMetricsHeaderList, lambda an, o: _plainColumns(an.atomMetrics(), **_SYM)),
 }
@@ -228,9 +237,9 @@ def rows(analyzer, mode, level="atom", radius=None, numSD=None, type="", atomMas
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore | model | local | fourier | mask;  level: atom | residue | domain | symmetry-atom
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore | model | local | fourier | mask | refine;  level: atom | residue | domain | symmetry-atom
     (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak, basin, shape and dipole) | atom-type (profile) | summary | blob
-    (partition) | summary (qscore: atom | residue | summary, no other option applies; model: atom | residue | summary, ``radius`` is the sphere's, by default the one of the statistics mode; local: atom | residue | summary under the module's window, no other option applies; fourier: shell | summary, ``shells`` resolution shells; mask: shell | summary, ``shells`` resolution shells);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
+    (partition) | summary (qscore: atom | residue | summary, no other option applies; model: atom | residue | summary, ``radius`` is the sphere's, by default the one of the statistics mode; local: atom | residue | summary under the module's window, no other option applies; fourier: shell | summary, ``shells`` resolution shells; mask: shell | summary, ``shells`` resolution shells; refine: atom | summary, no option applies);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
     (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
     maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default);  dipole: always the fused green
     and red lists (numSD default 3.0), ``radius`` is the largest gap between the two blobs when given (else 2.5 A);  radius default 3.5 elsewhere."""

@@ -35,3 +35,7 @@ done
 # float-cast-overflow: tests/test_spherebox_host.py builds the harness that way itself, writes the cases and compares every line
 echo "sphere planner, -fsanitize=address,undefined,float-cast-overflow:"
 python3 -m pytest tests/test_spherebox_host.py -q -p no:cacheprovider
+# The host's plan of pdbeda_atom_moments (pdb_eda_amd/csrc/pdbeda_gradplan.h) on tests/gradient_harness.cpp, the same way:
+# tests/test_gradient_plan_host.py builds the harness under ASan + UBSan itself, writes the cases and compares every line
+echo "atom-moment planner, -fsanitize=address,undefined,float-cast-overflow:"
+python3 -m pytest tests/test_gradient_plan_host.py -q -p no:cacheprovider
