@@ -553,6 +553,54 @@ int pdbeda_atom_moments(pdbeda_map *weight,
                         int32_t *n_voxels,                  /* [n_atoms] */
                         int64_t counters[3]);               /* any output may be NULL */
 
+/* ---- what fits in a blob: rigid-fragment poses scored on a map ----------------------------- */
+/* A small rigid fragment (a ligand, an ion, a side-chain conformer) tried under n_rot rotations at n_centres centres: every pose is
+ * scored by the map read BETWEEN voxels at its atoms, and the best poses of every centre are ranked (no reference counterpart).
+ * The fragment is frag_xyz [n_frag][3] relative to its pivot with weights frag_w [n_frag]; a rotation is a row-major 3x3 matrix made
+ * by the host (the device evaluates no sin or cos).  Rotations are NOT checked for orthonormality: they are 3x3 matrices.
+ * Position of atom a in pose (centre c, rotation R): p[i] = c[i] + dot(R[i], x_a), the dot product as everywhere, fma(R[i][2], x_a[2],
+ * fma(R[i][0], x_a[0], R[i][1] * x_a[1])), then ONE unfused fp64 add.
+ * Sample: v_a and valid_a are exactly pdbeda_interp_density's value and valid flag at p.  (A position that call would refuse -- not
+ * finite, or 2^29 grid steps or more from the origin, which only a matrix that is no rotation can produce -- has v_a = NaN, valid_a = 0.)
+ * Score: s = +0.0, then s = s + frag_w[a] * v_a for a = 0 .. n_frag-1: the product is rounded, then the sum, in unfused fp64.
+ * A NaN score is stored as THE quiet NaN 0x7ff8000000000000, so that equal inputs give equal bytes on every path.
+ * Low atoms: n_low = the atoms with v_a < (double)floor (a NaN on either side compares false).
+ * A pose is REJECTED when n_low > max_low (a negative max_low rejects every pose), when its score is NaN, or when some valid_a == 0
+ * unless PDBEDA_POSE_ALLOW_OUTSIDE is set.  Every other pose is kept.
+ * Ranking: the kept poses of ONE centre, by score descending compared as numbers (-0.0 == +0.0), ties to the lower rotation index: a
+ * strict total order.  best_rot [n_centres][top_k] the rotation indices in that order, -1 beyond the kept poses; best_score the scores,
+ * +0.0 where the index is -1; best_low the poses' n_low, 0 where the index is -1; n_kept [n_centres] the kept poses of a centre.
+ * The full table: all_score, all_low [n_centres][n_rot] and all_kept (1 / 0) of EVERY pose, rejected ones included (their score and
+ * n_low are what the rules above give).
+ * counters = {centres whose box was not staged in LDS and that read the map directly -- a slower path with the same results --, the
+ * largest staged box in voxels, rejected poses in total}.  The box of a centre covers the sphere of radius max_a |x_a| =
+ * max_a sqrt((x*x + y*y) + z*z) around it by pdbeda_atom_moments' box rule (any cell, skewed ones included), grown by two voxels on
+ * every side (the interpolation's support and one of safety) and NOT clipped: it is filled through the wrap rule.  It is staged when
+ * 4 bytes a voxel plus a stored bit a voxel (whole 64-bit words) fit 128 KiB.  No result depends on the box.
+ * PDBEDA_POSE_GLOBAL_ONLY (an A/B and test switch): no box is staged; the same bytes out, counters[0] = n_centres, counters[1] = 0.
+ * No floating-point atomic and no sum across poses: two calls agree to the bit; permuting the centres permutes the rows.
+ * n_centres == 0 succeeds and touches nothing.  PDBEDA_ERR_ARGUMENT before any launch, in this order, the message naming the offender:
+ * n_frag outside 1 .. PDBEDA_POSE_MAX_ATOMS, n_rot outside 1 .. PDBEDA_POSE_MAX_ROTATIONS, top_k outside 1 .. PDBEDA_POSE_MAX_TOP, an
+ * unknown flag, n_centres < 0 or n_centres * n_rot >= 2^31, a non-finite fragment coordinate or weight, a non-finite rotation entry, a
+ * non-finite centre, a fragment radius of 2^29 grid steps or more along a crs axis, a centre whose grid position is 2^29 steps or
+ * more.  floor may be anything (NaN and -INFINITY count no atom as low).  Synchronous; a failing call leaves the context usable.
+ * Large calls are cut into chunks of centres inside the call; the results do not depend on the cut. */
+#define PDBEDA_POSE_MAX_ATOMS 256
+#define PDBEDA_POSE_MAX_ROTATIONS 1048576
+#define PDBEDA_POSE_MAX_TOP 64
+#define PDBEDA_POSE_ALLOW_OUTSIDE 1u
+#define PDBEDA_POSE_GLOBAL_ONLY 2u
+int pdbeda_pose_scores(pdbeda_map *map,
+                       const double *frag_xyz, const double *frag_w, int32_t n_frag,   /* [n_frag][3] relative to the pivot, [n_frag] */
+                       const double *rot, int64_t n_rot,                                /* [n_rot][9], row-major 3x3 */
+                       const double *centres, int64_t n_centres,                        /* [n_centres][3] */
+                       float floor, int32_t max_low,                                    /* the low-atom rule */
+                       int32_t top_k, uint32_t flags,
+                       int32_t *best_rot, double *best_score, int32_t *best_low,        /* [n_centres][top_k] */
+                       int32_t *n_kept,                                                 /* [n_centres] */
+                       double *all_score, int32_t *all_low, uint8_t *all_kept,          /* [n_centres][n_rot] */
+                       int64_t counters[3]);                                            /* any output may be NULL */
+
 /* ---- from a map to a map through a neighbourhood: separable filters, local statistics ---- */
 /* A separable filter of a resident map (no reference counterpart; every other map-to-map call is voxel-wise).
  * Output and domain: *out is a NEW map owned by the library on the geometry of `map` -- ownership and lifetime are those of

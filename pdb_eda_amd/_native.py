@@ -125,6 +125,7 @@ _SIGS = {
     "pdbeda_model_density": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, _p, C.POINTER(_p), _p]),
     "pdbeda_map_pair_moments": (C.c_int, [_p, _p, C.c_float, C.POINTER(_i64), _p]),
     "pdbeda_atom_moments": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, C.c_uint32, _p, _p, _p]),
+    "pdbeda_pose_scores": (C.c_int, [_p, _p, _p, C.c_int32, _p, _i64, _p, _i64, C.c_float, C.c_int32, C.c_int32, C.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pdbeda_map_filter": (C.c_int, [_p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_uint32, C.POINTER(_p)]),
     "pdbeda_map_local_stats": (C.c_int, [_p, _p, _p, C.c_int32, _p, C.c_int32, _p, C.c_int32, C.c_double, _p, _p, _p, _p, _p, _p]),
     "pdbeda_map_spread": (C.c_int, [_p, C.c_float, C.c_uint32, _p, _i64, _p, _p, C.POINTER(_p), _p]),
@@ -540,6 +541,8 @@ SPREAD_MAX_OFFSETS = 16384       # PDBEDA_SPREAD_MAX_OFFSETS
 SPREAD_MAX_REACH = 32            # PDBEDA_SPREAD_MAX_REACH
 SPREAD_BELOW = 1                 # PDBEDA_SPREAD_BELOW
 MOMENTS_UNIQUE_BOX = 1           # PDBEDA_MOMENTS_UNIQUE_BOX
+POSE_ALLOW_OUTSIDE, POSE_GLOBAL_ONLY = 1, 2      # PDBEDA_POSE_ALLOW_OUTSIDE, PDBEDA_POSE_GLOBAL_ONLY
+POSE_MAX_ATOMS, POSE_MAX_ROTATIONS, POSE_MAX_TOP = 256, 1 << 20, 64
 LOCAL_STATS_OUTPUTS = ("mean_a", "std_a", "z_a", "mean_b", "std_b", "cc")      # the output pointers of pdbeda_map_local_stats, in order
 
 
@@ -726,6 +729,38 @@ class DeviceMap(object):
                                                            MOMENTS_UNIQUE_BOX if unique_box else 0, _ptr(moments) if na else None, _ptr(n_voxels) if na else None, _ptr(ctr)),
                         "pdbeda_atom_moments")
         return {"moments": moments, "nVoxels": n_voxels, "counters": {"shift": int(ctr[0]), "maxBoxVoxels": int(ctr[1]), "clippedAtoms": int(ctr[2])}}
+
+    def pose_scores(self, frag_xyz, frag_w, rot, centres, top_k=1, floor=-np.inf, max_low=None, allow_outside=False, full=False, global_only=False):
+        """pdbeda_pose_scores: the rigid fragment ``frag_xyz`` (n_frag x 3, relative to its pivot; weights ``frag_w``) under every rotation of
+        ``rot`` (n_rot x 3 x 3) at every centre of ``centres`` (n x 3) on this map.  A pose scores sum_a w_a * (the trilinear density at its atom
+        a); it is rejected when more than ``max_low`` atoms (None: never) read less than ``floor``, when its score is NaN, or -- unless
+        ``allow_outside`` -- when an atom reads a voxel that is not stored.  A dict: ``bestRot`` / ``bestScore`` / ``bestLow`` (n, top_k: the kept
+        poses of a centre, best first, -1 / +0.0 / 0 beyond them), ``nKept`` (n,), with ``full`` the tables ``scores`` / ``low`` / ``kept``
+        (n, n_rot), and ``counters`` {"globalCentres", "maxStagedBox", "rejected"}.  ``global_only``: no box is staged in LDS (an A/B switch)."""
+        frag_xyz = np.ascontiguousarray(frag_xyz, dtype=np.float64).reshape(-1, 3)
+        frag_w = np.ascontiguousarray(frag_w, dtype=np.float64).reshape(-1)
+        rot = np.ascontiguousarray(rot, dtype=np.float64).reshape(-1, 9)
+        centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 3)
+        if len(frag_w) != len(frag_xyz):
+            raise ValueError("frag_w must have one weight per fragment atom")
+        n, nr, k = len(centres), len(rot), int(top_k)
+        rows = max(k, 0)
+        best_rot, best_score, best_low = np.full((n, rows), -1, dtype=np.int32), np.zeros((n, rows), dtype=np.float64), np.zeros((n, rows), dtype=np.int32)
+        n_kept = np.zeros(n, dtype=np.int32)
+        score = np.zeros((n, nr), dtype=np.float64) if full else None
+        low = np.zeros((n, nr), dtype=np.int32) if full else None
+        kept = np.zeros((n, nr), dtype=np.uint8) if full else None
+        ctr = np.zeros(3, dtype=np.int64)
+        flags = (POSE_ALLOW_OUTSIDE if allow_outside else 0) | (POSE_GLOBAL_ONLY if global_only else 0)
+        self._ctx.check(self._ctx._lib.pdbeda_pose_scores(self._h, _ptr(frag_xyz), _ptr(frag_w), len(frag_xyz), _ptr(rot), nr, _ptr(centres) if n else None, n,
+                                                          C.c_float(floor), 2 ** 31 - 1 if max_low is None else int(max_low), k, flags,
+                                                          _ptr(best_rot), _ptr(best_score), _ptr(best_low), _ptr(n_kept), _ptr(score), _ptr(low), _ptr(kept), _ptr(ctr)),
+                        "pdbeda_pose_scores")
+        out = {"bestRot": best_rot, "bestScore": best_score, "bestLow": best_low, "nKept": n_kept,
+               "counters": {"globalCentres": int(ctr[0]), "maxStagedBox": int(ctr[1]), "rejected": int(ctr[2])}}
+        if full:
+            out.update(scores=score, low=low, kept=kept.astype(bool))
+        return out
 
     @classmethod
     def _made(cls, like, h):

@@ -124,6 +124,83 @@ def sphereLattice(n):
     return np.stack([rho * np.cos(phi), rho * np.sin(phi), z], axis=1)
 
 
+def _quaternionMatrices(q):
+    """(n, 4) unit quaternions (x, y, z, w) -> (n, 3, 3) rotation matrices (rows orthonormal to a few 1e-16, determinant +1)."""
+    x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    out = np.empty((len(q), 3, 3), dtype=np.float64)
+    out[:, 0, 0], out[:, 0, 1], out[:, 0, 2] = 1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)
+    out[:, 1, 0], out[:, 1, 1], out[:, 1, 2] = 2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)
+    out[:, 2, 0], out[:, 2, 1], out[:, 2, 2] = 2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)
+    return out
+
+
+def rotationLattice(n):
+    """``n`` rotation matrices, (n, 3, 3) float64, from a deterministic near-uniform lattice on SO(3): the super-Fibonacci spiral of unit
+    quaternions (Alexa, CVPR 2022).  For i = 0 .. n-1 with s = i + 1/2, t = s / n, d = 2 pi s: q = (sqrt(t) sin(d / sqrt 2), sqrt(t) cos(d / sqrt 2),
+    sqrt(1 - t) sin(d / psi), sqrt(1 - t) cos(d / psi)) as (x, y, z, w), psi = 1.533751168755204288118041 (the root of psi^4 = psi + 4), normalised
+    once more in fp64.  No table and no random draw: the same matrices on every host.  Index 0 is NOT the identity: it is the first point of
+    the spiral (for n = 1 a rotation by about 142 degrees); list the identity yourself where a search must contain it."""
+    n = int(n)
+    s = np.arange(n, dtype=np.float64) + 0.5
+    t, d = s / float(max(n, 1)), 2.0 * np.pi * s
+    r, big = np.sqrt(t), np.sqrt(1.0 - t)
+    alpha, beta = d / np.sqrt(2.0), d / 1.533751168755204288118041
+    q = np.stack([r * np.sin(alpha), r * np.cos(alpha), big * np.sin(beta), big * np.cos(beta)], axis=1)
+    q /= np.sqrt((q * q).sum(axis=1))[:, None]
+    return _quaternionMatrices(q)
+
+
+def rotationsNear(R, angle, n):
+    """``n`` rotations within ``angle`` (radians) of the rotation ``R``, (n, 3, 3), deterministic, ``R`` itself first.  Entry j >= 1 is D_j R: D_j
+    turns by angle * (j / (n - 1))^(1/3) (the radii that fill a ball evenly) about direction j - 1 of ``sphereLattice(n - 1)``, as a unit
+    quaternion, so the angle between entry j and ``R`` is exactly D_j's."""
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    n = int(n)
+    if n <= 1:
+        return R[None, :, :].copy()
+    axes = sphereLattice(n - 1)
+    theta = float(angle) * np.cbrt(np.arange(1, n, dtype=np.float64) / float(n - 1))
+    q = np.concatenate([axes * np.sin(0.5 * theta)[:, None], np.cos(0.5 * theta)[:, None]], axis=1)
+    q /= np.sqrt((q * q).sum(axis=1))[:, None]
+    return np.concatenate([R[None, :, :], np.einsum("nij,jk->nik", _quaternionMatrices(q), R)])
+
+
+def rotationAngle(a, b):
+    """The angle (radians) of the rotation that carries ``a`` to ``b`` (3x3 each; ``a`` may be (n, 3, 3))."""
+    trace = np.einsum("...ij,ij->...", np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64).reshape(3, 3))
+    return np.arccos(np.clip(0.5 * (trace - 1.0), -1.0, 1.0))
+
+
+def fragmentFrame(xyz, weights=None):
+    """A rigid fragment in its own frame: a dict ``xyz`` (n, 3: the coordinates relative to the weighted centroid, the pivot of its rotations),
+    ``weights`` (n,; ones when None), ``centroid`` (3,) and ``radius`` (max_a sqrt((x x + y y) + z z): what ``pdbeda_pose_scores`` sizes a centre's
+    box by).  Weights that sum to zero fall back to the plain centroid."""
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    w = np.ones(len(xyz)) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != len(xyz):
+        raise ValueError("weights must have one value per atom")
+    total = float(w.sum())
+    centroid = (xyz * w[:, None]).sum(axis=0) / total if total != 0.0 else xyz.mean(axis=0)
+    rel = xyz - centroid
+    return {"xyz": rel, "weights": w, "centroid": centroid, "radius": float(np.sqrt((rel[:, 0] * rel[:, 0] + rel[:, 1] * rel[:, 1]) + rel[:, 2] * rel[:, 2]).max()) if len(rel) else 0.0}
+
+
+_fmaElementwise = np.frompyfunc(_fma, 3, 1)
+
+
+def placeFragment(frame, centre, R):
+    """The coordinates (n, 3) of the pose (``centre``, ``R``) of a ``fragmentFrame`` (or of an (n, 3) array of pivot-relative coordinates),
+    evaluated as the device evaluates them: p[i] = centre[i] + fma(R[i][2], x[2], fma(R[i][0], x[0], R[i][1] * x[1])), the add unfused."""
+    x = np.asarray(frame["xyz"] if isinstance(frame, dict) else frame, dtype=np.float64).reshape(-1, 3)
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    c = np.asarray(centre, dtype=np.float64).reshape(3)
+    out = np.empty_like(x)
+    for i in range(3):
+        dot = _fmaElementwise(R[i, 2], x[:, 2], _fmaElementwise(R[i, 0], x[:, 0], R[i, 1] * x[:, 1])).astype(np.float64) if len(x) else 0.0
+        out[:, i] = c[i] + dot
+    return out
+
+
 def qScoreTables(sigma=0.6, step=0.1, nShells=21, nPoints=8, nLevels=4):
     """What the host hands ``pdbeda_atom_qscores``: (ref, unit_pts, level_offsets).  ref[k] = exp(-0.5 (k step32 / sigma)^2) with
     step32 = float(float32(step)), the radius the device uses; level l is ``sphereLattice(nPoints * 2**l)``."""
@@ -899,6 +976,64 @@ class DensityMatrix(object):
         ``counters`` (the shift S of the integer sums, the voxels of the largest box, the atoms whose box the domain clipped).  Results
         are the same bits in every run and for every order of the atoms.  ``gaussianAtomGradients`` turns them into derivatives."""
         return self._map.atom_moments(xyz, expo, radii, uniqueBox)
+
+    # -- what fits in a blob: rigid-fragment pose search (no reference counterpart) --
+    def poseScores(self, fragXyz, weights, rotations, centres, topK=1, floor=-np.inf, maxLow=None, allowOutside=False, full=False):
+        """Every pose (centre, rotation) of a rigid fragment scored on THIS map in one device call (``pdbeda_pose_scores`` in include/pdbeda.h
+        has the contract).  ``fragXyz`` (n, 3) is relative to the pivot (``fragmentFrame``), ``rotations`` (n_rot, 3, 3) come from
+        ``rotationLattice`` / ``rotationsNear``.  The score of a pose is sum_a weights[a] * (the trilinear density at atom a); a pose is rejected
+        when more than ``maxLow`` atoms read less than ``floor`` (None: no limit), when its score is NaN, or -- unless ``allowOutside`` -- when
+        an atom reads a voxel that is not stored.  A dict ``bestRot`` / ``bestScore`` / ``bestLow`` ((n_centres, topK): a centre's kept poses,
+        best first; ties go to the lower rotation index; -1 / 0.0 / 0 beyond them), ``nKept`` (n_centres,), with ``full`` also ``scores`` /
+        ``low`` / ``kept`` ((n_centres, n_rot)), and ``counters`` (centres that read the map directly, the largest staged box, rejected
+        poses).  The same bits in every run; permuting the centres permutes the rows."""
+        w = np.ones(len(np.asarray(fragXyz).reshape(-1, 3))) if weights is None else weights
+        return self._map.pose_scores(fragXyz, w, rotations, centres, topK, floor, maxLow, allowOutside, full)
+
+    def searchFragment(self, fragXyz, weights, centres, rotations=None, nRotations=4096, nBest=3, levels=4, nNear=256, nCloud=27, angle=None,
+                       floor=-np.inf, maxLow=None, allowOutside=False):
+        """Coarse-to-fine pose search with ``poseScores``, every level ONE device call.  Level 0 scores ``rotations`` (default
+        ``rotationLattice(nRotations)``) at every centre and keeps the ``nBest`` best poses over all centres.  Each later level, for every pose
+        kept so far, scores ``rotationsNear(R, angle_l, nNear)`` (the pose's own rotation first) at a cloud of ``nCloud`` centres -- the pose's
+        own centre first, then a cubic lattice of half-width step_l around it; the levels' calls are batched into one by listing all
+        clouds' centres against all poses' rotations and reading each pose's own block.  angle_l and step_l halve from level to level, starting at
+        ``angle`` (default: the lattice's spacing, (16 pi^2 / n_rot)^(1/3), capped at pi) and half a grid step.  A refined pose replaces
+        its parent only if its score is NOT lower.  It stops after ``levels`` levels.  Returns a list of dicts, best first: ``centre``, ``rotation``,
+        ``score``, ``low``, ``xyz`` (the placed atoms, ``placeFragment``) and ``trace`` (the score after every level, level 0 first)."""
+        frag = np.asarray(fragXyz, dtype=np.float64).reshape(-1, 3)
+        w = np.ones(len(frag)) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+        centres = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+        rot = rotationLattice(nRotations) if rotations is None else np.asarray(rotations, dtype=np.float64).reshape(-1, 3, 3)
+        rule = dict(floor=floor, maxLow=maxLow, allowOutside=allowOutside)
+        first = self.poseScores(frag, w, rot, centres, topK=min(int(nBest), _native.POSE_MAX_TOP), **rule)
+        rows = [(float(first["bestScore"][c, k]), c, k) for c in range(len(centres)) for k in range(first["bestRot"].shape[1]) if first["bestRot"][c, k] >= 0]
+        rows.sort(key=lambda r: (-r[0], r[1], r[2]))
+        poses = [{"centre": centres[c].copy(), "rotation": rot[first["bestRot"][c, k]].copy(), "score": s, "low": int(first["bestLow"][c, k]), "trace": [s]}
+                 for s, c, k in rows[:int(nBest)]]
+        theta = min(np.pi, (16.0 * np.pi ** 2 / max(len(rot), 1)) ** (1.0 / 3.0)) if angle is None else float(angle)
+        step = 0.5 * float(min(self.header.gridLength))
+        side = max(1, int(round(int(nCloud) ** (1.0 / 3.0))))
+        ticks = (np.arange(side, dtype=np.float64) - 0.5 * (side - 1)) / max(0.5 * (side - 1), 1.0)
+        cloud = np.array([[a, b, c] for a in ticks for b in ticks for c in ticks if (a, b, c) != (0.0, 0.0, 0.0)], dtype=np.float64).reshape(-1, 3)
+        for _ in range(int(levels)):
+            if not poses:
+                break
+            near = [rotationsNear(p["rotation"], theta, nNear) for p in poses]
+            around = [np.concatenate([p["centre"][None, :], p["centre"] + step * cloud]) for p in poses]
+            m, per = len(near[0]), len(around[0])
+            got = self.poseScores(frag, w, np.concatenate(near), np.concatenate(around), full=True, **rule)
+            for j, p in enumerate(poses):      # pose j's own block of the table: its centres against its rotations
+                block = np.where(got["kept"][j * per:(j + 1) * per, j * m:(j + 1) * m], got["scores"][j * per:(j + 1) * per, j * m:(j + 1) * m], -np.inf)
+                c, r = np.unravel_index(int(np.argmax(block)), block.shape)      # (the first maximum: the pose itself on a tie)
+                if block[c, r] >= p["score"] and block[c, r] > -np.inf:
+                    p["centre"], p["rotation"], p["score"] = around[j][c].copy(), near[j][r].copy(), float(block[c, r])
+                    p["low"] = int(got["low"][j * per + c, j * m + r])
+                p["trace"].append(p["score"])
+            theta, step = 0.5 * theta, 0.5 * step
+        poses.sort(key=lambda p: -p["score"])
+        for p in poses:
+            p["xyz"] = placeFragment(frag, p["centre"], p["rotation"])
+        return poses
 
     def _leastSquaresTarget(self, model):
         """(T, scale, offset, cc) of this map against ``model`` over the non-repeating box: T = sum (self - scale model - offset)^2 / 2 at

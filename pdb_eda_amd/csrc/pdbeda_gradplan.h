@@ -81,19 +81,28 @@ struct GradBox {
     int32_t lo[3];
     int32_t n[3];
 };
+// The covering range of crs axis k BEFORE any clipping, as doubles: voxels ceil(f - w) .. floor(f + w) (f, h and the widening w of the proof above).
+// false: the grid position or the half-width is not finite.  (pdbeda_poseplan.h builds its unclipped, wrap-aware box on this.)
+static inline bool grad_span(const GradGrid &g, const double xyz[3], double radius, int k, double *first, double *last) {
+    const double t0 = g.rows[3 * k] * xyz[0], t1 = g.rows[3 * k + 1] * xyz[1], t2 = g.rows[3 * k + 2] * xyz[2];
+    const double f = ((t0 + t1) + t2) + g.off[k];
+    const double h = radius * g.norm[k];
+    const double mag = (((std::fabs(t0) + std::fabs(t1)) + std::fabs(t2)) + std::fabs(g.off[k])) + (h + 1.0);
+    const double w = h + GP_PAD * mag;
+    if (!std::isfinite(f) || !std::isfinite(w)) return false;
+    *first = std::ceil(f - w);
+    *last = std::floor(f + w);
+    return true;
+}
 // *clipped: the covering box reaches beyond the domain on some axis (an atom wholly outside included).  Returns the box's voxels.
 static inline int64_t grad_box(const GradGrid &g, const double xyz[3], double radius, GradBox *box, bool *clipped) {
     double lo[3], hi[3];
     bool empty = false;
     *clipped = false;
     for (int k = 0; k < 3; ++k) {
-        const double t0 = g.rows[3 * k] * xyz[0], t1 = g.rows[3 * k + 1] * xyz[1], t2 = g.rows[3 * k + 2] * xyz[2];
-        const double f = ((t0 + t1) + t2) + g.off[k];
-        const double h = radius * g.norm[k];
-        const double mag = (((std::fabs(t0) + std::fabs(t1)) + std::fabs(t2)) + std::fabs(g.off[k])) + (h + 1.0);
-        const double w = h + GP_PAD * mag;
-        if (!std::isfinite(f) || !std::isfinite(w)) { empty = true; *clipped = true; lo[k] = 0.0; hi[k] = -1.0; continue; }
-        const double first = std::ceil(f - w), last = std::floor(f + w), top = (double)g.dom[k] - 1.0;
+        double first = 0.0, last = 0.0;
+        if (!grad_span(g, xyz, radius, k, &first, &last)) { empty = true; *clipped = true; lo[k] = 0.0; hi[k] = -1.0; continue; }
+        const double top = (double)g.dom[k] - 1.0;
         if (first < 0.0 || last > top) *clipped = true;
         lo[k] = std::max(first, 0.0);
         hi[k] = std::min(last, top);

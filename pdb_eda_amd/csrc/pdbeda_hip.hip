@@ -42,6 +42,7 @@
 #include "pdbeda_model.h"
 #include "pdbeda_partition.h"
 #include "pdbeda_peaks.h"
+#include "pdbeda_pose.h"
 #include "pdbeda_profiles.h"
 #include "pdbeda_qscore.h"
 #include "pdbeda_resample.h"
@@ -3696,6 +3697,92 @@ extern "C" int pdbeda_atom_moments(pdbeda_map *weight, const double *xyz, int64_
     });
     if (rc) return rc;
     if (counters) { counters[0] = S; counters[1] = v_max; counters[2] = n_clipped; }
+    return PDBEDA_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// What fits in a blob: rigid-fragment poses scored on a map (no reference counterpart; the contract: include/pdbeda.h, the plan: pdbeda_poseplan.h)
+// ------------------------------------------------------------------------------------
+// A staged box may take more dynamic LDS than the 64 KiB a kernel gets unasked: told to the runtime once per process.
+static hipError_t pose_lds_allowance() {
+    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pose_scores), hipFuncAttributeMaxDynamicSharedMemorySize, POSE_LDS_BUDGET);
+    return e;
+}
+
+// The launch graph: the host's checks and boxes (pdbeda_poseplan.h); the fragment, its weights and the rotations in one row of scratch, once; then per chunk
+// of centres (pose_chunk: the score table stays within POSE_TABLE_BYTES) the chunk's centres and boxes, k_pose_scores -- a workgroup per centre, dynamic LDS
+// for the chunk's largest staged box --, the requested rows and tables, and a wait.
+extern "C" int pdbeda_pose_scores(pdbeda_map *map, const double *frag_xyz, const double *frag_w, int32_t n_frag, const double *rot, int64_t n_rot, const double *centres,
+                                  int64_t n_centres, float floor, int32_t max_low, int32_t top_k, uint32_t flags, int32_t *best_rot, double *best_score, int32_t *best_low,
+                                  int32_t *n_kept, double *all_score, int32_t *all_low, uint8_t *all_kept, int64_t counters[3]) {
+    if (!map || !frag_xyz || !frag_w || !rot || (n_centres > 0 && !centres)) return PDBEDA_ERR_ARGUMENT;
+    pdbeda_ctx *ctx = map->ctx;
+    int64_t bad = -1;
+    double radius = 0.0;
+    switch (pose_check(frag_xyz, frag_w, n_frag, rot, n_rot, centres, n_centres, top_k, flags, PDBEDA_POSE_ALLOW_OUTSIDE | PDBEDA_POSE_GLOBAL_ONLY, &bad, &radius)) {
+    case POSE_ATOMS: return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: n_frag must be 1 .. %d", PDBEDA_POSE_MAX_ATOMS);
+    case POSE_ROTATIONS: return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: n_rot must be 1 .. %d", PDBEDA_POSE_MAX_ROTATIONS);
+    case POSE_TOP: return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: top_k must be 1 .. %d", PDBEDA_POSE_MAX_TOP);
+    case POSE_FLAG: return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: unknown flag 0x%x", flags);
+    case POSE_COUNT: return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: a negative number of centres, or n_centres * n_rot is 2^31 or more");
+    case POSE_FRAG_VALUE: return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: a coordinate or the weight of fragment atom %lld is not finite", (long long)bad);
+    case POSE_ROT_VALUE: return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: an entry of rotation %lld is not finite", (long long)bad);
+    case POSE_CENTRE_VALUE: return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: a coordinate of centre %lld is not finite", (long long)bad);
+    default: break;
+    }
+    if (n_centres == 0) return PDBEDA_OK;
+    const Geom &g = map->geom;
+    const GradGrid gg = grad_grid_of(g, false);
+    if (!grad_reach_ok(gg, radius)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: the fragment's radius spans 2^29 grid steps or more");
+    for (int64_t i = 0; i < n_centres; ++i)
+        if (!pose_centre_ok(gg, centres + 3 * i)) return fail(ctx, PDBEDA_ERR_ARGUMENT, "pose scores: centre %lld lies 2^29 grid steps or more from the map's origin", (long long)i);
+    const bool global_only = (flags & PDBEDA_POSE_GLOBAL_ONLY) != 0;
+    std::vector<PoseBox> boxes((size_t)n_centres);
+    int64_t n_global = 0, top_box = 0;
+    for (int64_t i = 0; i < n_centres; ++i) {
+        const int64_t vox = pose_box(gg, centres + 3 * i, radius, global_only, &boxes[(size_t)i]);
+        if (boxes[(size_t)i].staged) top_box = std::max(top_box, vox); else ++n_global;
+    }
+    if (ctx->timed_out) return PDBEDA_ERR_TIMEOUT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (pose_lds_bytes(top_box) > 64 * 1024) HIP_TRY(ctx, pose_lds_allowance());
+    const int64_t chunk = pose_chunk(n_centres, n_rot);
+    const size_t nf = (size_t)n_frag, nr = (size_t)n_rot, k = (size_t)top_k;
+    std::vector<int32_t> kept_of((size_t)n_centres);
+    PoseScratch sc;
+    const int rc = with_scratch(ctx, "pose scores", [&](Carver &cv) { sc.carve(cv, n_frag, n_rot, chunk, top_k); }, [&]() -> int {
+        const H2DItem in[3] = {{sc.frag, frag_xyz, 24 * nf}, {sc.w, frag_w, 8 * nf}, {sc.rot, rot, 72 * nr}};
+        HIP_TRY(ctx, h2d_row(ctx, in, 3));
+        for (int64_t c0 = 0; c0 < n_centres; c0 += chunk) {
+            const size_t ch = (size_t)std::min(chunk, n_centres - c0), at = (size_t)c0;
+            const H2DItem per[2] = {{sc.centres, centres + 3 * c0, 24 * ch}, {sc.box, boxes.data() + c0, sizeof(PoseBox) * ch}};
+            HIP_TRY(ctx, h2d_row(ctx, per, 2));
+            int64_t lds_box = 0;
+            for (size_t i = 0; i < ch; ++i)
+                if (boxes[at + i].staged) lds_box = std::max<int64_t>(lds_box, (int64_t)boxes[at + i].n[0] * boxes[at + i].n[1] * boxes[at + i].n[2]);
+            PoseArgs a;
+            a.geom = map->geom_dev; a.dens = map->dens;
+            a.frag = sc.frag; a.w = sc.w; a.rot = sc.rot; a.centres = sc.centres; a.box = sc.box;
+            a.n_frag = n_frag; a.n_rot = (int)n_rot; a.top_k = top_k;
+            a.floor_d = (double)floor; a.max_low = max_low; a.allow_outside = (flags & PDBEDA_POSE_ALLOW_OUTSIDE) ? 1 : 0;
+            a.score = sc.score; a.low = sc.low; a.kept = sc.kept;
+            a.best_rot = sc.best_rot; a.best_score = sc.best_score; a.best_low = sc.best_low; a.n_kept = sc.n_kept;
+            { PROF(ctx, "k_pose_scores"); hipLaunchKernelGGL(k_pose_scores, dim3((unsigned)ch), dim3(256), (size_t)pose_lds_bytes(lds_box), ctx->stream, a); }
+            HIP_TRY(ctx, hipGetLastError());
+            const D2HItem parts[7] = {{best_rot ? best_rot + at * k : nullptr, sc.best_rot, 4 * ch * k}, {best_score ? best_score + at * k : nullptr, sc.best_score, 8 * ch * k},
+                                      {best_low ? best_low + at * k : nullptr, sc.best_low, 4 * ch * k}, {kept_of.data() + at, sc.n_kept, 4 * ch},
+                                      {all_score ? all_score + at * nr : nullptr, sc.score, 8 * ch * nr}, {all_low ? all_low + at * nr : nullptr, sc.low, 4 * ch * nr},
+                                      {all_kept ? all_kept + at * nr : nullptr, sc.kept, ch * nr}};
+            HIP_TRY(ctx, d2h_each(ctx, parts, 7));
+            if (c0 + chunk < n_centres) HIP_TRY(ctx, ctx_sync(ctx));      // (the next chunk writes the same table: this one's copies are done first)
+        }
+        return 0;
+    });
+    if (rc) return rc;
+    int64_t rejected = 0;
+    for (int64_t i = 0; i < n_centres; ++i) rejected += n_rot - kept_of[(size_t)i];
+    if (n_kept) memcpy(n_kept, kept_of.data(), 4 * (size_t)n_centres);
+    if (counters) { counters[0] = n_global; counters[1] = top_box; counters[2] = rejected; }
     return PDBEDA_OK;
 }
 

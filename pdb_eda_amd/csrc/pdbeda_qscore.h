@@ -27,7 +27,9 @@ static constexpr int QS_STAGE = 128;      // neighbours a wave stages: 3 KB of c
 
 // Corner values -> the interpolant: the fp32 corners are promoted first; c, then r, then s; t == 0 returns the base corner exactly whenever the
 // other corner is finite (0 * finite = 0).  *valid: all eight corners are stored, whatever their weights.
-__device__ inline double interp_trilinear(const Geom &g, const float *__restrict__ dens, const double f[3], bool *valid) {
+// (Fetch: (c, r, s, bool *stored) -> float.  fetch_wrapped for the map itself; k_pose_scores reads a staged copy of the same floats and flags.)
+template <typename Fetch>
+__device__ inline double interp_trilinear_through(const Fetch &fetch, const double f[3], bool *valid) {
     const double fl[3] = {floor(f[0]), floor(f[1]), floor(f[2])};
     const int32_t b[3] = {(int32_t)fl[0], (int32_t)fl[1], (int32_t)fl[2]};
     const double t[3] = {f[0] - fl[0], f[1] - fl[1], f[2] - fl[2]};
@@ -35,7 +37,7 @@ __device__ inline double interp_trilinear(const Geom &g, const float *__restrict
     bool all = true;
     for (int k = 0; k < 8; ++k) {
         bool ok;
-        v[k] = (double)fetch_wrapped(g, dens, b[0] + (k & 1), b[1] + ((k >> 1) & 1), b[2] + (k >> 2), &ok);
+        v[k] = (double)fetch(b[0] + (k & 1), b[1] + ((k >> 1) & 1), b[2] + (k >> 2), &ok);
         all = all && ok;
     }
     *valid = all;
@@ -43,6 +45,9 @@ __device__ inline double interp_trilinear(const Geom &g, const float *__restrict
     const double c01 = v[4] + t[0] * (v[5] - v[4]), c11 = v[6] + t[0] * (v[7] - v[6]);
     const double r0 = c00 + t[1] * (c10 - c00), r1 = c01 + t[1] * (c11 - c01);
     return r0 + t[2] * (r1 - r0);
+}
+__device__ inline double interp_trilinear(const Geom &g, const float *__restrict__ dens, const double f[3], bool *valid) {
+    return interp_trilinear_through([&](int32_t c, int32_t r, int32_t s, bool *ok) { return fetch_wrapped(g, dens, c, r, s, ok); }, f, valid);
 }
 
 __global__ void __launch_bounds__(256) k_interp_density(const Geom *__restrict__ geom, const float *__restrict__ dens, const double *__restrict__ xyz, int64_t n,

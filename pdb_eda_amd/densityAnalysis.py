@@ -40,6 +40,10 @@ modelBlur = 0.0
 modelSigmas = ccp4.MODEL_N_SIGMA
 refineCycles = 5          # cycles of ``refineAtoms`` / the "refine" mode
 refineMaxShift = 0.3      # A: the longest shift of an atom in one refinement cycle
+fitRotations = 4096       # rotations of the lattice pass of ``fitFragment`` / the "fit" mode
+fitPenaltyCutoffs = 3.0   # the clash penalty of ``fitFragment``, in units of the Fo-Fc map's ``diffDensityCutoff``
+fitMinVolumePerAtom = 0.5   # A^3 of blob per fragment atom below which ``calculateBlobFits`` skips a blob
+fitMaxCentres = 2000      # the most voxel centres of a blob that ``fitFragment`` tries (a larger blob is thinned evenly)
 
 # the local statistics of a map: the Gaussian window's standard deviation (A) and cut-off (standard deviations), and the floor under a local
 # standard deviation as a fraction of the whole map's stdDensity (a flat solvent region must not turn rounding noise into z-scores)
@@ -127,6 +131,26 @@ def _attachCutoffs(densityObj, diffDensityObj):
 def residueAtomName(atom):
     """ref densityAnalysis.py:1243-1252."""
     return atom.parent.resname.strip() + '_' + atom.name
+
+
+def fragmentFromResidue(residue):
+    """A rigid fragment from the object model: a dict ``xyz`` (n, 3) float64, ``electrons`` (n,: the parameter tables' electrons of
+    'RES_ATOM' times the occupancy; an atom the tables do not know counts by its element's atomic number, 6 when that is unknown too),
+    ``elements`` and ``names`` -- what ``DensityAnalysis.fitFragment`` takes.  Atoms of occupancy 0 are left out."""
+    _requireParams()
+    numbers = {"H": 1.0, "C": 6.0, "N": 7.0, "O": 8.0, "F": 9.0, "NA": 11.0, "MG": 12.0, "P": 15.0, "S": 16.0, "CL": 17.0, "K": 19.0, "CA": 20.0, "FE": 26.0, "ZN": 30.0}
+    xyz, electrons, elements, names = [], [], [], []
+    for atom in residue.child_list:
+        if float(atom.occupancy) == 0.0:
+            continue
+        name = residueAtomName(atom)
+        z = fullAtomNameMapElectronsGlobal.get(name) if fullAtomNameMapElectronsGlobal else None
+        element = (getattr(atom, "element", "") or "").strip().upper()
+        xyz.append(np.asarray(atom.coord, dtype=np.float64))
+        electrons.append((float(z) if z is not None else numbers.get(element, 6.0)) * float(atom.occupancy))
+        elements.append(element)
+        names.append(atom.name)
+    return {"xyz": np.array(xyz, dtype=np.float64).reshape(-1, 3), "electrons": np.array(electrons, dtype=np.float64), "elements": elements, "names": names}
 
 
 class SymAtom(object):
@@ -431,6 +455,7 @@ class DensityAnalysis(object):
     atomModelCorrelationHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'rscc_model', 'rsr_model']
     atomGradientHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'dT_dx', 'dT_dy', 'dT_dz', 'dT_dB', 'dT_docc',
                           'shift_x', 'shift_y', 'shift_z', 'shift_b', 'shift_occ', 'num_voxels']
+    blobFitHeader = ['blob_index', 'blob_num_voxels', 'rank', 'centre', 'rotation', 'score', 'low_atoms', 'rscc', 'xyz']
     refineAtomHeader = ['model', 'chain', 'residue_number', 'residue_name', "atom_name", "occupancy", 'bfactor', 'refined_x', 'refined_y', 'refined_z', 'refined_bfactor',
                         'refined_occupancy', 'shift', 'delta_b']
     residueModelCorrelationHeader = ['model', 'chain', 'residue_number', 'residue_name', "mean_occupancy", 'rscc_model', 'rsr_model']
@@ -1721,6 +1746,102 @@ class DensityAnalysis(object):
         return {"num_atoms": len(atoms["atomRows"]), "cycles": len(trace["halvings"]), "target_before": trace["T"][0], "target_after": trace["T"][-1],
                 "cc_before": trace["cc"][0], "cc_after": trace["cc"][-1], "scale_before": trace["scale"][0], "scale_after": trace["scale"][-1],
                 "rms_shift": float(np.sqrt(((out["xyz"] - atoms["xyz"]) ** 2).sum() / n)), "rms_delta_b": float(np.sqrt(((out["bfactors"] - atoms["bfactors"]) ** 2).sum() / n))}
+
+    # ---- what fits in a green blob: rigid-fragment pose search on the Fo-Fc map (no reference counterpart) ----
+    def _fitScoreMap(self, penalty):
+        """The map a fragment is scored on: Fo-Fc - penalty * ``atomMask`` of ALL symmetry atoms (van der Waals spheres, ``ccp4.maskRadii`` by
+        element), made by the existing ``atomMask`` and ``pdbeda_map_combine`` calls as a resident map, kept per penalty."""
+        key = ("fitScore", float(penalty))
+        if key not in self._local:
+            diff = self.diffDensityObj
+            if penalty == 0.0:
+                self._local[key] = diff
+            else:
+                cols = _structure.columns(self.biopdbObj)
+                rows = np.asarray(self.symmetryAtoms._idx, dtype=np.int64)
+                coords = np.asarray(self.symmetryAtomCoords, dtype=np.float64).reshape(-1, 3)
+                elements = [getattr(cols.atoms[r], "element", "") or "" for r in rows]
+                mask = diff.atomMask(coords, ccp4.maskRadii(elements) if len(rows) else np.zeros(0))
+                self._local[key] = ccp4.DensityMatrix.fromDeviceMap(diff.header, diff.origin, type(diff._map).combine(diff._map, mask._map, -float(penalty)), diff.pdbid, diff._ctx)
+        return self._local[key]
+
+    def _blobCentres(self, blob):
+        """The voxel centres of a blob, thinned evenly to ``fitMaxCentres``."""
+        crs = np.asarray(sorted(blob.crsList), dtype=np.int64).reshape(-1, 3)
+        if len(crs) > fitMaxCentres:
+            crs = crs[np.linspace(0, len(crs) - 1, fitMaxCentres).astype(np.int64)]
+        return np.asarray(self.diffDensityObj.header.crs2xyz_array(crs), dtype=np.float64).reshape(-1, 3)
+
+    def fitFragment(self, fragment, blob=None, centres=None, nRotations=None, topK=5, penalty=None, refine=True):
+        """Where a rigid ``fragment`` (``fragmentFromResidue``, or a dict ``xyz`` / ``electrons``) sits best in unexplained density: every pose
+        (centre, rotation) is scored on the device (``DensityMatrix.searchFragment`` / ``pdbeda_pose_scores``) by sum_a electrons_a * rho(atom a) on
+        the SCORE MAP, Fo-Fc minus ``penalty`` times the ``atomMask`` of the symmetry atoms.  Clash avoidance therefore costs no kernel code; the
+        interpolation smears the mask's edge over one voxel, so it is a SOFT penalty: an atom half a voxel inside a neighbour's sphere pays about
+        half of it.  ``centres`` default to the voxel centres of ``blob`` (a green blob or its index in ``greenBlobList``; None: the largest), or
+        pass the blob's peaks.  ``penalty`` defaults to ``fitPenaltyCutoffs`` Fo-Fc cut-offs.  The lattice pass scores ``nRotations``
+        (``fitRotations``) rotations at every centre; with ``refine`` the ``topK`` best poses are polished coarse to fine, every level one device
+        call.  Returns ``topK`` rows at the most, best first (``blobFitHeader`` without its two leading blob columns): rank, centre, rotation (9
+        numbers, row-major), score, the atoms that read below 0 on the score map, the RSCC of the placed fragment -- its ``modelDensity`` (B 20,
+        the module's blur) against the Fo-Fc map where the model exceeds 0 (``correlate``) --, and the placed coordinates."""
+        frame = ccp4.fragmentFrame(fragment["xyz"], fragment.get("electrons"))
+        if centres is None:
+            blobs = self.greenBlobList
+            if blob is None:
+                if not len(blobs):
+                    return []
+                blob = max(range(len(blobs)), key=lambda i: blobs[i].numVoxels)
+            centres = self._blobCentres(blobs[blob] if isinstance(blob, (int, np.integer)) else blob)
+        centres = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+        if not len(centres) or not len(frame["xyz"]):
+            return []
+        diff = self.diffDensityObj
+        cutoff = float(diff.diffDensityCutoff)
+        score = self._fitScoreMap(fitPenaltyCutoffs * cutoff if penalty is None else float(penalty))
+        n_rot = int(fitRotations if nRotations is None else nRotations)
+        poses = score.searchFragment(frame["xyz"], frame["weights"], centres, nRotations=n_rot, nBest=int(topK), levels=4 if refine else 0, floor=0.0, allowOutside=True)
+        rows = []
+        z = np.asarray(frame["weights"], dtype=np.float64)
+        amp, expo, bEff = ccp4.gaussianAtomTerms(z, np.full(len(z), 20.0), np.ones(len(z)), blur=modelBlur)
+        radii = ccp4.modelRadii(bEff, modelSigmas)
+        for rank, pose in enumerate(poses):
+            fit = diff.correlate(diff.modelDensity(pose["xyz"], amp, expo, radii), floor=0.0)
+            rscc = None if fit["cc"] != fit["cc"] else float(fit["cc"])
+            rows.append([rank, [float(v) for v in pose["centre"]], [float(v) for v in pose["rotation"].reshape(-1)], float(pose["score"]), int(pose["low"]), rscc,
+                         [[float(v) for v in p] for p in pose["xyz"]]])
+        return rows
+
+    def calculateBlobFits(self, fragment, minElectrons=None, topK=1, **kw):
+        """``fitFragment`` over every green blob large enough to hold the fragment: one row per blob and rank (``blobFitHeader``).  A blob
+        is large enough when its volume is at least ``fitMinVolumePerAtom`` (half a cubic Angstrom: the core a 3 sigma contour leaves of an atom
+        is a few times that; specks of noise are far below it) times the fragment's atoms, or, with ``minElectrons``, when its density
+        integrates to that many electrons (``densityElectronRatio``, which needs the atom clouds)."""
+        blobs = self.greenBlobList
+        n_atoms = len(np.asarray(fragment["xyz"]).reshape(-1, 3))
+        voxel = float(self.diffDensityObj.header.unitVolume)
+        out = []
+        for i in range(len(blobs)):
+            blob = blobs[i]
+            if minElectrons is None:
+                enough = blob.numVoxels * voxel >= n_atoms * fitMinVolumePerAtom
+            else:
+                if not self.densityElectronRatio:
+                    raise RuntimeError("Failed to calculate densityElectronRatio, probably due to total aggregated electrons less than the minimum.")
+                enough = abs(blob.totalDensity / self.densityElectronRatio) >= float(minElectrons)
+            if enough:
+                out += [[i, int(blob.numVoxels)] + row for row in self.fitFragment(fragment, blob=i, topK=topK, **kw)]
+        return out
+
+    def defaultFitFragment(self, resname=""):
+        """The fragment of the "fit" mode: the first residue of the structure called ``resname``; by default the first hetero residue that is
+        not water, else the first residue."""
+        residues = list(self.biopdbObj.get_residues())
+        if resname:
+            named = [r for r in residues if r.resname.strip() == resname.strip()]
+        else:
+            named = [r for r in residues if r.id[0].strip() not in ("", "W")] or residues
+        if not named:
+            raise ValueError("no residue %r in the structure to take the fragment from" % resname)
+        return fragmentFromResidue(named[0])
 
     # ---- local statistics: significance against the surroundings, local map-model correlation (no reference counterpart) ----
     def _localTaps(self, densityObj):

@@ -14,7 +14,7 @@ import numpy
 
 from . import densityAnalysis
 
-MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore", "model", "local", "fourier", "mask", "refine")
+MODES = ("cloud", "density", "difference", "blob", "statistics", "peak", "profile", "partition", "shape", "dipole", "basin", "qscore", "model", "local", "fourier", "mask", "refine", "fit")
 
 
 def numpyConverter(obj):
@@ -228,6 +228,8 @@ TABLES = {
     # (no reference counterpart: real-space refinement of the deposited atoms against the 2Fo-Fc map, x, y, z and B; no option applies)
     ("refine", "atom"): (lambda an: _DA.refineAtomHeader, lambda an, o: an.refineAtoms()),
     ("refine", "summary"): (lambda an: list(_REFINE_SUMMARY), _refineSummaryTable),
+    # (no reference counterpart: a rigid fragment -- a residue of the structure, named by ``type`` -- tried in every green blob that can hold it; blob: the best pose per blob)
+    ("fit", "blob"): (lambda an: _DA.blobFitHeader, lambda an, o: an.calculateBlobFits(an.defaultFitFragment(o["type"]))),
     ("statistics", "residue"): (lambda an: an.residueMetricsHeaderList, lambda an, o: an.residueMetrics()),
     ("statistics", "atom"): (lambda an: an.atomMetricsHeaderList, lambda an, o: _plainColumns(an.atomMetrics(), **_SYM)),
 }
@@ -237,9 +239,9 @@ def rows(analyzer, mode, level="atom", radius=None, numSD=None, type="", atomMas
          includePdbid=False, shells=20):
     """(headerList, rowList) of one ``pdb_eda single`` sub-mode, looked up in ``TABLES``.
 
-    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore | model | local | fourier | mask | refine;  level: atom | residue | domain | symmetry-atom
+    mode: cloud | density | difference | blob | statistics | peak | profile | partition | shape | dipole | basin | qscore | model | local | fourier | mask | refine | fit;  level: atom | residue | domain | symmetry-atom
     (the reference's --atom / --residue / --domain / --symmetry-atom; ignored by blob, peak, basin, shape and dipole) | atom-type (profile) | summary | blob
-    (partition) | summary (qscore: atom | residue | summary, no other option applies; model: atom | residue | summary, ``radius`` is the sphere's, by default the one of the statistics mode; local: atom | residue | summary under the module's window, no other option applies; fourier: shell | summary, ``shells`` resolution shells; mask: shell | summary, ``shells`` resolution shells; refine: atom | summary, no option applies);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
+    (partition) | summary (qscore: atom | residue | summary, no other option applies; model: atom | residue | summary, ``radius`` is the sphere's, by default the one of the statistics mode; local: atom | residue | summary under the module's window, no other option applies; fourier: shell | summary, ``shells`` resolution shells; mask: shell | summary, ``shells`` resolution shells; refine: atom | summary, no option applies; fit: blob, ``type`` names the residue whose atoms are the fragment);  green / red: blob / peak / basin / shape colours (neither = blue);  numSD default 3.0 for green / red / difference / partition, else 1.5
     (singleStructure.py:65-67);  profile: ``radius`` is the profile's maxRadius, cut into ``shells`` shells;  partition: ``radius`` is the
     maximum distance of a voxel from its owner, green / red pick the blob level's lists (green alone by default);  dipole: always the fused green
     and red lists (numSD default 3.0), ``radius`` is the largest gap between the two blobs when given (else 2.5 A);  radius default 3.5 elsewhere."""

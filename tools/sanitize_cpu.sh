@@ -39,3 +39,6 @@ python3 -m pytest tests/test_spherebox_host.py -q -p no:cacheprovider
 # tests/test_gradient_plan_host.py builds the harness under ASan + UBSan itself, writes the cases and compares every line
 echo "atom-moment planner, -fsanitize=address,undefined,float-cast-overflow:"
 python3 -m pytest tests/test_gradient_plan_host.py -q -p no:cacheprovider
+# The host's plan of pdbeda_pose_scores (pdb_eda_amd/csrc/pdbeda_poseplan.h) on tests/pose_harness.cpp, the same way
+echo "pose planner, -fsanitize=address,undefined,float-cast-overflow:"
+python3 -m pytest tests/test_pose_plan_host.py -q -p no:cacheprovider
